@@ -17,6 +17,19 @@ Scaling modes.  Default (weak): every rank processes its own `--frames`-frame sh
 T frames are cut into contiguous shards (distributed.shard_range), every rank runs its shard and
 all ranks receive all T results (distributed.all_gather_results).
 
+Plain run and --full.  A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what `value` needs: set-up,
+W warm-up steps, ONE timed region of exactly N steps, the outputs of its last step if `--dump-outputs DIR` is given,
+and the JSON line.  Everything else described below -- the further timed regions of the headline (value = their
+median), io_inclusive, json_inclusive, dropin_loop, the MLP's accuracy modes, the kernel-level roofline pass, the
+parity sample and the CPU baseline, the gather check after the timed region -- runs with `--full` only; in a plain
+run those fields of the line are null.
+
+--dump-outputs DIR.  After the timed region: what its last step returned, as a caller of the path receives it (with
+N > 1 ranks: the gathered result, written by rank 0), in DIR/poses.npy ([frames, persons capacity, joints, 3]; float32
+for the MLP path, float64 for DLT; slots past a frame's person count zeroed: they hold no result), DIR/n_persons.npy
+and DIR/frame_index.npy (float64).  Beyond 64 MB, a fixed seeded sample of the frames (frame_index says which).  The
+frames and weights are hash-generated, so the same arguments give the same inputs on every run.
+
 What is timed.  `value` = whole-job frames/s with the packed 2D skeletons already resident in HBM
 when the timed region starts and the poses left in HBM (barrier + synchronize on both sides, max
 over ranks; the bench contract's definition -- "inputs already resident in HBM when the timed region
@@ -66,6 +79,9 @@ PKG = '3d_multi_pose_estimator_amd'
 PEAK_FP32_MFMA_TFLOPS = 157.3
 PEAK_BF16_MFMA_TFLOPS = 2500.0      # dense (MI355X_MICROARCH.md; the 5 PF headline figure includes 2:1 sparsity)
 PEAK_HBM_TBS = 8.0
+DUMP_BYTES = 64 * 10 ** 6 - 4096      # --dump-outputs: at most 64 MB in all (the .npy headers included)
+
+
 def traffic_files():
     """profiles/rNN_pmc_traffic.json, newest round first (the record of THIS round when its profile pass has been committed)."""
     import glob
@@ -83,7 +99,13 @@ def parse_args(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=300)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--regions', type=int, default=3, help='timed regions of --steps steps each; value = the median region')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: further timed regions, io / JSON / drop-in regions, accuracy modes, kernel-level '
+                         'roofline, parity sample and CPU baseline (a plain run times --steps steps once and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (poses, person counts) to DIR/*.npy')
+    ap.add_argument('--regions', type=int, default=None,
+                    help='timed regions of --steps steps each; value = the median region (default: 1, with --full 3)')
     ap.add_argument('--frames', type=int, default=1000, help='frames per rank and step (weak scaling)')
     ap.add_argument('--total-frames', type=int, default=0,
                     help='strong scaling: this many frames per step in total, sharded over the ranks (configs[3]: 100000 with --persons 10)')
@@ -425,18 +447,22 @@ def run_rank(args):
     for _ in range(args.warmup):
         step()
 
-    # The headline region is timed `--regions` times (3) in this process, each EXACTLY --steps steps between barrier + synchronize;
-    # `value` is the MEDIAN region, value_min / value_max the slowest / fastest: one region of 20 steps is 75 ms, and a single
-    # sample of it moved by 2 % between boards and runs without any code change (BENCH_r04 / r05).
+    # The headline region is timed `--regions` times in this process (a plain run: once; --full: 3), each EXACTLY --steps steps
+    # between barrier + synchronize; `value` is the MEDIAN region, value_min / value_max the slowest / fastest: one region of 20
+    # steps is 75 ms, and a single sample of it moved by 2 % between boards and runs without any code change (BENCH_r04 / r05).
+    n_regions = args.regions if args.regions is not None else (3 if args.full else 1)
     regions = []
-    for _ in range(max(1, args.regions)):
+    for _ in range(max(1, n_regions)):
         dt_r, (poses, n_persons) = timed(lambda i: step(), args.steps)
         regions.append(dt_r)
     elapsed = sorted(regions)[len(regions) // 2]
 
+    if args.dump_outputs:                    # the last timed step's results (timed() ended with a device synchronize)
+        dump_outputs(args.dump_outputs, np, torch, dmod, gather, poses, n_persons, distributed, rank, world, cap, total, strong)
+
     # the exchange once more, checked: every rank finds its own shard, bit for bit, at its place in what it received
     gathered_ok = None
-    if distributed:
+    if distributed and args.full:
         for s_ in [s_match, s_3d] + ctx_streams:
             if s_ is not None:
                 torch.cuda.current_stream(device).wait_stream(s_)
@@ -444,7 +470,7 @@ def run_rank(args):
 
     # ---- kernel-level pass: one stream, HIP event pairs around the GEMM launches of every n-th step ----
     prof = None
-    if not args.no_profile and args.profile_steps > 0:
+    if args.full and not args.no_profile and args.profile_steps > 0:
         every = max(1, args.profile_every)
         for s_ in [s_match, s_3d] + ctx_streams:
             if s_ is not None:
@@ -466,7 +492,7 @@ def run_rank(args):
     # ---- the MLP's maximum-accuracy mode (f64 flush per K stage) beside the default: same region, same engine mode, fewer steps ----
     max_acc = None
     plain_parity_path = args.mode == 'mlp' and not (args.reduced or args.cfg4 or args.bf16_mlp or args.fast_mlp or args.mlp_fp32_mfma)
-    if plain_parity_path and not distributed and args.steps >= 10 and not args.no_accuracy_modes:
+    if args.full and plain_parity_path and not distributed and args.steps >= 10 and not args.no_accuracy_modes:
         for s_ in [s_match, s_3d] + ctx_streams:
             if s_ is not None:
                 torch.cuda.current_stream(device).wait_stream(s_)
@@ -496,15 +522,15 @@ def run_rank(args):
 
     # ---- contract form: pinned host -> H2D -> compute -> D2H into pinned host, double-buffered ----
     io = None
-    if not args.no_io:
+    if args.full and not args.no_io:
         io = io_inclusive(args, torch, dist, packing, engs, pb, device, stage3d, gather, timed, distributed, total)
     jsn = None
-    if (not args.no_io or os.environ.get('MPE_BENCH_JSON_WITHOUT_IO')) and args.json_steps > 0 and not distributed:
+    if args.full and (not args.no_io or os.environ.get('MPE_BENCH_JSON_WITHOUT_IO')) and args.json_steps > 0 and not distributed:
         jsn = json_inclusive(args, torch, eng, wire, B, uniq, K)
 
     # ---- the reference's own call pattern: ONE frame per call through the drop-in mirrors (metrics_from_model.py:178-294) ----
     dropin = None
-    if args.dropin_frames > 0 and not distributed and args.preset == 'PANOPTIC' and args.mode == 'mlp' and not (args.reduced or args.cfg4 or args.bf16_mlp):
+    if args.full and args.dropin_frames > 0 and not distributed and args.preset == 'PANOPTIC' and args.mode == 'mlp' and not (args.reduced or args.cfg4 or args.bf16_mlp):
         loop = importlib.import_module(PKG + '.harness.dropin_loop')
         model_, mlp_ = loop.build_models(gat_sd, prm, mlp_sd)
         n_dl = args.dropin_frames
@@ -528,7 +554,7 @@ def run_rank(args):
     reduced = args.reduced or args.bf16_mlp or args.cfg4
     out = {
         'metric': 'frames/sec (5-view Panoptic, 4 persons) at 1/2/4/8 GPUs; MPJPE vs ref',
-        'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'full': args.full,
         'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'strong' if strong else 'weak',
         'value_min': total * args.steps / max(regions), 'value_max': total * args.steps / min(regions),
         'timed_regions': {'n': len(regions), 'steps_each': args.steps, 'ms_per_step': [1e3 * r / args.steps for r in regions],
@@ -578,8 +604,8 @@ def run_rank(args):
     }
     if rank == 0:
         out['roofline'] = roofline(args, prof, elapsed, total, world, V, J, args.persons, reduced)
-        # the CPU baseline and the parity sample are taken on rank 0 at N = 1 only
-        base, par_ = (None, None) if world > 1 else cpu_baseline_and_parity(args, np, torch, calib, params, lo, device)
+        # the CPU baseline and the parity sample are taken on rank 0 at N = 1 only, with --full
+        base, par_ = (None, None) if world > 1 or not args.full else cpu_baseline_and_parity(args, np, torch, calib, params, lo, device)
         out['cpu_baseline'] = base
         if par_ is not None and max_acc is not None and par_.get('mlp_max_accuracy') is not None:
             par_['mlp_max_accuracy'].update({'frames_per_s': max_acc['value'], 'frames_per_s_default_mode': value,
@@ -607,6 +633,35 @@ def check_gather(torch, dist, gather, poses, n_persons, rank, cap, B, device):
     t = torch.tensor([1 if ok else 0], dtype=torch.int32, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MIN)
     return bool(t.item())
+
+
+def dump_outputs(out_dir, np, torch, dmod, gather, poses, n_persons, distributed, rank, world, cap, total, strong):
+    """--dump-outputs: the poses and person counts of the last timed step as a caller receives them.  With N > 1 ranks
+    every rank takes part in one more all-gather and rank 0 writes the frames of all shards, in global frame order.
+    Slots past a frame's person count are zeroed (torch.empty: they hold no result); beyond DUMP_BYTES a fixed seeded
+    sample of the frames is written, frame_index says which."""
+    if distributed:
+        gp, gn = gather(poses, n_persons)
+        rows = []
+        for r in range(world):
+            r_lo, r_hi, _ = dmod.shard_range(total, r, world) if strong else (r * cap, (r + 1) * cap, cap)
+            rows.append(torch.arange(r * cap, r * cap + (r_hi - r_lo), device=gp.device))
+        rows = torch.cat(rows)
+        poses, n_persons = gp[rows], gn[rows]
+    if rank != 0:
+        return
+    p = poses.cpu().numpy()
+    n = n_persons.cpu().numpy().astype(np.int64)
+    live = np.arange(p.shape[1])[None, :] < n[:, None]
+    p = np.where(live[:, :, None, None], p, np.zeros((), p.dtype)).astype(np.float64 if p.dtype == np.float64 else np.float32)
+    idx = np.arange(p.shape[0])
+    per_frame = p[:1].nbytes + 2 * 8
+    if len(idx) * per_frame > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(len(idx), DUMP_BYTES // per_frame, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'poses.npy'), np.ascontiguousarray(p[idx]))
+    np.save(os.path.join(out_dir, 'n_persons.npy'), n[idx].astype(np.float64))
+    np.save(os.path.join(out_dir, 'frame_index.npy'), idx.astype(np.float64))
 
 
 def io_inclusive(args, torch, dist, packing, engs, pb, device, stage3d, gather, timed, distributed, total):

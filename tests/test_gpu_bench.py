@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,7 @@ def test_rank_body_under_a_forced_process_group_matches_the_plain_run():
     the barrier pair around the timed region, all_gather_results and the all-reduce(MAX) of the time all execute on the
     card; the reported workload, step count and parity fields are identical and the throughput is the same to within
     the all-gather's cost."""
-    args = ('--gpus', '1', '--steps', '40', '--warmup', '5', '--frames', '256', '--cpu-sample', '4', '--json-steps', '0', '--no-io',
+    args = ('--gpus', '1', '--steps', '40', '--warmup', '5', '--full', '--frames', '256', '--cpu-sample', '4', '--json-steps', '0', '--no-io',
             '--profile-steps', '4')
     plain = _bench({}, *args)
     forced = _bench({'MPE_BENCH_FORCE_DIST': '1', 'WORLD_SIZE': '1', 'RANK': '0', 'LOCAL_RANK': '0', 'MASTER_ADDR': '127.0.0.1',
@@ -55,3 +56,24 @@ def test_rank_body_under_a_forced_process_group_matches_the_plain_run():
     # re-synchronised the step would show as a large drop
     # (measured 0.93-0.97 with the production GEMM; 0.80 with the slow register-staged kernel of the switch matrix)
     assert forced['value'] >= 0.65 * plain['value'], (forced['value'], plain['value'])
+
+
+def test_plain_run_times_steps_once_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): one timed region of exactly --steps steps, the fields that need --full null; --dump-outputs
+    writes the last timed step's poses and person counts, and a second run with the same arguments writes the same bits."""
+    args = ('--gpus', '1', '--steps', '7', '--warmup', '2', '--frames', '64')
+    runs = []
+    for k in range(2):
+        out = tmp_path / ('dump%d' % k)
+        d = _bench({}, *args, '--dump-outputs', str(out))
+        assert d['full'] is False and d['steps'] == 7 and d['warmup'] == 2 and d['unit'] == 'frames/s' and d['dtype'] == 'f32'
+        assert d['timed_regions']['n'] == 1 and d['timed_regions']['steps_each'] == 7
+        assert d['value'] > 0 and abs(d['value'] - 64 / (d['ms_per_step'] * 1e-3)) <= 1e-6 * d['value']
+        for key in ('roofline', 'cpu_baseline', 'parity', 'io_inclusive', 'json_inclusive', 'dropin_loop'):
+            assert d[key] is None, key
+        poses, n = np.load(out / 'poses.npy'), np.load(out / 'n_persons.npy')
+        assert poses.dtype == np.float32 and poses.shape[0] == 64 and poses.shape[2:] == (18, 3) and n.dtype == np.float64
+        assert np.array_equal(np.load(out / 'frame_index.npy'), np.arange(64.0))
+        assert n.min() >= 1 and n.max() <= 4 and np.isfinite(poses).all() and np.abs(poses).max() > 0
+        runs.append((poses, n))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])

@@ -512,6 +512,30 @@ def test_bench_reads_the_newest_pmc_traffic_record():
     assert names and sorted(names) == have and names[0] == have[-1]
 
 
+def test_bench_dump_outputs_writes_the_live_results_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: poses (float32, or float64 for DLT) with the slots past a frame's person count zeroed, person
+    counts and frame indices as float64; an output beyond 64 MB is cut to a fixed seeded sample of frames, the same on every run."""
+    bench = _bench_module()
+    for frames, dtype in ((500, torch.float32), (3000, torch.float64), (100000, torch.float32)):
+        poses = torch.randn(frames, 10, 18, 3, dtype=dtype)
+        n = torch.randint(0, 11, (frames,), dtype=torch.int32)
+        written = []
+        for k in range(2):
+            out = tmp_path / ('%d_%d' % (frames, k))
+            bench.dump_outputs(str(out), np, torch, None, None, poses, n, False, 0, 1, frames, frames, False)
+            assert sorted(os.listdir(out)) == ['frame_index.npy', 'n_persons.npy', 'poses.npy']
+            assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 10 ** 6
+            p, c, idx = (np.load(out / f) for f in ('poses.npy', 'n_persons.npy', 'frame_index.npy'))
+            assert p.dtype == (np.float64 if dtype == torch.float64 else np.float32) and c.dtype == idx.dtype == np.float64
+            rows = idx.astype(np.int64)
+            assert len(rows) == len(p) == len(c) and (len(rows) == frames) == (frames < 100000)
+            assert np.array_equal(rows, np.unique(rows)) and np.array_equal(c, n.numpy()[rows])
+            live = np.arange(10)[None, :] < c[:, None]
+            assert np.array_equal(p[live], poses.numpy()[rows][live]) and not p[~live].any()
+            written.append(p)
+        assert np.array_equal(written[0], written[1])
+
+
 def test_projection_helpers_match_reference_formulas():
     """pose_estimator_utils.apply_distortion / from_homogeneous(2) / get_distortion_coefficients:
     host-side tensor helpers of the reprojection check (reference pose_estimator_utils.py:32-50).

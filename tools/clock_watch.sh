@@ -1,7 +1,7 @@
 # shader clock and socket power while the default bench runs (3000 steps = 17 s): is the GEMM power-limited?
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/clk; mkdir -p $O
 cd $R
-python bench.py --steps 3000 --warmup 20 --cpu-sample 0 --no-io > $O/bench.json 2> $O/bench.err &
+python bench.py --full --steps 3000 --warmup 20 --cpu-sample 0 --no-io > $O/bench.json 2> $O/bench.err &
 BP=$!
 for i in $(seq 1 40); do
   printf "%s " "$(date +%S.%N | cut -c1-5)"

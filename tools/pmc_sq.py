@@ -1,7 +1,7 @@
 """rocprofv3 SQ-counter pass -> per-kernel summary (LDS bank-conflict share, MFMA busy share).
 
     rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE \
-              --output-format csv -d DIR -o sq -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-io
+              --output-format csv -d DIR -o sq -- python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --no-io
     python tools/pmc_sq.py DIR/sq_counter_collection.csv out.json
 
 lds_conflict_share = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE (extra LDS-array cycles / all LDS-array

@@ -1,7 +1,7 @@
 """rocprofv3 PMC passes -> profiles/r01_pmc_traffic.json (fabric bytes per launch and kernel).
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR -o fetch -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d DIR -o write -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR -o fetch -- python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d DIR -o write -- python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0
     python tools/pmc_traffic.py DIR/fetch_counter_collection.csv DIR/write_counter_collection.csv out.json
 
 Units and corrections as MI355X_MICROARCH.md prescribes: FETCH_SIZE / WRITE_SIZE count KiB;
@@ -23,7 +23,7 @@ def per_kernel(path, counter):
 
 fetch, n_f = per_kernel(sys.argv[1], 'FETCH_SIZE')
 write, n_w = per_kernel(sys.argv[2], 'WRITE_SIZE')
-out = {'command': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0',
+out = {'command': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0',
        'note': 'FETCH_SIZE/WRITE_SIZE are KiB; corrected bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950 FETCH_SIZE x2); Infinity-Cache hits are counted: fabric traffic, an upper bound on HBM traffic',
        'kernels': {}}
 lin_bytes, lin_n = 0.0, 0

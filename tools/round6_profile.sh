@@ -19,22 +19,22 @@ print('$1', round(d['value'],1), 'frames/s', round(d['ms_per_step'],4),'ms', 'mi
 if [ "$1" = F1 ]; then
   TAG=${2:-base}
   X="--json-steps 0 --dropin-frames 0 --cpu-sample 0 --no-accuracy-modes"
-  timeout -k 10 300 python bench.py --frames 1 --steps 400 --warmup 40 $X > $O/bench_1frame_$TAG.json 2> $O/bench_1frame_$TAG.err || { tail -5 $O/bench_1frame_$TAG.err; exit 1; }; show 1frame_$TAG
-  timeout -k 10 300 python bench.py --frames 1 --contexts 1 --streams 1 --steps 400 --warmup 40 $X > $O/bench_1frame_s1_$TAG.json 2>> $O/bench_1frame_$TAG.err || exit 1; show 1frame_s1_$TAG
-  timeout -k 10 300 python bench.py --frames 8 --contexts 1 --streams 1 --steps 400 --warmup 40 $X > $O/bench_8frame_s1_$TAG.json 2>> $O/bench_1frame_$TAG.err || exit 1; show 8frame_s1_$TAG
+  timeout -k 10 300 python bench.py --full --frames 1 --steps 400 --warmup 40 $X > $O/bench_1frame_$TAG.json 2> $O/bench_1frame_$TAG.err || { tail -5 $O/bench_1frame_$TAG.err; exit 1; }; show 1frame_$TAG
+  timeout -k 10 300 python bench.py --full --frames 1 --contexts 1 --streams 1 --steps 400 --warmup 40 $X > $O/bench_1frame_s1_$TAG.json 2>> $O/bench_1frame_$TAG.err || exit 1; show 1frame_s1_$TAG
+  timeout -k 10 300 python bench.py --full --frames 8 --contexts 1 --streams 1 --steps 400 --warmup 40 $X > $O/bench_8frame_s1_$TAG.json 2>> $O/bench_1frame_$TAG.err || exit 1; show 8frame_s1_$TAG
   cd /tmp; export TMPDIR=/tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_1f_$TAG -o run -- python3 $R/bench.py --frames 1 --contexts 1 --streams 1 --steps 200 --warmup 20 $X --no-io --no-profile > $O/bench_1frame_s1_${TAG}_under_rocprof.json 2> $O/stats_1f_$TAG.err; echo "stats rc $?"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_1f_$TAG -o run -- python3 $R/bench.py --full --frames 1 --contexts 1 --streams 1 --steps 200 --warmup 20 $X --no-io --no-profile > $O/bench_1frame_s1_${TAG}_under_rocprof.json 2> $O/stats_1f_$TAG.err; echo "stats rc $?"
   python3 $R/tools/launch_gaps.py $O/stats_1f_$TAG/run_kernel_trace.csv 200 > $O/1frame_${TAG}_launch_gaps.txt 2>&1; cat $O/1frame_${TAG}_launch_gaps.txt
   rm -f $O/stats_1f_$TAG/run_kernel_trace.csv
 fi
 if [ "$1" = A ]; then
   cd $R
-  timeout -k 10 500 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }; show default
-  timeout -k 10 300 python bench.py --contexts 1 --streams 1 --json-steps 0 --dropin-frames 0 > $O/bench_streams1.json 2>> $O/bench_default.err || exit 1; show streams1
+  timeout -k 10 500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }; show default
+  timeout -k 10 300 python bench.py --full --contexts 1 --streams 1 --json-steps 0 --dropin-frames 0 > $O/bench_streams1.json 2>> $O/bench_default.err || exit 1; show streams1
   cd /tmp; export TMPDIR=/tmp
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -o run -- python3 $R/bench.py --contexts 1 --streams 1 --json-steps 0 --no-io --cpu-sample 0 --dropin-frames 0 --no-accuracy-modes > $O/bench_streams1_under_rocprof.json 2> $O/stats1.err; echo "stats (one stream) rc $?"
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -o run -- python3 $R/bench.py --full --contexts 1 --streams 1 --json-steps 0 --no-io --cpu-sample 0 --dropin-frames 0 --no-accuracy-modes > $O/bench_streams1_under_rocprof.json 2> $O/stats1.err; echo "stats (one stream) rc $?"
   rm -f $O/stats*/run_kernel_trace.csv
-  for C in FETCH_SIZE WRITE_SIZE; do timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/pmc -o $C -- python3 $R/bench.py --contexts 1 --streams 1 --steps 3 --warmup 1 --cpu-sample 0 --no-io --json-steps 0 --no-profile --dropin-frames 0 > /dev/null 2> $O/$C.err; echo "$C rc $?"; done
+  for C in FETCH_SIZE WRITE_SIZE; do timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/pmc -o $C -- python3 $R/bench.py --full --contexts 1 --streams 1 --steps 3 --warmup 1 --cpu-sample 0 --no-io --json-steps 0 --no-profile --dropin-frames 0 > /dev/null 2> $O/$C.err; echo "$C rc $?"; done
   python3 $R/tools/pmc_traffic.py $O/pmc/FETCH_SIZE_counter_collection.csv $O/pmc/WRITE_SIZE_counter_collection.csv $O/pmc_traffic.json
   rm -f $O/*/*_kernel_trace.csv
   python3 - <<PY
@@ -49,9 +49,9 @@ fi
 if [ "$1" = B ]; then
   cd $R
   X="--json-steps 0 --dropin-frames 0"
-  timeout -k 10 300 python bench.py --mode tri --cpu-sample 20 $X > $O/bench_tri.json 2> $O/bench_b.err; show tri
-  timeout -k 10 300 python bench.py --persons 10 --frames 500 --cpu-sample 0 --steps 30 $X > $O/bench_5x10.json 2>> $O/bench_b.err; show 5x10
-  timeout -k 10 300 python bench.py --persons 10 --total-frames 12500 --cpu-sample 0 --steps 5 --warmup 1 $X > $O/bench_c4_shard.json 2>> $O/bench_b.err; show c4_shard
-  timeout -k 10 300 python bench.py --preset RING23 --persons 10 --frames 96 --cpu-sample 0 --steps 6 --warmup 2 $X > $O/bench_ring96.json 2>> $O/bench_b.err; show ring96
-  timeout -k 10 300 python bench.py --frames 1 --cpu-sample 0 --steps 400 --warmup 40 $X > $O/bench_1frame.json 2>> $O/bench_b.err; show 1frame
+  timeout -k 10 300 python bench.py --full --mode tri --cpu-sample 20 $X > $O/bench_tri.json 2> $O/bench_b.err; show tri
+  timeout -k 10 300 python bench.py --full --persons 10 --frames 500 --cpu-sample 0 --steps 30 $X > $O/bench_5x10.json 2>> $O/bench_b.err; show 5x10
+  timeout -k 10 300 python bench.py --full --persons 10 --total-frames 12500 --cpu-sample 0 --steps 5 --warmup 1 $X > $O/bench_c4_shard.json 2>> $O/bench_b.err; show c4_shard
+  timeout -k 10 300 python bench.py --full --preset RING23 --persons 10 --frames 96 --cpu-sample 0 --steps 6 --warmup 2 $X > $O/bench_ring96.json 2>> $O/bench_b.err; show ring96
+  timeout -k 10 300 python bench.py --full --frames 1 --cpu-sample 0 --steps 400 --warmup 40 $X > $O/bench_1frame.json 2>> $O/bench_b.err; show 1frame
 fi

@@ -1,10 +1,10 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/def; mkdir -p $O
 cd $R
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/err.log || exit 1
-timeout -k 10 300 python bench.py --profile-every 1 --cpu-sample 0 > $O/bench_every1.json 2>> $O/err.log || exit 1
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/err.log || exit 1
+timeout -k 10 300 python bench.py --full --profile-every 1 --cpu-sample 0 > $O/bench_every1.json 2>> $O/err.log || exit 1
 cd /tmp; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py > $O/bench_under_rocprof.json 2> $O/stats.err; echo "stats rc $?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --full > $O/bench_under_rocprof.json 2> $O/stats.err; echo "stats rc $?"
 rm -f $O/stats/run_kernel_trace.csv
 python3 - <<PY
 import csv,json

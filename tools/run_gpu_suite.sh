@@ -6,7 +6,7 @@ cd $R
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gputest_$T.log 2>&1; rc=$?
 tail -15 $O/gputest_$T.log
 [ $rc = 0 ] || exit $rc
-timeout -k 10 300 python bench.py > $O/bench_$T.json 2> $O/bench_$T.err || { tail -5 $O/bench_$T.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench_$T.json 2> $O/bench_$T.err || { tail -5 $O/bench_$T.err; exit 1; }
 python3 - <<PY
 import json
 d = json.load(open('$O/bench_$T.json'))

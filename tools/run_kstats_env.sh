@@ -6,7 +6,7 @@ cd /tmp; export TMPDIR=/tmp
 i=0
 for E in "$@"; do i=$((i+1))
   rm -rf $O/s$i
-  env $E timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s$i -o run -- python3 $R/bench.py --steps 40 --warmup 5 --cpu-sample 0 --no-io --no-profile > $O/bench$i.json 2> $O/s$i.err || { tail -3 $O/s$i.err; exit 1; }
+  env $E timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s$i -o run -- python3 $R/bench.py --full --steps 40 --warmup 5 --cpu-sample 0 --no-io --no-profile > $O/bench$i.json 2> $O/s$i.err || { tail -3 $O/s$i.err; exit 1; }
   rm -f $O/s$i/run_kernel_trace.csv
   echo "== $E"
   python3 - <<PY

@@ -1306,6 +1306,23 @@ int mpe_triangulate_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const 
     return MPE_OK;
 }
 
+int mpe_eval_batch(mpe_ctx *ctx, void *stream, const mpe_eval_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_eval_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames < 0 || a->pcap < 1 || a->gcap < 1 || a->n_joints < 1 || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_eval_batch: bad sizes or modes");
+    if (a->pcap > 1024 || a->gcap > 1024 || a->n_joints > MPE_MAX_JOINTS)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_eval_batch: pcap %d / gcap %d / joints %d over 1024 / 1024 / %d", a->pcap,
+                    a->gcap, a->n_joints, MPE_MAX_JOINTS);
+    if (a->n_frames == 0) return MPE_OK;
+    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_gt_xyz || !a->d_gt_joint || !a->d_n_gt_in || !a->d_table ||
+        !a->d_assign || !a->d_err || !a->d_invalid || !a->d_n_gt || !a->d_n_res || !a->d_status)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_eval_batch: NULL argument");
+    HIPCHK(ctx, launch_eval(static_cast<hipStream_t>(stream), *a));
+    return MPE_OK;
+}
+
 int mpe_dlt_pairs(mpe_ctx *ctx, void *stream, const double *d_pts, const int32_t *d_cams, int32_t n, double *d_out) {
     if (!ctx) return MPE_ERR_INVALID;
     DeviceGuard dg(ctx);

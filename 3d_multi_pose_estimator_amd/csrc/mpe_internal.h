@@ -299,4 +299,7 @@ hipError_t launch_decode(hipStream_t s, int n_frames, int pcap, int n_out, float
                          const int32_t *person_off, const float *y, int ld_y, float *poses);
 int cluster_table_cap(int hmax);
 
+// eval.hip
+hipError_t launch_eval(hipStream_t s, const mpe_eval_args &a);
+
 }  // namespace mpe

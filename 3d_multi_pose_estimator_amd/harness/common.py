@@ -23,8 +23,10 @@ import torch
 
 from .. import synthetic
 from ..calibration import Calibration, load_transform_manager
+from ..lib import MPE_EVAL_NO_ASSIGNMENT, MPE_EVAL_OVER_BUDGET, MPE_EVAL_OVER_CAP, MPE_EVAL_SKIPPED
 from ..parameters import parameters
 from ..pipeline import Engine
+from .assignment import assign_bnb, frame_records
 
 THRESHOLDS_MM = np.arange(25, 155, 25)
 
@@ -48,6 +50,8 @@ def build_parser(description):
                    help='f64 running sums in every GEMM of the matching network (Engine.set_precision(gat_acc64=True); default: single fp32 chains for K <= 512)')
     p.add_argument('--mlp-precision', choices=['default', 'max_accuracy', 'f64'], default='default',
                    help='MLP mode 3 (default: f64 sums every second K stage), 4 (an f64 flush per stage) or 5 (the network evaluated on the f64 matrix pipe)')
+    p.add_argument('--device-metrics', action='store_true',
+                   help='error tables and pose-to-GT assignment on the GPU (mpe_eval_batch): the same report, the poses stay on the device')
     return p
 
 
@@ -107,6 +111,31 @@ def ground_truth(frame, T_dataset_cam1, T_i_cam1):
         gts.append({j: world[j].numpy() for j in parameters.joint_list if str(j) in body})
         valid.append('-1' in body)
     return gts, valid
+
+
+def pack_ground_truth(frames, T_d1s, T_i1):
+    """ground_truth() of every frame, packed for mpe_eval_batch: {'xyz': [B,Gcap,J,3] f32 world, 'joint': [B,Gcap,J] u8
+    (joint given for the body), 'valid': [B,Gcap] u8 ('-1' in the body), 'n': [B] i32 (0: no GT bodies, the frame the
+    callers skip)}; Gcap = the largest body count, at least 1.  The values are ground_truth()'s own, bit for bit; like
+    it, raises SystemExit for a frame without a GT field."""
+    J = len(parameters.joint_list)
+    if list(parameters.joint_list) != list(range(J)):
+        raise ValueError('pack_ground_truth: joint_list must be range(J)')
+    per = [ground_truth(f, T, T_i1) for f, T in zip(frames, T_d1s)]
+    B = len(per)
+    gcap = max([1] + [len(g[0]) for g in per if g is not None])
+    out = {'xyz': np.zeros((B, gcap, J, 3), np.float32), 'joint': np.zeros((B, gcap, J), np.uint8),
+           'valid': np.zeros((B, gcap), np.uint8), 'n': np.zeros(B, np.int32)}
+    for f, g in enumerate(per):
+        if g is None:
+            continue
+        out['n'][f] = len(g[0])
+        for b, (body, ok) in enumerate(zip(*g)):
+            out['valid'][f, b] = ok
+            for j, xyz in body.items():
+                out['xyz'][f, b, j] = xyz
+                out['joint'][f, b, j] = 1
+    return out
 
 
 class Metrics:
@@ -194,6 +223,51 @@ class Metrics:
         return out
 
 
+class DeviceMetrics(Metrics):
+    """Metrics fed by mpe_eval_batch instead of per-frame dicts: the table and the assignment come from the device
+    (harness/assignment.py states them), the bookkeeping of Metrics.add_frame runs vectorised over the records of a
+    batch in frame order, then detection order -- TP / FP per threshold, n_gt -= 1 for a match to an invalid GT body,
+    the triangulation script's invalid detections as false positives -- and the MPJPE sum is a sequential np.cumsum
+    (the host's left fold).  report() is Metrics.report()."""
+
+    def add_batch(self, ev, gt_valid, triangulation=False):
+        """ev: Engine.evaluate's tensors; gt_valid [B,Gcap] (pack_ground_truth's 'valid').  Frames the device search
+        declined (over 64 rows or columns, over its node budget) are finished here by assignment.assign_bnb on the
+        device's table.  -> the host records {'n_gt','n_res','status','assign','err','invalid'}."""
+        h = {k: ev[k].cpu().numpy() for k in ('n_gt', 'n_res', 'status', 'assign', 'err', 'invalid')}
+        for f in np.flatnonzero(h['status'] & (MPE_EVAL_OVER_CAP | MPE_EVAL_OVER_BUDGET)):
+            G, R = int(h['n_gt'][f]), int(h['n_res'][f])
+            table = ev['table'][f, :G, :R].cpu().numpy()
+            best_p = assign_bnb(table)
+            if best_p is None:
+                h['status'][f] |= MPE_EVAL_NO_ASSIGNMENT
+            h['assign'][f, :R], h['err'][f, :R] = frame_records(table, best_p)
+        keep = (h['status'] & MPE_EVAL_SKIPPED) == 0
+        if np.any(keep & (h['status'] & MPE_EVAL_NO_ASSIGNMENT != 0) & (h['n_res'] > 0)):
+            raise RuntimeError('no assignment sums below 10000 (the reference loop fails on such a frame)')
+        n_res = h['n_res'].astype(np.int64)
+        self.n_poses += int(n_res[keep].sum())
+        self.n_gt += int(h['n_gt'][keep].sum())
+        rec = keep[:, None] & (np.arange(h['assign'].shape[1])[None, :] < n_res[:, None])
+        fr = np.nonzero(rec)[0]
+        g, e, inv = h['assign'][rec], h['err'][rec], h['invalid'][rec] != 0
+        has = g >= 0
+        vg = np.zeros(len(g), bool)
+        vg[has] = np.asarray(gt_valid, bool)[fr[has], g[has]]
+        matched = has & vg
+        self.n_matching += int(matched.sum())
+        if matched.any():
+            self.acc_err = np.cumsum(np.concatenate(([self.acc_err], e[matched])))[-1]
+        self.n_gt -= int((has & ~vg).sum())
+        cond = has & ~inv if triangulation else has
+        kept = ~(cond & ~vg)
+        for k, th in enumerate(THRESHOLDS_MM):
+            tp = (cond & (e * 1000. < th))[kept].astype(np.int64)
+            self.TP[k].extend(tp.tolist())
+            self.FP[k].extend((1 - tp).tolist())
+        return h
+
+
 def teacher_scores(db, owners):
     """Ground-truth pairing as scores: 1 for two views of one person, 0 otherwise."""
     from ..packing import pairs_of_frame
@@ -265,6 +339,29 @@ def evaluate(work, infer, mode, T_i1, batch=256):
     return metrics, n_data, n_results
 
 
+def evaluate_on_device(work, infer, mode, T_i1, batch=256):
+    """evaluate() with --device-metrics: `infer(frames, owners, gt)` runs the inference path and Engine.evaluate on
+    the device and returns its tensors; the frames and the skip rules are evaluate()'s.  Returns (DeviceMetrics,
+    n_data, n_results)."""
+    metrics = DeviceMetrics()
+    n_data = n_results = 0
+    for start in range(0, len(work), batch):
+        chunk = work[start:start + batch]
+        gt = pack_ground_truth([w[0] for w in chunk], [w[1] for w in chunk], T_i1)
+        sel = np.flatnonzero(gt['n'] > 0)
+        if not len(sel):
+            continue
+        gt = {k: v[sel] for k, v in gt.items()}
+        keep = [chunk[i] for i in sel]
+        frames = [{c: [frame[c][0], frame[c][1]] for c in frame if json.loads(frame[c][0])} for frame, _, _ in keep]
+        ev = infer(frames, [o for _, _, o in keep], gt)
+        h = metrics.add_batch(ev, gt['valid'], triangulation=(mode != 'mlp'))
+        done = (h['status'] & MPE_EVAL_SKIPPED) == 0
+        n_data += int(done.sum())
+        n_results += int(h['n_res'][done].sum())
+    return metrics, n_data, n_results
+
+
 def max_skeletons_per_camera(work):
     """Largest skeleton list of any camera in the selected frames: sizes the engine's per-frame
     capacity (the reference has no such limit; its graphs simply grow)."""
@@ -324,7 +421,35 @@ def run(args, mode):
             out.append(results)
         return out
 
-    metrics, n_data, n_results = evaluate(work, infer, mode, T_i1, args.batch)
+    def infer_device(frames, owners, gt):
+        db = eng.to_device(eng.pack(frames))
+        torch.cuda.synchronize()
+        t0 = time.time()
+        if args.teacher_scores and owners[0] is not None:
+            persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
+        else:
+            _, persons, n_persons = eng.match(db, want_scores=False)
+        torch.cuda.synchronize()
+        t1 = time.time()
+        if mode == 'mlp':
+            poses, flags = eng.mlp3d(db, persons, n_persons)
+        else:
+            poses, flags = eng.triangulate(db, persons, n_persons)
+        torch.cuda.synchronize()
+        t2 = time.time()
+        ev = eng.evaluate(db, poses, flags, n_persons, gt, mode)
+        torch.cuda.synchronize()
+        t['match'] += t1 - t0
+        t['3d'] += t2 - t1
+        t['eval'] += time.time() - t2
+        eng.sync_status()
+        return ev
+
+    if getattr(args, 'device_metrics', False):
+        t['eval'] = 0.0
+        metrics, n_data, n_results = evaluate_on_device(work, infer_device, mode, T_i1, args.batch)
+    else:
+        metrics, n_data, n_results = evaluate(work, infer, mode, T_i1, args.batch)
     out = metrics.report()
     if n_data > 0:
         print('Mean time for graph matching', t['match'] / n_data)
@@ -332,6 +457,8 @@ def run(args, mode):
         print('Mean time for 3D', t['3d'] / n_data)
         print('Mean time for 3D (per person)', t['3d'] / max(1, n_results))
         print('Frames per second', n_data / max(1e-9, t['match'] + t['3d']))
+        if 'eval' in t:
+            print('Mean time for evaluation on the device', t['eval'] / n_data)
     out['n_data'] = n_data
     eng.close()
     return out

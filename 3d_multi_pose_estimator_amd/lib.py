@@ -74,6 +74,19 @@ class mpe_pack_dst(C.Structure):
                 ('xy', C.c_void_p), ('vp', C.c_void_p)]
 
 
+class mpe_eval_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('gcap', C.c_int32),
+                ('pose_f64', C.c_int32), ('joint_flags', C.c_int32), ('used_joint_mask', C.c_uint32),
+                ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_gt_xyz', C.c_void_p),
+                ('d_gt_joint', C.c_void_p), ('d_gt_valid', C.c_void_p), ('d_n_gt_in', C.c_void_p), ('d_skip', C.c_void_p),
+                ('d_table', C.c_void_p), ('d_assign', C.c_void_p), ('d_err', C.c_void_p), ('d_invalid', C.c_void_p),
+                ('d_n_gt', C.c_void_p), ('d_n_res', C.c_void_p), ('d_status', C.c_void_p)]
+
+
+# per-frame status bits of mpe_eval_batch
+MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
+
+
 # name -> (restype, argtypes); must list every symbol include/mpe.h declares
 SYMBOLS = {
     'mpe_create': (C.c_int, [C.POINTER(mpe_config), C.POINTER(C.c_void_p)]),
@@ -115,6 +128,7 @@ SYMBOLS = {
     'mpe_mlp_input_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.c_void_p]),
     'mpe_mlp_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
+    'mpe_eval_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_eval_args)]),
     'mpe_dlt_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'mpe_pack_json': (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -853,6 +853,55 @@ class Engine:
                                                  (1 if all_joints else 0) | (2 if positive_ids_only else 0)))
         return poses, jv
 
+    def evaluate(self, db, poses, flags, n_persons, gt, mode, skip=None):
+        """Error table and pose-to-ground-truth assignment of every frame on the device (mpe_eval_batch).
+        poses / flags / n_persons: what mlp3d (mode 'mlp': f32 poses, person flags) or triangulate (mode 'tri': f64
+        poses, joint flags) returned for `db`; gt: harness.common.pack_ground_truth's arrays for the same frames.  Frames
+        without a cross-camera pair (M == 0) are skipped unless `skip` ([B] bool) says otherwise.  -> dict of device
+        tensors: table [B,Gcap,Pcap] f64, assign / err / invalid [B,Pcap] (detection order), n_gt / n_res / status [B];
+        frames with MPE_EVAL_OVER_CAP / _OVER_BUDGET in status are the caller's to finish from the table."""
+        B = db.n_frames
+        if mode not in ('mlp', 'tri'):
+            raise ValueError('mode must be mlp or tri')
+        want = torch.float32 if mode == 'mlp' else torch.float64
+        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, self.J, 3):
+            raise ValueError('poses must be %s [%d,%d,%d,3]' % (want, B, self.pcap, self.J))
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap) if mode == 'mlp' else (B, self.pcap, self.J)):
+            raise ValueError('flags do not match mode %s' % mode)
+        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
+            raise ValueError('n_persons must be int32 [%d]' % B)
+        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous()):
+            raise ValueError('poses, flags and n_persons must be contiguous')
+        if gt['xyz'].shape[0] != B or np.any(np.asarray(gt['n']) > gt['xyz'].shape[1]):
+            raise ValueError('ground truth for %d frames, batch has %d' % (gt['xyz'].shape[0], B))
+        if skip is None:
+            skip = (np.diff(np.asarray(db.host.frame_en_off[:B + 1])) == 0).astype(np.uint8)
+        dev = self.device
+        gcap = max(1, gt['xyz'].shape[1])
+        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev, non_blocking=False)
+        gx = up(gt['xyz'], torch.float32) if gt['xyz'].shape[1] else torch.zeros((B, 1, self.J, 3), dtype=torch.float32, device=dev)
+        gj = up(gt['joint'], torch.uint8) if gt['xyz'].shape[1] else torch.zeros((B, 1, self.J), dtype=torch.uint8, device=dev)
+        gv = up(gt['valid'], torch.uint8) if gt['xyz'].shape[1] else torch.zeros((B, 1), dtype=torch.uint8, device=dev)
+        gn = up(gt['n'], torch.int32)
+        sk = up(np.asarray(skip, dtype=np.uint8), torch.uint8)
+        out = {'table': torch.empty((B, gcap, self.pcap), dtype=torch.float64, device=dev),
+               'assign': torch.empty((B, self.pcap), dtype=torch.int32, device=dev),
+               'err': torch.empty((B, self.pcap), dtype=torch.float64, device=dev),
+               'invalid': torch.empty((B, self.pcap), dtype=torch.uint8, device=dev)}
+        for k in ('n_gt', 'n_res', 'status'):
+            out[k] = torch.empty((B,), dtype=torch.int32, device=dev)
+        a = L.mpe_eval_args()
+        a.n_frames, a.pcap, a.n_joints, a.gcap = B, self.pcap, self.J, gcap
+        a.pose_f64, a.joint_flags = int(mode == 'tri'), int(mode == 'tri')
+        a.used_joint_mask = sum(1 << j for j in self.params.used_joints)
+        a.d_poses, a.d_flags, a.d_n_persons = poses.data_ptr(), flags.data_ptr(), n_persons.data_ptr()
+        a.d_gt_xyz, a.d_gt_joint, a.d_gt_valid, a.d_n_gt_in, a.d_skip = gx.data_ptr(), gj.data_ptr(), gv.data_ptr(), gn.data_ptr(), sk.data_ptr()
+        a.d_table, a.d_assign, a.d_err, a.d_invalid = (out[k].data_ptr() for k in ('table', 'assign', 'err', 'invalid'))
+        a.d_n_gt, a.d_n_res, a.d_status = (out[k].data_ptr() for k in ('n_gt', 'n_res', 'status'))
+        self._chk(self.lib.mpe_eval_batch(self.ctx, self._stream(), C.byref(a)))
+        out['_keep'] = (gx, gj, gv, gn, sk)          # inputs stay alive until the caller has synchronised
+        return out
+
     def dlt_pairs(self, pts, cams):
         pts = torch.as_tensor(pts, dtype=torch.float64, device=self.device).contiguous()
         cams = torch.as_tensor(cams, dtype=torch.int32, device=self.device).contiguous()

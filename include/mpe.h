@@ -218,6 +218,48 @@ int mpe_triangulate_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b,
                           const int32_t *d_persons, const int32_t *d_n_persons,
                           double *d_poses, uint8_t *d_joint_valid, uint32_t flags);
 
+/* Evaluation: error table and pose-to-ground-truth assignment of the callers' scoring loop
+ * (metrics_from_model.py:303-337, metrics_from_triangulation.py:281-320), per frame of a batch.
+ * Detections of frame f: persons p < d_n_persons[f] in order; with joint_flags == 0 (MLP mode) only those with
+ * d_flags[f][p] != 0, all joints present; with joint_flags == 1 (triangulation) all of them, joint j present when
+ * d_flags[f][p][j] != 0.  Detection r of a frame is its r-th such person.
+ *   d_table[f][g][r] f64 [n_frames][gcap][pcap]: mean over the used joints of GT body g (d_gt_joint != 0 and bit j of
+ *   used_joint_mask, increasing j) that the detection has, of |pose - gt|; 0 if there is none.  pose_f64 == 0: f32
+ *   poses, the f32 arithmetic of numpy's float32 dot / norm and a f32 mean; pose_f64 == 1: f64 poses minus the f32 GT,
+ *   f64 throughout.  d_invalid[f][r] = 1 when a used joint of any GT body is missing from detection r.
+ *   d_assign[f][r] = the GT row of detection r in the first permutation (itertools order over range(max(G, R)))
+ *   whose left-fold f64 sum is the minimum below 10000., -1 if none; d_err[f][r] = d_table[f][g][r] for that row.
+ *   d_n_gt / d_n_res / d_status per frame.  A frame with d_skip[f] != 0 (d_skip may be NULL) gets status
+ *   MPE_EVAL_SKIPPED and no rows.  The search runs on the device for max(G, R) <= 64 within a fixed node budget;
+ *   other frames get MPE_EVAL_OVER_CAP / MPE_EVAL_OVER_BUDGET and their rows of d_assign stay -1: the caller
+ *   finishes them from d_table.  MPE_ERR_CAPACITY for pcap > 1024, gcap > 1024 or n_joints > MPE_MAX_JOINTS. */
+enum {
+    MPE_EVAL_SKIPPED = 1,
+    MPE_EVAL_OVER_CAP = 2,
+    MPE_EVAL_OVER_BUDGET = 4,
+    MPE_EVAL_NO_ASSIGNMENT = 8
+};
+typedef struct {
+    int32_t n_frames, pcap, n_joints, gcap;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t used_joint_mask;
+    const void *d_poses;
+    const uint8_t *d_flags;
+    const int32_t *d_n_persons;    /* [n_frames] */
+    const float *d_gt_xyz;         /* [n_frames][gcap][J][3] world, metres */
+    const uint8_t *d_gt_joint;     /* [n_frames][gcap][J] */
+    const uint8_t *d_gt_valid;     /* [n_frames][gcap] (not read: carried for the caller's bookkeeping) */
+    const int32_t *d_n_gt_in;      /* [n_frames] bodies per frame, <= gcap */
+    const uint8_t *d_skip;         /* [n_frames] or NULL */
+    double *d_table;               /* [n_frames][gcap][pcap] */
+    int32_t *d_assign;             /* [n_frames][pcap] */
+    double *d_err;                 /* [n_frames][pcap] */
+    uint8_t *d_invalid;            /* [n_frames][pcap] */
+    int32_t *d_n_gt, *d_n_res, *d_status;   /* [n_frames] */
+} mpe_eval_args;
+int mpe_eval_batch(mpe_ctx *ctx, void *stream, const mpe_eval_args *a);
+
 /* ---- stage-level entry points (parity tests, Python mirrors of single reference symbols) */
 /* C[M][N] = act(A[M][K] * W[N][K]^T + bias): nn.Linear (+ LeakyReLU when slope_on != 0).
  * Row strides in elements; A and C device pointers, W/bias device pointers prepared by

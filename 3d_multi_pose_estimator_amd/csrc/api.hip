@@ -768,6 +768,9 @@ int mpe_create(const mpe_config *cfg, mpe_ctx **out) {
         if ((rc = dev_alloc(ctx, &ctx->en_frame, (size_t)cfg->max_edge_nodes))) break;
         if ((rc = dev_alloc(ctx, &ctx->en_pair, (size_t)cfg->max_edge_nodes * 2))) break;
         if ((rc = dev_alloc(ctx, &ctx->node_off, (size_t)cfg->max_frames + 1))) break;
+        if ((rc = dev_alloc(ctx, &ctx->res_state, (size_t)cfg->n_cameras))) break;
+        if ((rc = dev_alloc(ctx, &ctx->res_hist, (size_t)cfg->n_cameras * 2 * RESIDUAL_BINS))) break;
+        if ((rc = dev_alloc(ctx, &ctx->res_partial, (size_t)cfg->n_cameras * RESIDUAL_SUM_BLOCKS))) break;
         ctx->cl_keys_per_frame = cluster_keys_per_frame(cfg->max_heads_per_frame);
         {
             // in-edge source table of the heads: implicit topology [hmax][hmax + 1] per frame; explicit edge-node lists
@@ -1320,6 +1323,38 @@ int mpe_eval_batch(mpe_ctx *ctx, void *stream, const mpe_eval_args *a) {
         !a->d_assign || !a->d_err || !a->d_invalid || !a->d_n_gt || !a->d_n_res || !a->d_status)
         return fail(ctx, MPE_ERR_INVALID, "mpe_eval_batch: NULL argument");
     HIPCHK(ctx, launch_eval(static_cast<hipStream_t>(stream), *a));
+    return MPE_OK;
+}
+
+int mpe_reproject_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_reproject_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_reproject_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames != b->n_frames || a->pcap < 1 || a->n_joints != ctx->cfg.n_joints || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_reproject_batch: bad sizes or modes");
+    if (b->n_frames == 0) return MPE_OK;
+    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags || !a->d_res)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_reproject_batch: NULL argument");
+    HIPCHK(ctx, launch_reproject(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
+    return MPE_OK;
+}
+
+int mpe_residual_stats(mpe_ctx *ctx, void *stream, const mpe_residual_stats_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_residual_stats: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_buffers < 0 || a->n_joints < 1 || a->n_joints > MPE_MAX_JOINTS || !a->d_count || !a->d_nonfinite || !a->d_sum || !a->d_mid ||
+        (a->n_buffers && (!a->d_res || !a->n_groups)))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_residual_stats: bad argument");
+    long long total = 0;
+    for (int i = 0; i < a->n_buffers; ++i) {
+        if (a->n_groups[i] < 0 || (a->n_groups[i] && !a->d_res[i])) return fail(ctx, MPE_ERR_INVALID, "mpe_residual_stats: bad buffer %d", i);
+        if (a->n_groups[i] > (1ll << 31) / a->n_joints) return fail(ctx, MPE_ERR_CAPACITY, "mpe_residual_stats: buffer %d too large", i);
+        total += (long long)a->n_groups[i] * a->n_joints;
+    }
+    if (total >= (1ll << 32)) return fail(ctx, MPE_ERR_CAPACITY, "mpe_residual_stats: more than 2^32 - 1 entries per camera");
+    HIPCHK(ctx, launch_residual_stats(static_cast<hipStream_t>(stream), ctx->cfg.n_cameras, *a, ctx->res_state, ctx->res_hist, ctx->res_partial));
     return MPE_OK;
 }
 

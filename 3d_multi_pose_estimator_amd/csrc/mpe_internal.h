@@ -66,6 +66,17 @@ struct ProfileRec {
     int kind;          // 0 = fp32 MFMA launch (gemm.hip), 1 = split-bf16 launch (gemm_sb16.hip)
 };
 
+// reproject.hip: per-camera state of the radix select of mpe_residual_stats
+struct ResidualState {
+    unsigned long long prefix[2];  // high bits fixed so far of the lower / upper middle element
+    unsigned long long rank[2];    // rank of that element among the entries that share the prefix
+    long long count;               // entries >= 0
+    unsigned long long nonfinite;
+    double sum;
+};
+constexpr int RESIDUAL_BINS = 2048;          // 11-bit digits
+constexpr int RESIDUAL_SUM_BLOCKS = 64;      // partial sums per camera and buffer
+
 }  // namespace mpe
 
 struct mpe_ctx {
@@ -138,6 +149,9 @@ struct mpe_ctx {
     size_t head_src_cap = 0;       // entries allocated
     int x_m_cap = 0;               // explicit pair lists: edge-nodes a frame may hold (0 = mode unavailable on this context)
     int32_t *node_off = nullptr;   // [max_frames+1]
+    mpe::ResidualState *res_state = nullptr;   // mpe_residual_stats: [V]
+    uint32_t *res_hist = nullptr;              // [V][2][RESIDUAL_BINS]
+    double *res_partial = nullptr;             // [V][RESIDUAL_SUM_BLOCKS]
     uint64_t *cl_keys = nullptr;   // clustering scratch
     int32_t *cl_scratch = nullptr;
     size_t cl_keys_per_frame = 0, cl_scratch_per_frame = 0;
@@ -301,5 +315,10 @@ int cluster_table_cap(int hmax);
 
 // eval.hip
 hipError_t launch_eval(hipStream_t s, const mpe_eval_args &a);
+
+// reproject.hip
+hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);
+hipError_t launch_residual_stats(hipStream_t s, int V, const mpe_residual_stats_args &a, ResidualState *state, uint32_t *hist,
+                                 double *partial);
 
 }  // namespace mpe

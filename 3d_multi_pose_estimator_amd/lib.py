@@ -83,6 +83,18 @@ class mpe_eval_args(C.Structure):
                 ('d_n_gt', C.c_void_p), ('d_n_res', C.c_void_p), ('d_status', C.c_void_p)]
 
 
+class mpe_reproject_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float),
+                ('d_persons', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_poses', C.c_void_p), ('d_flags', C.c_void_p),
+                ('d_res', C.c_void_p)]
+
+
+class mpe_residual_stats_args(C.Structure):
+    _fields_ = [('n_buffers', C.c_int32), ('n_joints', C.c_int32), ('d_res', C.POINTER(C.c_void_p)), ('n_groups', C.POINTER(C.c_int64)),
+                ('d_count', C.c_void_p), ('d_nonfinite', C.c_void_p), ('d_sum', C.c_void_p), ('d_mid', C.c_void_p)]
+
+
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
 
@@ -129,6 +141,8 @@ SYMBOLS = {
                                      C.c_void_p, C.c_int32, C.c_void_p]),
     'mpe_mlp_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     'mpe_eval_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_eval_args)]),
+    'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
+    'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),
     'mpe_dlt_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'mpe_pack_json': (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),

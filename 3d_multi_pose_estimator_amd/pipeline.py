@@ -902,6 +902,68 @@ class Engine:
         out['_keep'] = (gx, gj, gv, gn, sk)          # inputs stay alive until the caller has synchronised
         return out
 
+    def reproject(self, db, persons, n_persons, poses, flags, kind, joint_mask=None, threshold=0.5):
+        """Reprojection residuals on the device (mpe_reproject_batch): how far every joint of every 3D pose lands from
+        the 2D detection it came from, per camera -- a quality signal that needs no ground truth.  kind 'est': what mlp3d
+        returned (f32 poses, person flags; the used joints); 'triang': what triangulate returned (f64 poses, joint flags;
+        all joints); 'gt': f32 poses with person flags and the script's one GT joint (the last of joint_list).
+        joint_mask overrides the kind's joints.  -> res [B,Pcap,V,J] f64 pixels, -1 where nothing is counted."""
+        B = db.n_frames
+        if kind not in ('est', 'triang', 'gt'):
+            raise ValueError('kind must be est, triang or gt')
+        tri = kind == 'triang'
+        want = torch.float64 if tri else torch.float32
+        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, self.J, 3):
+            raise ValueError('poses must be %s [%d,%d,%d,3]' % (want, B, self.pcap, self.J))
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, self.J) if tri else (B, self.pcap)):
+            raise ValueError('flags do not match kind %s' % kind)
+        if persons.dtype != torch.int32 or tuple(persons.shape) != (B, self.pcap, self.V):
+            raise ValueError('persons must be int32 [%d,%d,%d]' % (B, self.pcap, self.V))
+        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
+            raise ValueError('n_persons must be int32 [%d]' % B)
+        if not (poses.is_contiguous() and flags.is_contiguous() and persons.is_contiguous() and n_persons.is_contiguous()):
+            raise ValueError('persons, n_persons, poses and flags must be contiguous')
+        if joint_mask is None:
+            joint_mask = {'est': sum(1 << j for j in self.params.used_joints), 'triang': (1 << self.J) - 1,
+                          'gt': 1 << int(list(self.params.joint_list)[-1])}[kind]
+        res = torch.empty((B, self.pcap, self.V, self.J), dtype=torch.float64, device=self.device)
+        a = L.mpe_reproject_args()
+        a.n_frames, a.pcap, a.n_joints = B, self.pcap, self.J
+        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), int(joint_mask), float(threshold)
+        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
+        a.d_res = res.data_ptr()
+        self._chk(self.lib.mpe_reproject_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return res
+
+    def residual_stats(self, res_list):
+        """Per-camera statistics of one or more residual tensors [..., V, J] f64 on the device (mpe_residual_stats): the
+        exact middle elements by radix select, a sum reduced in a fixed order.  -> dict of numpy arrays over the cameras:
+        count, nonfinite (int64), sum, mean, median (NaN for a camera without entries or with a NaN entry), mid [V,2]."""
+        if isinstance(res_list, torch.Tensor):
+            res_list = [res_list]
+        res_list = list(res_list)
+        for r in res_list:
+            if r.dtype != torch.float64 or r.dim() < 2 or tuple(r.shape[-2:]) != (self.V, self.J) or not r.is_contiguous() or not r.is_cuda:
+                raise ValueError('residual buffers must be contiguous float64 device tensors [..., %d, %d]' % (self.V, self.J))
+        n = len(res_list)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.data_ptr() for r in res_list])
+        groups = (C.c_int64 * max(n, 1))(*[r.numel() // (self.V * self.J) for r in res_list])
+        cnt = torch.empty((2, self.V), dtype=torch.int64, device=self.device)
+        val = torch.empty((3, self.V), dtype=torch.float64, device=self.device)          # sum | mid as [V][2]
+        a = L.mpe_residual_stats_args()
+        a.n_buffers, a.n_joints = n, self.J
+        a.d_res, a.n_groups = C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(groups, C.POINTER(C.c_int64))
+        a.d_count, a.d_nonfinite = cnt[0].data_ptr(), cnt[1].data_ptr()
+        a.d_sum, a.d_mid = val[0].data_ptr(), val[1].data_ptr()
+        self._chk(self.lib.mpe_residual_stats(self.ctx, self._stream(), C.byref(a)))
+        cnt, val = cnt.cpu().numpy(), val.cpu().numpy()
+        out = {'count': cnt[0], 'nonfinite': cnt[1], 'sum': val[0], 'mid': val[1:].reshape(self.V, 2)}
+        with np.errstate(all='ignore'):
+            out['mean'] = np.where(out['count'] > 0, out['sum'] / np.maximum(out['count'], 1), np.nan)
+            med = (out['mid'][:, 0] + out['mid'][:, 1]) / 2
+        out['median'] = np.where(np.isnan(out['sum']), np.nan, med)
+        return out
+
     def dlt_pairs(self, pts, cams):
         pts = torch.as_tensor(pts, dtype=torch.float64, device=self.device).contiguous()
         cams = torch.as_tensor(cams, dtype=torch.int32, device=self.device).contiguous()

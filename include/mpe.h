@@ -260,6 +260,64 @@ typedef struct {
 } mpe_eval_args;
 int mpe_eval_batch(mpe_ctx *ctx, void *stream, const mpe_eval_args *a);
 
+/* Reprojection residuals: how well a 3D pose agrees with the 2D detections it came from (test/reprojection_error.py:
+ * 89-107, 350-420) -- a quality signal that needs no ground truth.
+ *   d_res[f][p][c][j] f64 [n_frames][pcap][V][J]: the pixel distance between the projection of joint j of person p into
+ *   camera c and the detection of that joint in the skeleton d_persons[f][p][c] names; -1 (a negative sentinel) where
+ *   nothing is counted: p >= d_n_persons[f], the camera has no head for the person, bit j of joint_mask is clear, the
+ *   person's flag (joint_flags == 0: d_flags[f][p]) or the joint's flag (joint_flags == 1: d_flags[f][p][j]) is 0, joint
+ *   j is absent from that skeleton (d_joint_mask of the batch), or its `valid` (d_vp, fp32) is not > threshold (strict,
+ *   :365).  The script's rows: `est` = the MLP poses (f32, person flags, used_joint_mask); `triang` = the triangulated
+ *   poses (f64, joint flags, all joints); `GT` = ground-truth bodies as f32 poses with a one-bit joint_mask.
+ * Arithmetic: get_projected_coordinates (:89-107) in fp32, f64 poses rounded to fp32 first (:405); every operation rounded
+ * on its own (nothing fused), quotients and roots correctly rounded, in this order (harness/reprojection.py states the same
+ * on the host, and the two agree bit for bit):
+ *   T  = (float) cfg.P[c] ; kd = (float) cfg.dist[c][0], [1], [4]         radial terms only
+ *   pc_i = ((T[i][0]*X + T[i][1]*Y) + T[i][2]*Z) + T[i][3]                i = 0..2
+ *   h0 = pc_0 / pc_2 ; h1 = pc_1 / pc_2 ; n = sqrt(h0*h0 + h1*h1) ; r = n*n
+ *   f  = ((1 + kd0*r) + (kd1*r)*r) + ((kd2*r)*r)*r ; d0 = h0*f ; d1 = h1*f
+ *   u_i = (K[c][i][0]*d0 + K[c][i][1]*d1) + K[c][i][2] ; px = u_0 / u_2 ; py = u_1 / u_2
+ *   res = sqrt(((double)px - x)*((double)px - x) + ((double)py - y)*((double)py - y))          f64 (:366)
+ * n_frames must equal the batch's, n_joints the context's. */
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t joint_mask;           /* bit j: joint j is projected                                    */
+    float threshold;               /* 0.5 in the script                                              */
+    const int32_t *d_persons;      /* [n_frames][pcap][V], as the matching stage writes them         */
+    const int32_t *d_n_persons;    /* [n_frames]                                                     */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    double *d_res;                 /* [n_frames][pcap][V][J]                                         */
+} mpe_reproject_args;
+int mpe_reproject_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_reproject_args *a);
+
+/* Per-camera statistics of one or more residual buffers of the layout above (the script's np.mean / np.median per camera
+ * over a whole run, :422-430; medians do not compose across batches, so the buffers of all batches are kept and read
+ * here once).  Per camera c of the context:
+ *   d_count[c]      i64  entries >= 0
+ *   d_nonfinite[c]  i64  entries that are NaN or infinite
+ *   d_sum[c]        f64  sum of the entries that are not negative, reduced in a fixed order (the same input gives the
+ *                        same bits); NaN when an entry is NaN -- mean and median of that camera are then NaN, as numpy's
+ *   d_mid[c][2]     f64  the elements of rank (n-1)/2 and n/2 among the n entries >= 0 in ascending order, EXACT (a radix
+ *                        select over the 64-bit patterns, which order like the non-negative doubles they encode; +inf is
+ *                        the largest; an entry of -0.0 counts as 0 and comes back as +0.0); np.median is
+ *                        (d_mid[c][0] + d_mid[c][1]) / 2.  NaN when n == 0.
+ * d_res and n_groups are HOST arrays of n_buffers entries: the device pointer and n_frames * pcap of each buffer (0 =
+ * skipped).  MPE_ERR_CAPACITY beyond 2^32 - 1 entries per camera.  The select state, the histograms and the partial sums
+ * are workspace of the context: one call at a time per context, also across streams (as for every batch entry point,
+ * one mpe_ctx serves one thread and one stream of work at a time). */
+typedef struct {
+    int32_t n_buffers, n_joints;
+    const double *const *d_res;
+    const int64_t *n_groups;
+    int64_t *d_count, *d_nonfinite;    /* [V]    */
+    double *d_sum;                     /* [V]    */
+    double *d_mid;                     /* [V][2] */
+} mpe_residual_stats_args;
+int mpe_residual_stats(mpe_ctx *ctx, void *stream, const mpe_residual_stats_args *a);
+
 /* ---- stage-level entry points (parity tests, Python mirrors of single reference symbols) */
 /* C[M][N] = act(A[M][K] * W[N][K]^T + bias): nn.Linear (+ LeakyReLU when slope_on != 0).
  * Row strides in elements; A and C device pointers, W/bias device pointers prepared by

@@ -1358,6 +1358,58 @@ int mpe_residual_stats(mpe_ctx *ctx, void *stream, const mpe_residual_stats_args
     return MPE_OK;
 }
 
+int mpe_partition_labels(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_partition_labels_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_partition_labels: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames != b->n_frames || a->pcap < 1 || a->hcap < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_partition_labels: bad sizes");
+    if (b->n_frames == 0) return MPE_OK;
+    if (!a->d_persons || !a->d_n_persons || !a->d_labels || !a->d_count || !a->d_status)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_partition_labels: NULL argument");
+    HIPCHK(ctx, launch_partition_labels(static_cast<hipStream_t>(stream), ctx->cfg.n_cameras, *b, *a));
+    return MPE_OK;
+}
+
+int mpe_group_bodies(mpe_ctx *ctx, void *stream, const mpe_group_bodies_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_group_bodies: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames < 0 || a->scap < 1 || a->kcap < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_group_bodies: bad sizes");
+    if (a->kcap > MPE_PART_MAX_KEYS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_group_bodies: %d joint keys over %d", a->kcap, MPE_PART_MAX_KEYS);
+    if (a->n_frames == 0) return MPE_OK;
+    if (!a->d_xyz || !a->d_mask || !a->d_nkeys || !a->d_order || !a->d_m1 || !a->d_n || !a->d_labels || !a->d_n_groups || !a->d_skip ||
+        !a->d_status)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_group_bodies: NULL argument");
+    HIPCHK(ctx, launch_group_bodies(static_cast<hipStream_t>(stream), *a));
+    return MPE_OK;
+}
+
+int mpe_set_log_table(mpe_ctx *ctx, const double *table, int32_t n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    DeviceGuard dg(ctx);
+    if (!table || n < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_set_log_table: bad argument");
+    if (ctx->log_table) return fail(ctx, MPE_ERR_STATE, "the table of logarithms is set once per context");
+    int rc = dev_alloc(ctx, &ctx->log_table, (size_t)n, false);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(ctx->log_table, table, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    ctx->n_log = n;
+    return MPE_OK;
+}
+
+int mpe_partition_scores(mpe_ctx *ctx, void *stream, const mpe_partition_scores_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_partition_scores: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames < 0 || a->ld_true < 1 || a->ld_pred < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_partition_scores: bad sizes");
+    if (ctx->n_log < 1) return fail(ctx, MPE_ERR_STATE, "mpe_partition_scores: no table of logarithms (mpe_set_log_table)");
+    if (a->n_frames == 0) return MPE_OK;
+    if (!a->d_labels_true || !a->d_labels_pred || !a->d_count || !a->d_scores || !a->d_status)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_partition_scores: NULL argument");
+    HIPCHK(ctx, launch_partition_scores(static_cast<hipStream_t>(stream), *a, ctx->log_table, ctx->n_log));
+    return MPE_OK;
+}
+
 int mpe_dlt_pairs(mpe_ctx *ctx, void *stream, const double *d_pts, const int32_t *d_cams, int32_t n, double *d_out) {
     if (!ctx) return MPE_ERR_INVALID;
     DeviceGuard dg(ctx);

@@ -152,6 +152,8 @@ struct mpe_ctx {
     mpe::ResidualState *res_state = nullptr;   // mpe_residual_stats: [V]
     uint32_t *res_hist = nullptr;              // [V][2][RESIDUAL_BINS]
     double *res_partial = nullptr;             // [V][RESIDUAL_SUM_BLOCKS]
+    double *log_table = nullptr;               // mpe_partition_scores: log 1 .. log n_log, as mpe_set_log_table received them
+    int n_log = 0;
     uint64_t *cl_keys = nullptr;   // clustering scratch
     int32_t *cl_scratch = nullptr;
     size_t cl_keys_per_frame = 0, cl_scratch_per_frame = 0;
@@ -318,6 +320,10 @@ hipError_t launch_eval(hipStream_t s, const mpe_eval_args &a);
 
 // reproject.hip
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);
+// partition.hip
+hipError_t launch_partition_labels(hipStream_t s, int V, const mpe_batch &b, const mpe_partition_labels_args &a);
+hipError_t launch_group_bodies(hipStream_t s, const mpe_group_bodies_args &a);
+hipError_t launch_partition_scores(hipStream_t s, const mpe_partition_scores_args &a, const double *log_table, int n_log);
 hipError_t launch_residual_stats(hipStream_t s, int V, const mpe_residual_stats_args &a, ResidualState *state, uint32_t *hist,
                                  double *partial);
 

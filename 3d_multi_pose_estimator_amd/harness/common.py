@@ -51,7 +51,9 @@ def build_parser(description):
     p.add_argument('--mlp-precision', choices=['default', 'max_accuracy', 'f64'], default='default',
                    help='MLP mode 3 (default: f64 sums every second K stage), 4 (an f64 flush per stage) or 5 (the network evaluated on the f64 matrix pipe)')
     p.add_argument('--device-metrics', action='store_true',
-                   help='error tables and pose-to-GT assignment on the GPU (mpe_eval_batch): the same report, the poses stay on the device')
+                   help='scoring on the GPU: error tables and pose-to-GT assignment (mpe_eval_batch) in the two metrics_from_* scripts, residuals and '
+                        'medians in reprojection_error, GT grouping, labels and the four clustering scores (mpe_group_bodies, mpe_partition_labels, '
+                        'mpe_partition_scores) in sm_metrics and sm_metrics_without_gt: the same report, the results stay on the device')
     return p
 
 

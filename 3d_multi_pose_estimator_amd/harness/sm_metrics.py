@@ -8,6 +8,11 @@ mean joint distance is <= 1 unit, else founds a new one, :128-160); frames with 
 the '-1' key or without any GT are skipped (:131-132, :166-167); one label per head node:
 index of the proposal containing it, or len(proposals) for unassigned heads (:208-216);
 metrics averaged over frames (:218-229).  Matching itself runs batched on the device.
+
+With --device-metrics the scoring runs there too: the bodies of a batch are packed (partition.pack_bodies) and grouped by
+Engine.group_bodies, the proposals become labels in Engine.partition_labels, Engine.partition_scores scores the two, and
+one [B,4] array comes back per batch; the totals are added here in frame order.  harness/partition.py states the
+arithmetic (sklearn's, with every sum in a written order); without the flag the loop below and sklearn do the work.
 """
 import copy
 import json
@@ -20,6 +25,7 @@ from .. import synthetic
 from ..calibration import Calibration
 from ..parameters import parameters
 from ..pipeline import Engine
+from . import partition as P
 from .common import build_parser, load_models, teacher_scores
 
 
@@ -112,6 +118,52 @@ def evaluate(work, infer, batch=256):
     return out
 
 
+KEYS = ('rand score', 'homogeneity', 'completeness', 'v_measure')
+
+
+def evaluate_on_device(work, infer, batch=256):
+    """evaluate() with --device-metrics.  `infer(frames, owners, packed)` -> (scores [B,4] float64 of the batch as
+    Engine.partition_scores left them, H [B], M [B], finish) with finish(f) -> the frame's (proposals as rows, their
+    number).  The skip rules are evaluate()'s and are known here from the counts: no GT person or a body without '-1'
+    (gt_labels gives None), no graph (M == 0), len(labels) != H.  A frame that counts but came back as NaN (over a compiled
+    cap of the kernels, or a batch whose bodies cannot be packed) is finished by the numpy statement."""
+    tot = np.zeros(4, np.float64)
+    n_data = 0
+    for start in range(0, len(work), batch):
+        chunk = work[start:start + batch]
+        try:
+            packed = P.pack_bodies([f for f, _ in chunk])
+            S = packed['n']
+            valid = np.array([S[i] > 0 and bool(packed['m1'][i, :S[i]].all()) for i in range(len(chunk))])
+        except ValueError:               # more joint keys than presence bits, or a value that is not a point: the host groups this batch
+            packed = None
+            gts = [gt_labels(f) for f, _ in chunk]
+            S = np.array([len(g) if g is not None else 0 for g in gts], np.int32)
+            valid = np.array([g is not None for g in gts])
+        if not valid.any():
+            continue
+        # as in evaluate(): only the frames gt_labels() accepts are packed and matched
+        sel = np.flatnonzero(valid)
+        chunk, S = [chunk[i] for i in sel], S[sel]
+        if packed is not None:
+            packed = {k: (v[sel] if isinstance(v, np.ndarray) else v) for k, v in packed.items()}
+        frames = [{c: [f[c][0], f[c][1]] for c in f if json.loads(f[c][0])} for f, _ in chunk]
+        scores, H, M, finish = infer(frames, [o for _, o in chunk], packed)
+        counted = (M != 0) & (S == H)
+        for i in np.flatnonzero(counted):
+            row = scores[i] if scores is not None else None
+            if row is None or np.isnan(row).any():
+                rows, n = finish(i)
+                row = P.partition_scores(gt_labels(chunk[i][0]), P.proposal_labels(rows, n, int(H[i])))
+            n_data += 1
+            tot += row                   # frame order, float64: the host loop's sums
+    out = {k: float(tot[j]) / max(1, n_data) for j, k in enumerate(KEYS)}
+    for k in KEYS:
+        print(k, out[k])
+    out['n_data'] = n_data
+    return out
+
+
 def run(args):
     from .common import max_skeletons_per_camera
     calib = Calibration(parameters)
@@ -137,7 +189,27 @@ def run(args):
                 out.append((H, [[int(h) for h in persons[f, p] if h >= 0] for p in range(int(n_persons[f]))]))
         return out
 
-    out = evaluate(work, infer, args.batch)
+    def infer_device(frames, owners, packed):
+        db = eng.to_device(eng.pack(frames))
+        if args.teacher_scores and owners[0] is not None:
+            persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
+        else:
+            _, persons, n_persons = eng.match(db, want_scores=False)
+        B = len(frames)
+        H = np.diff(np.asarray(db.host.frame_head_off[:B + 1]))
+        M = np.diff(np.asarray(db.host.frame_en_off[:B + 1]))
+        scores = None
+        if packed is not None:
+            gt = eng.group_bodies(packed, skip_in=(M == 0))
+            est = eng.partition_labels(db, persons, n_persons)
+            scores, _ = eng.partition_scores(gt['labels'], est['labels'], est['count'], skip=gt['skip'], count_true=gt['count'])
+        eng.sync_status()
+        return (scores.cpu().numpy() if scores is not None else None), H, M, lambda f: (persons[f].cpu().numpy(), int(n_persons[f]))
+
+    if getattr(args, 'device_metrics', False):
+        out = evaluate_on_device(work, infer_device, args.batch)
+    else:
+        out = evaluate(work, infer, args.batch)
     eng.close()
     return out
 

@@ -95,6 +95,27 @@ class mpe_residual_stats_args(C.Structure):
                 ('d_count', C.c_void_p), ('d_nonfinite', C.c_void_p), ('d_sum', C.c_void_p), ('d_mid', C.c_void_p)]
 
 
+class mpe_partition_labels_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('hcap', C.c_int32), ('d_persons', C.c_void_p), ('d_n_persons', C.c_void_p),
+                ('d_labels', C.c_void_p), ('d_count', C.c_void_p), ('d_status', C.c_void_p)]
+
+
+class mpe_group_bodies_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('scap', C.c_int32), ('kcap', C.c_int32), ('d_xyz', C.c_void_p), ('d_mask', C.c_void_p),
+                ('d_nkeys', C.c_void_p), ('d_order', C.c_void_p), ('d_m1', C.c_void_p), ('d_n', C.c_void_p), ('d_skip_in', C.c_void_p),
+                ('d_labels', C.c_void_p), ('d_n_groups', C.c_void_p), ('d_skip', C.c_void_p), ('d_status', C.c_void_p)]
+
+
+class mpe_partition_scores_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('ld_true', C.c_int32), ('ld_pred', C.c_int32), ('d_labels_true', C.c_void_p),
+                ('d_labels_pred', C.c_void_p), ('d_count', C.c_void_p), ('d_count_true', C.c_void_p), ('d_skip', C.c_void_p),
+                ('d_scores', C.c_void_p), ('d_status', C.c_void_p)]
+
+
+# per-frame status bits and compiled caps of mpe_partition_labels / mpe_group_bodies / mpe_partition_scores
+MPE_PART_SKIPPED, MPE_PART_OVER_CAP = 1, 2
+MPE_PART_MAX_SAMPLES, MPE_PART_MAX_SKELETONS, MPE_PART_MAX_KEYS = 256, 1024, 32
+
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
 
@@ -143,6 +164,10 @@ SYMBOLS = {
     'mpe_eval_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_eval_args)]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),
+    'mpe_partition_labels': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_partition_labels_args)]),
+    'mpe_group_bodies': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_group_bodies_args)]),
+    'mpe_set_log_table': (C.c_int, [C.c_void_p, c_f64p, C.c_int32]),
+    'mpe_partition_scores': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_partition_scores_args)]),
     'mpe_dlt_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'mpe_pack_json': (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -12,6 +12,7 @@ import torch
 
 from . import lib as L
 from .calibration import Calibration
+from .logtable import DEVICE_ENTRIES, log_table
 from .packing import (CapacityArena, DeviceBatch, JsonIndex, JsonStage, NeedsHostParser, PackedBatch, ParsedOnDevice, pack_frames,
                       pack_json, pack_json_into, stage_json_window)
 
@@ -88,6 +89,7 @@ class Engine:
         self._state = {}                 # what was loaded / set, so that sibling() can repeat it
         self._siblings = []
         self._json_streams = None
+        self._log_table_set = False      # partition_scores hands the table of logarithms to the context at its first call
         if os.environ.get('MPE_JSON_STREAMS_EARLY', '0') == '1':           # diagnostics (see _make_json_streams)
             self._make_json_streams()
 
@@ -963,6 +965,80 @@ class Engine:
             med = (out['mid'][:, 0] + out['mid'][:, 1]) / 2
         out['median'] = np.where(np.isnan(out['sum']), np.nan, med)
         return out
+
+    def partition_labels(self, db, persons, n_persons, hcap=None):
+        """One label per head of every frame on the device (mpe_partition_labels): the index of the first proposal that
+        holds the head, else n_persons -- the rule of test/sm_metrics.py:211-218 (harness/partition.py:proposal_labels).
+        -> dict of device tensors: labels [B,Hcap] i32 (-1 beyond the frame's heads), count [B] i32 (heads), status [B]."""
+        B = db.n_frames
+        if persons.dtype != torch.int32 or tuple(persons.shape) != (B, self.pcap, self.V) or not persons.is_contiguous():
+            raise ValueError('persons must be contiguous int32 [%d,%d,%d]' % (B, self.pcap, self.V))
+        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,) or not n_persons.is_contiguous():
+            raise ValueError('n_persons must be contiguous int32 [%d]' % B)
+        hcap = max(1, int(hcap if hcap is not None else (db.host.max_heads_per_frame() if B else 1)))
+        out = {'labels': torch.empty((B, hcap), dtype=torch.int32, device=self.device),
+               'count': torch.empty((B,), dtype=torch.int32, device=self.device),
+               'status': torch.empty((B,), dtype=torch.int32, device=self.device)}
+        a = L.mpe_partition_labels_args()
+        a.n_frames, a.pcap, a.hcap = B, self.pcap, hcap
+        a.d_persons, a.d_n_persons = persons.data_ptr(), n_persons.data_ptr()
+        a.d_labels, a.d_count, a.d_status = out['labels'].data_ptr(), out['count'].data_ptr(), out['status'].data_ptr()
+        self._chk(self.lib.mpe_partition_labels(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return out
+
+    def group_bodies(self, packed, skip_in=None):
+        """Ground-truth persons of every frame by greedy 3D proximity on the device (mpe_group_bodies; test/sm_metrics.py:
+        125-157).  packed: harness.partition.pack_bodies' arrays; skip_in [B]: frames not to group.  -> dict of device
+        tensors: labels [B,Scap] i32 (-1 beyond the frame's skeletons), count [B] i32 (skeletons), n_groups [B] i32,
+        skip [B] u8 (no person, a body without '-1', or skip_in), status [B] i32."""
+        B = len(packed['n'])
+        scap, kcap = packed['xyz'].shape[1:3]
+        if kcap > L.MPE_PART_MAX_KEYS:
+            raise ValueError('%d distinct joint keys, at most %d' % (kcap, L.MPE_PART_MAX_KEYS))
+        dev = self.device
+        up = lambda v, dt: torch.as_tensor(np.ascontiguousarray(v, dtype=dt)).to(dev)
+        t = {'xyz': up(packed['xyz'], np.float64), 'mask': up(packed['mask'].view(np.int32), np.int32), 'nkeys': up(packed['nkeys'], np.int32),
+             'order': up(packed['order'], np.uint8), 'm1': up(packed['m1'], np.uint8), 'n': up(packed['n'], np.int32)}
+        sk = up(np.asarray(skip_in).astype(np.uint8), np.uint8) if skip_in is not None else None
+        out = {'labels': torch.empty((B, scap), dtype=torch.int32, device=dev), 'count': t['n'],
+               'n_groups': torch.empty((B,), dtype=torch.int32, device=dev), 'skip': torch.empty((B,), dtype=torch.uint8, device=dev),
+               'status': torch.empty((B,), dtype=torch.int32, device=dev)}
+        a = L.mpe_group_bodies_args()
+        a.n_frames, a.scap, a.kcap = B, scap, kcap
+        a.d_xyz, a.d_mask, a.d_nkeys, a.d_order, a.d_m1, a.d_n = (t[k].data_ptr() for k in ('xyz', 'mask', 'nkeys', 'order', 'm1', 'n'))
+        a.d_skip_in = sk.data_ptr() if sk is not None else None
+        a.d_labels, a.d_n_groups, a.d_skip, a.d_status = (out[k].data_ptr() for k in ('labels', 'n_groups', 'skip', 'status'))
+        self._chk(self.lib.mpe_group_bodies(self.ctx, self._stream(), C.byref(a)))
+        out['_keep'] = (t, sk)                       # inputs stay alive until the caller has synchronised
+        return out
+
+    def partition_scores(self, labels_true, labels_pred, count, skip=None, count_true=None):
+        """Adjusted Rand index, homogeneity, completeness and V-measure of two labelings per frame on the device
+        (mpe_partition_scores): sklearn's numbers in the written summation order of harness/partition.py, bit for bit.
+        labels_true [B,Lt] / labels_pred [B,Lp] i32 device tensors, count [B] i32 labels per frame; skip [B] u8 and
+        count_true [B] i32 optional (a frame with skip set or with count_true != count is not scored).  -> (scores [B,4]
+        f64, NaN rows for frames not scored, status [B] i32: MPE_PART_SKIPPED / MPE_PART_OVER_CAP)."""
+        B = int(count.shape[0])
+        for t, dt, name in ((labels_true, torch.int32, 'labels_true'), (labels_pred, torch.int32, 'labels_pred'), (count, torch.int32, 'count'),
+                            (skip, torch.uint8, 'skip'), (count_true, torch.int32, 'count_true')):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or not t.is_cuda or t.shape[0] != B):
+                raise ValueError('%s must be a contiguous %s device tensor over %d frames' % (name, dt, B))
+        if labels_true.dim() != 2 or labels_pred.dim() != 2 or labels_true.shape[1] < 1 or labels_pred.shape[1] < 1:
+            raise ValueError('labels must be [B, L >= 1]')
+        if not self._log_table_set:
+            lg = np.ascontiguousarray(log_table()[:DEVICE_ENTRIES])
+            self._chk(self.lib.mpe_set_log_table(self.ctx, lg.ctypes.data_as(L.c_f64p), len(lg)))
+            self._log_table_set = True
+        scores = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        status = torch.empty((B,), dtype=torch.int32, device=self.device)
+        a = L.mpe_partition_scores_args()
+        a.n_frames, a.ld_true, a.ld_pred = B, labels_true.shape[1], labels_pred.shape[1]
+        a.d_labels_true, a.d_labels_pred, a.d_count = labels_true.data_ptr(), labels_pred.data_ptr(), count.data_ptr()
+        a.d_count_true = count_true.data_ptr() if count_true is not None else None
+        a.d_skip = skip.data_ptr() if skip is not None else None
+        a.d_scores, a.d_status = scores.data_ptr(), status.data_ptr()
+        self._chk(self.lib.mpe_partition_scores(self.ctx, self._stream(), C.byref(a)))
+        return scores, status
 
     def dlt_pairs(self, pts, cams):
         pts = torch.as_tensor(pts, dtype=torch.float64, device=self.device).contiguous()

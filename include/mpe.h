@@ -318,6 +318,79 @@ typedef struct {
 } mpe_residual_stats_args;
 int mpe_residual_stats(mpe_ctx *ctx, void *stream, const mpe_residual_stats_args *a);
 
+/* Clustering quality of the matching stage (test/sm_metrics.py:125-229, test/sm_metrics_without_gt.py:131-170): labels
+ * from proposals, the ground-truth grouping of a frame's bodies_3D, and the four scores of two labelings.
+ * harness/partition.py states all three on the host; host and device agree bit for bit.  Per-frame status words: */
+enum {
+    MPE_PART_SKIPPED = 1,          /* nothing computed for the frame (skip flag, no sample, unequal counts) */
+    MPE_PART_OVER_CAP = 2          /* the frame exceeds a compiled cap: the caller finishes it on the host */
+};
+#define MPE_PART_MAX_SAMPLES 256    /* labels per frame mpe_partition_scores takes           */
+#define MPE_PART_MAX_SKELETONS 1024 /* skeletons per frame mpe_group_bodies takes            */
+#define MPE_PART_MAX_KEYS 32        /* distinct joint keys of a batch: one presence bit each */
+
+/* One label per head of every frame: the index of the first proposal p < d_n_persons[f] whose row d_persons[f][p][:]
+ * holds the frame-local head id, else d_n_persons[f] (sm_metrics.py:211-218).  d_labels[f][h] for h < H (the frame's head
+ * count, from the batch), -1 beyond; d_count[f] = H; a frame with H > hcap gets MPE_PART_OVER_CAP and its first hcap labels. */
+typedef struct {
+    int32_t n_frames, pcap, hcap;
+    const int32_t *d_persons;      /* [n_frames][pcap][V], as mpe_match_batch / mpe_cluster_batch write them */
+    const int32_t *d_n_persons;    /* [n_frames]        */
+    int32_t *d_labels;             /* [n_frames][hcap]  */
+    int32_t *d_count;              /* [n_frames]        */
+    int32_t *d_status;             /* [n_frames]        */
+} mpe_partition_labels_args;
+int mpe_partition_labels(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_partition_labels_args *a);
+
+/* Ground-truth persons by greedy 3D proximity (sm_metrics.py:125-157).  The bodies of frame f, d_n[f] of them in (used
+ * camera, list) order, are packed per joint KEY: the distinct keys of the batch are numbered 0..kcap-1; skeleton s has
+ * d_xyz[f][s][k] for the keys of d_mask[f][s] (bit k), d_nkeys[f][s] keys in all, d_order[f][s][0..nkeys) their numbers in
+ * the order of the body's dict, d_m1[f][s] = '-1' in body.  Skeleton by skeleton: against every person founded so far the
+ * distance is the left-to-right f64 sum over the FOUNDING skeleton's keys in its d_order, of sqrt(fma(dz, dz, fma(dy, dy,
+ * dx*dx))) for the keys skeleton s has too; the least distance wins (strict <, from 1e9; the first person of equals);
+ * without a shared key or with distance / keys > 1. the skeleton founds person number d_n_groups.  d_labels[f][s] = the
+ * person, -1 for s >= d_n[f]; d_skip[f] = 1 for a frame without persons, with a body lacking '-1', or with d_skip_in[f]
+ * != 0 (d_skip_in may be NULL; such a frame is not grouped and gets MPE_PART_SKIPPED).  A frame with more than
+ * MPE_PART_MAX_SKELETONS skeletons gets MPE_PART_OVER_CAP, d_skip = 1 and no labels.  MPE_ERR_CAPACITY for kcap >
+ * MPE_PART_MAX_KEYS. */
+typedef struct {
+    int32_t n_frames, scap, kcap;
+    const double *d_xyz;           /* [n_frames][scap][kcap][3] */
+    const uint32_t *d_mask;        /* [n_frames][scap]          */
+    const int32_t *d_nkeys;        /* [n_frames][scap]          */
+    const uint8_t *d_order;        /* [n_frames][scap][kcap]    */
+    const uint8_t *d_m1;           /* [n_frames][scap]          */
+    const int32_t *d_n;            /* [n_frames]                */
+    const uint8_t *d_skip_in;      /* [n_frames] or NULL        */
+    int32_t *d_labels;             /* [n_frames][scap]          */
+    int32_t *d_n_groups;           /* [n_frames]                */
+    uint8_t *d_skip;               /* [n_frames]                */
+    int32_t *d_status;             /* [n_frames]                */
+} mpe_group_bodies_args;
+int mpe_group_bodies(mpe_ctx *ctx, void *stream, const mpe_group_bodies_args *a);
+
+/* The table of logarithms mpe_partition_scores reads: table[k - 1] = log k for k = 1..n, host memory, copied as it is (the
+ * host statement reads the same numbers, so no logarithm is ever taken twice).  Once per context, before the first call. */
+int mpe_set_log_table(mpe_ctx *ctx, const double *table, int32_t n);
+
+/* d_scores[f] = adjusted Rand index, homogeneity, completeness, V-measure of the labelings d_labels_true[f][0..n) and
+ * d_labels_pred[f][0..n), n = d_count[f] (sklearn's adjusted_rand_score and homogeneity_completeness_v_measure, sums in
+ * the order harness/partition.py writes them: classes by ascending label, cells by ascending (true, predicted); integer
+ * pair counts exact; nothing fused).  Four NaN and MPE_PART_SKIPPED for a frame with n <= 0, with d_skip[f] != 0 (may be
+ * NULL) or with d_count_true[f] != n (may be NULL); four NaN and MPE_PART_OVER_CAP for n > ld_true, n > ld_pred
+ * (the row lengths of the two label arrays), n > MPE_PART_MAX_SAMPLES or n * n beyond the table.  MPE_ERR_STATE without a table. */
+typedef struct {
+    int32_t n_frames, ld_true, ld_pred;
+    const int32_t *d_labels_true;  /* [n_frames][ld_true] */
+    const int32_t *d_labels_pred;  /* [n_frames][ld_pred] */
+    const int32_t *d_count;        /* [n_frames]       */
+    const int32_t *d_count_true;   /* [n_frames] or NULL */
+    const uint8_t *d_skip;         /* [n_frames] or NULL */
+    double *d_scores;              /* [n_frames][4]    */
+    int32_t *d_status;             /* [n_frames]       */
+} mpe_partition_scores_args;
+int mpe_partition_scores(mpe_ctx *ctx, void *stream, const mpe_partition_scores_args *a);
+
 /* ---- stage-level entry points (parity tests, Python mirrors of single reference symbols) */
 /* C[M][N] = act(A[M][K] * W[N][K]^T + bias): nn.Linear (+ LeakyReLU when slope_on != 0).
  * Row strides in elements; A and C device pointers, W/bias device pointers prepared by

@@ -181,16 +181,10 @@ struct SkExt {
     int32_t b, e;
 };
 
-__global__ __launch_bounds__(64) void k_json_braces(const char *__restrict__ text, const mpe_json_entry *__restrict__ entries,
-                                                     int n_entries, int kcap, SkExt *__restrict__ ext, int32_t *__restrict__ n_sk,
-                                                     int32_t *__restrict__ totals) {
-    const int e = blockIdx.x, lane = threadIdx.x;
-    if (e >= n_entries) return;
-    const mpe_json_entry en = entries[e];
-    const char *t = text + en.begin;
-    const int n = (int)(en.end - en.begin);
-    SkExt *my = ext + (size_t)e * kcap;
-    int n_open = 0, n_close = 0;
+// the wave's scan of one text: extents of the first kcap brace pairs into `my`, the two counts to every lane
+__device__ __forceinline__ void brace_scan(const char *t, int n, int kcap, SkExt *__restrict__ my, int lane, int &n_open, int &n_close) {
+    n_open = 0;
+    n_close = 0;
     for (int base = 0; base < n; base += 1024) {
         const int off = base + lane * 16;
         uint32_t wv[4] = {0, 0, 0, 0};
@@ -233,9 +227,36 @@ __global__ __launch_bounds__(64) void k_json_braces(const char *__restrict__ tex
         n_open += __shfl(so, 63);
         n_close += __shfl(sc, 63);
     }
+}
+
+__global__ __launch_bounds__(64) void k_json_braces(const char *__restrict__ text, const mpe_json_entry *__restrict__ entries,
+                                                     int n_entries, int kcap, SkExt *__restrict__ ext, int32_t *__restrict__ n_sk,
+                                                     int32_t *__restrict__ totals) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    if (e >= n_entries) return;
+    const mpe_json_entry en = entries[e];
+    int n_open, n_close;
+    brace_scan(text + en.begin, (int)(en.end - en.begin), kcap, ext + (size_t)e * kcap, lane, n_open, n_close);
     if (lane == 0) {
         n_sk[e] = n_open < kcap ? n_open : kcap;
         if (n_open != n_close || n_open > kcap) atomicOr(&totals[2], JS_FALLBACK);
+    }
+}
+
+// the same scan over a list of ground-truth bodies: the count is kept as it is (mpe_gt_from_bodies compares counts), and a list
+// with more bodies than a frame has rows is a matter of capacity, not of language
+__global__ __launch_bounds__(64) void k_body_braces(const char *__restrict__ text, const mpe_json_entry *__restrict__ entries,
+                                                     int n_entries, int scap, SkExt *__restrict__ ext, int32_t *__restrict__ n_b,
+                                                     int32_t *__restrict__ status) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    if (e >= n_entries) return;
+    const mpe_json_entry en = entries[e];
+    int n_open, n_close;
+    brace_scan(text + en.begin, (int)(en.end - en.begin), scap, ext + (size_t)e * scap, lane, n_open, n_close);
+    if (lane == 0) {
+        n_b[e] = n_open;
+        if (n_open != n_close) atomicOr(status, JS_FALLBACK);
+        if (n_open > scap) atomicOr(status, JS_CAPACITY);
     }
 }
 
@@ -387,6 +408,170 @@ __global__ __launch_bounds__(256) void k_json_compact(const mpe_json_entry *__re
     }
 }
 
+// ---- ground-truth bodies (element [3] of every camera entry; include/mpe.h: mpe_json_parse_bodies_device) ----------------
+// The text is the OUTER document here (a JSON list, not a string): quotes are plain and blanks are literal.  The property
+// k_json_braces rests on holds as well: keys are quoted integers, so a brace inside a string is something the walker
+// declines anyway, and body k of an entry is its k-th '{' .. k-th '}'.
+//   k_body_braces   the wave-per-entry brace scan of k_json_braces: extents and count of the bodies of its list
+//   k_body_layout   one thread per frame: the row of every entry's first body -- configured cameras first, the others behind
+//                   them -- d_n, d_entry_count, the capacity bit
+//   k_body_walk     one thread per body, (entry, k) pairs k-major like k_json_skeleton and on the same capped grid: a body is
+//                   ~1.1 KB of serial byte work, the size of a skeleton, read through the same 8-byte register window
+
+// One body, text[b .. e) = "{ ... }" -> its row.  false = not in the device's language.
+__device__ bool walk_body(const char *t, int b, int e, double *xyz, uint8_t *order, uint32_t *mask_out, int *nkeys_out) {
+    JCur c(t, b, e);
+    if (c.ch() != '{') return false;
+    ++c.i;
+    uint32_t mask = 0;
+    int nk = 0;
+    c.ws();
+    if (c.ch() == '}') {
+        ++c.i;
+    } else {
+        for (;;) {
+            c.ws();
+            if (c.ch() != '"') return false;
+            ++c.i;
+            int slot;
+            if (c.ch() == '-') {                               // "-1" is the only negative key
+                if (c.ch1() != '1') return false;
+                c.i += 2;
+                slot = MPE_GT_M1_SLOT;
+            } else {
+                const int d0 = c.ch();
+                if (d0 < '0' || d0 > '9') return false;
+                slot = d0 - '0';
+                ++c.i;
+                const int d1 = c.ch();
+                if (d1 >= '0' && d1 <= '9') {
+                    if (slot == 0) return false;               // "07" is another key than "7"
+                    slot = slot * 10 + (d1 - '0');
+                    ++c.i;
+                }
+                if (slot >= MPE_GT_M1_SLOT) return false;      // a third digit fails at the closing quote
+            }
+            if (c.ch() != '"') return false;
+            ++c.i;
+            if (mask >> slot & 1u) return false;               // a duplicate key: the dict keeps the last value in the first position
+            c.ws();
+            if (c.ch() != ':') return false;
+            ++c.i;
+            c.ws();
+            if (c.ch() != '[') return false;
+            ++c.i;
+            double v[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                c.ws();
+                // JSON's number shape where el_parse_number_src is laxer: no '+', a digit first, no leading zero, a digit last
+                int d = c.ch();
+                if (d == '-') d = c.ch1();
+                if (d < '0' || d > '9') return false;
+                if (d == '0') {
+                    const int nx = c.at(c.i + (c.ch() == '-' ? 2 : 1));
+                    if (nx >= '0' && nx <= '9') return false;
+                }
+                bool ok = true;
+                if (el_parse_number_src(c, &v[q], &ok) == 0 || !ok) return false;
+                const int last = c.at(c.i - 1);
+                if (last < '0' || last > '9') return false;
+                c.ws();
+                if (c.ch() != (q < 2 ? ',' : ']')) return false;
+                ++c.i;
+            }
+            xyz[slot * 3 + 0] = v[0];
+            xyz[slot * 3 + 1] = v[1];
+            xyz[slot * 3 + 2] = v[2];
+            order[nk++] = (uint8_t)slot;                       // nk <= 32: every slot at most once
+            mask |= 1u << slot;
+            c.ws();
+            if (c.ch() == ',') {
+                ++c.i;
+                continue;
+            }
+            if (c.ch() == '}') {
+                ++c.i;
+                break;
+            }
+            return false;
+        }
+    }
+    if (c.i != e) return false;                                // the object closes where the brace scan said (no nesting)
+    *mask_out = mask;
+    *nkeys_out = nk;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_body_layout(const mpe_json_entry *__restrict__ entries, const int32_t *__restrict__ frame_entry_off,
+                                                      int n_frames, int scap, const int32_t *__restrict__ n_b, int32_t *__restrict__ entry_row,
+                                                      int32_t *__restrict__ d_n, int32_t *__restrict__ status) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_frames) return;
+    const int e0 = frame_entry_off[f], e1 = frame_entry_off[f + 1];
+    long row = 0;
+    for (int e = e0; e < e1; ++e)
+        if (entries[e].cam >= 0) {
+            entry_row[e] = (int32_t)(row < scap ? row : scap);
+            row += n_b[e];
+        }
+    d_n[f] = (int32_t)(row < scap ? row : scap);
+    for (int e = e0; e < e1; ++e)
+        if (entries[e].cam < 0) {
+            entry_row[e] = (int32_t)(row < scap ? row : scap);
+            row += n_b[e];
+        }
+    if (row > scap) atomicOr(status, JS_CAPACITY);
+}
+
+__global__ __launch_bounds__(256) void k_body_walk(const char *__restrict__ text, const mpe_json_entry *__restrict__ entries, int n_entries,
+                                                    int scap, const SkExt *__restrict__ ext, const int32_t *__restrict__ n_b,
+                                                    const int32_t *__restrict__ entry_row, double *__restrict__ xyz,
+                                                    uint32_t *__restrict__ mask, int32_t *__restrict__ nkeys, uint8_t *__restrict__ order,
+                                                    uint8_t *__restrict__ m1, int32_t *__restrict__ body_cam, int32_t *__restrict__ status) {
+    const long total = (long)n_entries * scap;
+    for (long gid = (long)blockIdx.x * blockDim.x + threadIdx.x; gid < total; gid += (long)gridDim.x * blockDim.x) {
+        const int k = (int)(gid / n_entries), e = (int)(gid - (long)k * n_entries);
+        const int cnt = n_b[e] < scap ? n_b[e] : scap;         // k_body_braces keeps the first scap extents
+        if (k >= (cnt > 0 ? cnt : 1)) continue;
+        const mpe_json_entry en = entries[e];
+        const char *t = text + en.begin;
+        const int n = (int)(en.end - en.begin);
+        bool ok = true;
+        if (cnt == 0) {
+            JCur c(t, 0, n);                                   // "[]" with blanks
+            c.ws();
+            ok = c.ch() == '[';
+            ++c.i;
+            c.ws();
+            ok = ok && c.ch() == ']';
+            ++c.i;
+            c.ws();
+            ok = ok && c.i == n;
+        } else {
+            const SkExt *my = ext + (size_t)e * scap;
+            const int b = my[k].b, en_ = my[k].e;
+            ok = b < en_ && en_ <= n;
+            if (ok && k == 0) ok = gap_is(t, n, 0, b, '[');
+            const int row = entry_row[e] + k;
+            if (ok && row < scap) {                            // rows past scap belong to a frame that has raised JS_CAPACITY
+                const size_t r = (size_t)en.frame * scap + row;
+                uint32_t mk = 0;
+                int nk = 0;
+                ok = walk_body(t, b, en_, xyz + r * MPE_GT_KEY_SLOTS * 3, order + r * MPE_GT_KEY_SLOTS, &mk, &nk);
+                if (ok) {
+                    mask[r] = mk;
+                    nkeys[r] = nk;
+                    m1[r] = (uint8_t)(mk >> MPE_GT_M1_SLOT & 1u);
+                    body_cam[r] = en.cam;
+                }
+            }
+            if (ok) ok = k + 1 < cnt ? (my[k + 1].b >= en_ && gap_is(t, n, en_, my[k + 1].b, ',')) : (n_b[e] > scap || gap_is(t, n, en_, n, ']'));
+        }
+        if (!ok) atomicOr(status, JS_FALLBACK);
+    }
+}
+
 }  // namespace mpe
 
 using namespace mpe;
@@ -452,5 +637,45 @@ extern "C" int mpe_json_parse_device(mpe_ctx *ctx, void *stream, const char *d_t
                            const_cast<uint32_t *>(out->d_joint_mask), const_cast<uint32_t *>(out->d_tri_mask),
                            const_cast<double *>(out->d_xy), const_cast<float *>(out->d_vp));
     }
+    return hipGetLastError() == hipSuccess ? MPE_OK : MPE_ERR_HIP;
+}
+
+extern "C" size_t mpe_json_bodies_scratch_bytes(int32_t n_entries_cap, int32_t scap) {
+    const size_t e = (size_t)(n_entries_cap > 0 ? n_entries_cap : 1), k = (size_t)(scap > 0 ? scap : 1);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    return up(e * 4) + up(e * k * sizeof(SkExt));
+}
+
+extern "C" int mpe_json_parse_bodies_device(mpe_ctx *ctx, void *stream, const mpe_json_bodies_args *a) {
+    if (!ctx || !a || a->n_frames < 0 || a->n_entries < 0 || a->scap < 1 || !a->d_status || !a->d_scratch) return MPE_ERR_INVALID;
+    if (a->n_frames > 0 && (!a->d_frame_entry_off || !a->d_xyz || !a->d_mask || !a->d_nkeys || !a->d_order || !a->d_m1 || !a->d_n || !a->d_body_cam))
+        return MPE_ERR_INVALID;
+    if (a->n_entries > 0 && (!a->d_text || !a->d_entries || !a->d_entry_count)) return MPE_ERR_INVALID;
+    if (mpe_json_bodies_scratch_bytes(a->n_entries, a->scap) > a->scratch_bytes) return MPE_ERR_CAPACITY;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MPE_ERR_HIP;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t e = (size_t)(a->n_entries > 0 ? a->n_entries : 1);
+    char *p = static_cast<char *>(a->d_scratch);
+    int32_t *entry_row = reinterpret_cast<int32_t *>(p); p += up(e * 4);
+    SkExt *ext = reinterpret_cast<SkExt *>(p);
+    const size_t rows = (size_t)a->n_frames * a->scap;
+    if (hipMemsetAsync(a->d_status, 0, sizeof(int32_t), s) != hipSuccess) return MPE_ERR_HIP;
+    if (a->n_frames == 0) return MPE_OK;
+    // unused rows and absent keys read as zero, the camera of an unused row as -1
+    if (hipMemsetAsync(a->d_xyz, 0, rows * MPE_GT_KEY_SLOTS * 3 * sizeof(double), s) != hipSuccess ||
+        hipMemsetAsync(a->d_mask, 0, rows * 4, s) != hipSuccess || hipMemsetAsync(a->d_nkeys, 0, rows * 4, s) != hipSuccess ||
+        hipMemsetAsync(a->d_order, 0, rows * MPE_GT_KEY_SLOTS, s) != hipSuccess || hipMemsetAsync(a->d_m1, 0, rows, s) != hipSuccess ||
+        hipMemsetAsync(a->d_body_cam, 0xFF, rows * 4, s) != hipSuccess)
+        return MPE_ERR_HIP;
+    if (a->n_entries > 0)
+        hipLaunchKernelGGL(k_body_braces, dim3((unsigned)a->n_entries), dim3(64), 0, s, a->d_text, a->d_entries, a->n_entries, a->scap, ext,
+                           a->d_entry_count, a->d_status);
+    hipLaunchKernelGGL(k_body_layout, dim3((unsigned)((a->n_frames + 255) / 256)), dim3(256), 0, s, a->d_entries, a->d_frame_entry_off,
+                       a->n_frames, a->scap, a->d_entry_count, entry_row, a->d_n, a->d_status);
+    if (a->n_entries > 0)
+        hipLaunchKernelGGL(k_body_walk, dim3(side_grid((long)a->n_entries * a->scap)), dim3(256), 0, s, a->d_text, a->d_entries, a->n_entries,
+                           a->scap, ext, a->d_entry_count, entry_row, a->d_xyz, a->d_mask, a->d_nkeys, a->d_order, a->d_m1, a->d_body_cam,
+                           a->d_status);
     return hipGetLastError() == hipSuccess ? MPE_OK : MPE_ERR_HIP;
 }

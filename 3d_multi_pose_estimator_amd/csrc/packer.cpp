@@ -590,6 +590,60 @@ bool index_frame(const char *b, const char *e, const std::vector<std::string> &c
     return false;
 }
 
+// First level for the ground truth (mpe_json_stage_gt_window): every camera key of the frame, in key order, with the extent of
+// element [3] of its entry (cam = -1 for a key outside `cams`).  `unsupported` = an entry that is not a list of exactly four
+// elements, or whose fourth element is not a list: the caller's host path decides what that means.
+bool index_frame_gt(const char *b, const char *e, const std::vector<std::string> &cams, std::vector<StrExtent> *out, std::string *err,
+                    bool *unsupported) {
+    Cursor c{b, e, false};
+    skip_ws(c);
+    if (c.p >= c.end || *c.p != '{') { *err = "frame is not an object"; return false; }
+    ++c.p;
+    const int V = (int)cams.size();
+    skip_ws(c);
+    if (c.p < c.end && *c.p == '}') return true;
+    std::string key;
+    while (c.p < c.end) {
+        skip_ws(c);
+        if (!read_key(c, &key)) { *err = "bad camera key"; return false; }
+        skip_ws(c);
+        if (c.p >= c.end || *c.p != ':') { *err = "missing ':' after camera"; return false; }
+        ++c.p;
+        int cam = -1;
+        for (int i = 0; i < V; ++i)
+            if (cams[i] == key) { cam = i; break; }
+        skip_ws(c);
+        if (c.p >= c.end || *c.p != '[') { *unsupported = true; return true; }
+        ++c.p;
+        skip_ws(c);
+        if (c.p < c.end && *c.p == ']') { *unsupported = true; return true; }
+        int n_el = 0;
+        for (;;) {
+            skip_ws(c);
+            const char *vb = c.p;
+            if (n_el == 3 && (c.p >= c.end || *c.p != '[')) { *unsupported = true; return true; }
+            if (!skip_value(c)) { *err = "bad camera entry"; return false; }
+            if (n_el == 3) out->push_back({cam, vb, c.p});
+            ++n_el;
+            skip_ws(c);
+            if (c.p >= c.end) { *err = "unterminated camera entry"; return false; }
+            if (*c.p == ',') { ++c.p; continue; }
+            if (*c.p == ']') { ++c.p; break; }
+            *err = "bad camera entry";
+            return false;
+        }
+        if (n_el != 4) { *unsupported = true; return true; }
+        skip_ws(c);
+        if (c.p >= c.end) break;
+        if (*c.p == ',') { ++c.p; continue; }
+        if (*c.p == '}') return true;
+        *err = "bad frame object";
+        return false;
+    }
+    *err = "unterminated frame";
+    return false;
+}
+
 // ---- byte searches of the frame scanner -------------------------------------------------------
 // scalar forms (any CPU) and AVX2 forms (32 bytes per step), chosen once at start-up
 static const char *find_special_scalar(const char *p, const char *e) {
@@ -1317,10 +1371,12 @@ int mpe_pack_indexed_into(mpe_json_index *ix, const char *const *camera_names, i
     return MPE_OK;
 }
 
-int mpe_json_stage_window(mpe_json_index *ix, const char *const *camera_names, int32_t n_cameras, int32_t frame_start,
-                          int32_t frame_step, int32_t max_frames, int32_t n_threads, char *text_dst, size_t text_cap,
-                          mpe_json_entry *entries, int32_t entry_cap, int32_t *frame_entry_off, int32_t *n_frames,
-                          int32_t *n_entries, size_t *text_bytes) {
+// mpe_json_stage_window (gt = false: the skeleton strings of the configured cameras) and mpe_json_stage_gt_window (gt = true:
+// element [3] of every camera entry) share everything but the first-level walk of a frame
+static int stage_window(bool gt, mpe_json_index *ix, const char *const *camera_names, int32_t n_cameras, int32_t frame_start,
+                        int32_t frame_step, int32_t max_frames, int32_t n_threads, char *text_dst, size_t text_cap,
+                        mpe_json_entry *entries, int32_t entry_cap, int32_t *frame_entry_off, int32_t *n_frames,
+                        int32_t *n_entries, size_t *text_bytes) {
     if (!ix || !camera_names || n_cameras < 1 || n_cameras > MPE_MAX_CAMERAS || frame_start < 0 || frame_step < 1 || max_frames < 1 ||
         !text_dst || !entries || !frame_entry_off || !n_frames || !n_entries || !text_bytes) {
         g_pack_error = "mpe_json_stage_window: bad argument";
@@ -1370,7 +1426,8 @@ int mpe_json_stage_window(mpe_json_index *ix, const char *const *camera_names, i
     run([&](int i) {
         bool un = false;
         per[(size_t)i].reserve((size_t)n_cameras);
-        if (!index_frame(sel[(size_t)i].first, sel[(size_t)i].second, cams, &per[(size_t)i], &errs[(size_t)i], &un)) failed = true;
+        if (!(gt ? index_frame_gt : index_frame)(sel[(size_t)i].first, sel[(size_t)i].second, cams, &per[(size_t)i], &errs[(size_t)i], &un))
+            failed = true;
         if (un) unsupported = true;
     });
     if (failed) {
@@ -1382,7 +1439,9 @@ int mpe_json_stage_window(mpe_json_index *ix, const char *const *camera_names, i
         return MPE_ERR_INVALID;
     }
     if (unsupported) {
-        g_pack_error = "mpe_json_stage_window: a frame needs the host parser (skeleton list not a string, or more camera entries than cameras)";
+        g_pack_error = gt ? "mpe_json_stage_gt_window: a frame needs the host parser (a camera entry that is not a list of four elements, or "
+                            "whose fourth element is not a list)"
+                          : "mpe_json_stage_window: a frame needs the host parser (skeleton list not a string, or more camera entries than cameras)";
         return MPE_ERR_UNSUPPORTED;
     }
     const auto tt2 = std::chrono::steady_clock::now();
@@ -1425,6 +1484,22 @@ int mpe_json_stage_window(mpe_json_index *ix, const char *const *camera_names, i
     *n_entries = ne;
     *text_bytes = off;
     return MPE_OK;
+}
+
+int mpe_json_stage_window(mpe_json_index *ix, const char *const *camera_names, int32_t n_cameras, int32_t frame_start,
+                          int32_t frame_step, int32_t max_frames, int32_t n_threads, char *text_dst, size_t text_cap,
+                          mpe_json_entry *entries, int32_t entry_cap, int32_t *frame_entry_off, int32_t *n_frames,
+                          int32_t *n_entries, size_t *text_bytes) {
+    return stage_window(false, ix, camera_names, n_cameras, frame_start, frame_step, max_frames, n_threads, text_dst, text_cap, entries,
+                        entry_cap, frame_entry_off, n_frames, n_entries, text_bytes);
+}
+
+int mpe_json_stage_gt_window(mpe_json_index *ix, const char *const *camera_names, int32_t n_cameras, int32_t frame_start,
+                             int32_t frame_step, int32_t max_frames, int32_t n_threads, char *text_dst, size_t text_cap,
+                             mpe_json_entry *entries, int32_t entry_cap, int32_t *frame_entry_off, int32_t *n_frames,
+                             int32_t *n_entries, size_t *text_bytes) {
+    return stage_window(true, ix, camera_names, n_cameras, frame_start, frame_step, max_frames, n_threads, text_dst, text_cap, entries,
+                        entry_cap, frame_entry_off, n_frames, n_entries, text_bytes);
 }
 
 int mpe_packed_view(const mpe_packed *pk, mpe_packed_arrays *v) {

@@ -54,6 +54,11 @@ def build_parser(description):
                    help='scoring on the GPU: error tables and pose-to-GT assignment (mpe_eval_batch) in the two metrics_from_* scripts, residuals and '
                         'medians in reprojection_error, GT grouping, labels and the four clustering scores (mpe_group_bodies, mpe_partition_labels, '
                         'mpe_partition_scores) in sm_metrics and sm_metrics_without_gt: the same report, the results stay on the device')
+    p.add_argument('--device-gt', action='store_true',
+                   help='implies --device-metrics; the ground truth is built on the GPU as well: the bodies_3D lists of the test files are '
+                        'parsed there from the files\' bytes (mpe_json_parse_bodies_device) and turned into the arrays the scoring kernels read '
+                        '(mpe_gt_from_bodies in the metrics_from_* scripts, mpe_group_bodies in sm_metrics); a window the device declines is '
+                        'redone on the host')
     return p
 
 
@@ -291,9 +296,73 @@ def teacher_scores(db, owners):
     return torch.from_numpy(sc)
 
 
-def collect_work(args, calib):
+class DeviceGT:
+    """--device-gt: the test files as bytes behind one mpe_json_index each, and for every item of `work` the (file, frame
+    index) it came from.  runs(start, n) cuts a batch into stretches of one file, each a window (first frame, --datastep
+    as the stride, count) of that file's index."""
+
+    def __init__(self, eng, files, src, datastep):
+        from ..packing import JsonIndex
+        self.eng, self.src, self.datastep = eng, src, int(datastep)
+        self.indexes = []
+        for file in files:
+            with open(file, 'rb') as fh:
+                self.indexes.append(JsonIndex(fh.read()))
+        self.windows = self.declined = 0
+
+    def runs(self, start, n):
+        i = 0
+        while i < n:
+            file_no, first = self.src[start + i]
+            j = i + 1
+            while j < n and self.src[start + j][0] == file_no:
+                j += 1
+            yield i, j, file_no, first
+            i = j
+
+    def bodies(self, file_no, first, count):
+        """-> ParsedBodies of the window, or None where the host path has to take over."""
+        self.windows += 1
+        pb = self.eng.bodies_from_json(self.indexes[file_no], first, self.datastep, count)
+        if pb.status != 0 or pb.n_frames != count:
+            self.declined += 1
+            return None
+        return pb
+
+    def ground_truth(self, start, chunk, T_d_files, T_i1):
+        """pack_ground_truth's dict for a batch as device tensors: Engine.ground_truth per stretch, pack_ground_truth (uploaded)
+        for a stretch the device declines."""
+        dev, parts = self.eng.device, []
+        for i, j, file_no, first in self.runs(start, len(chunk)):
+            pb = self.bodies(file_no, first, j - i)
+            if pb is not None:
+                gt = self.eng.ground_truth(pb, [T_d_files[file_no].numpy()], np.zeros(j - i, np.int32), T_i1.numpy())
+            else:
+                host = pack_ground_truth([w[0] for w in chunk[i:j]], [w[1] for w in chunk[i:j]], T_i1)
+                gt = {k: torch.from_numpy(host[k]).to(dev) for k in ('xyz', 'joint', 'valid', 'n')}
+            parts.append(gt)
+        gcap = max(p['xyz'].shape[1] for p in parts)
+        out = {}
+        for k in ('xyz', 'joint', 'valid', 'n'):
+            cols = []
+            for p in parts:
+                t = p[k]
+                if k != 'n' and t.shape[1] < gcap:
+                    pad = torch.zeros((t.shape[0], gcap - t.shape[1]) + tuple(t.shape[2:]), dtype=t.dtype, device=dev)
+                    t = torch.cat((t, pad), 1)
+                cols.append(t)
+            out[k] = torch.cat(cols, 0) if len(cols) > 1 else cols[0]
+        return out
+
+    def close(self):
+        for ix in self.indexes:
+            ix.close()
+
+
+def collect_work(args, calib, src=None):
     """[(frame, T_dataset_cam1, owners or None)] honouring --datastep across files (the counter
-    runs over all files, metrics_from_model.py:102-124)."""
+    runs over all files, metrics_from_model.py:102-124).  src, a list, receives (file number, frame index in the file) of
+    every item."""
     work = []
     if args.synthetic:
         spec = synthetic.FrameSpec(persons=args.persons, noise_px=args.noise_px)
@@ -306,10 +375,12 @@ def collect_work(args, calib):
     for file in args.testfiles:
         print(file)
         T_d1 = torch.from_numpy(dataset_transform(tm_dir, file).get_transform('root', parameters.camera_names[1])).type(torch.float32)
-        for frame in json.load(open(file, 'rb')):
+        for k, frame in enumerate(json.load(open(file, 'rb'))):
             n_input += 1
             if (n_input - 1) % args.datastep == 0:
                 work.append((frame, T_d1, None))
+                if src is not None:
+                    src.append((args.testfiles.index(file), k))
     return work
 
 
@@ -341,23 +412,34 @@ def evaluate(work, infer, mode, T_i1, batch=256):
     return metrics, n_data, n_results
 
 
-def evaluate_on_device(work, infer, mode, T_i1, batch=256):
+def evaluate_on_device(work, infer, mode, T_i1, batch=256, device_gt=None, T_d_files=None):
     """evaluate() with --device-metrics: `infer(frames, owners, gt)` runs the inference path and Engine.evaluate on
-    the device and returns its tensors; the frames and the skip rules are evaluate()'s.  Returns (DeviceMetrics,
-    n_data, n_results)."""
+    the device and returns its tensors; the frames and the skip rules are evaluate()'s.  With device_gt (a DeviceGT,
+    --device-gt) the ground truth of a batch is built on the device from the files' bytes and stays there; only the body
+    counts and the '-1' flags of the batch come back.  Returns (DeviceMetrics, n_data, n_results)."""
     metrics = DeviceMetrics()
     n_data = n_results = 0
     for start in range(0, len(work), batch):
         chunk = work[start:start + batch]
-        gt = pack_ground_truth([w[0] for w in chunk], [w[1] for w in chunk], T_i1)
-        sel = np.flatnonzero(gt['n'] > 0)
-        if not len(sel):
-            continue
-        gt = {k: v[sel] for k, v in gt.items()}
+        if device_gt is not None:
+            gt = device_gt.ground_truth(start, chunk, T_d_files, T_i1)
+            sel = np.flatnonzero(gt['n'].cpu().numpy() > 0)
+            if not len(sel):
+                continue
+            pick = torch.from_numpy(sel).to(gt['n'].device)
+            gt = {k: v.index_select(0, pick) for k, v in gt.items() if isinstance(v, torch.Tensor)}
+            gt_valid = gt['valid'].cpu().numpy()
+        else:
+            gt = pack_ground_truth([w[0] for w in chunk], [w[1] for w in chunk], T_i1)
+            sel = np.flatnonzero(gt['n'] > 0)
+            if not len(sel):
+                continue
+            gt = {k: v[sel] for k, v in gt.items()}
+            gt_valid = gt['valid']
         keep = [chunk[i] for i in sel]
         frames = [{c: [frame[c][0], frame[c][1]] for c in frame if json.loads(frame[c][0])} for frame, _, _ in keep]
         ev = infer(frames, [o for _, _, o in keep], gt)
-        h = metrics.add_batch(ev, gt['valid'], triangulation=(mode != 'mlp'))
+        h = metrics.add_batch(ev, gt_valid, triangulation=(mode != 'mlp'))
         done = (h['status'] & MPE_EVAL_SKIPPED) == 0
         n_data += int(done.sum())
         n_results += int(h['n_res'][done].sum())
@@ -376,7 +458,11 @@ def max_skeletons_per_camera(work):
 
 def run(args, mode):
     calib = Calibration(parameters)
-    work = collect_work(args, calib)
+    device_gt = getattr(args, 'device_gt', False) and not args.synthetic       # synthetic frames have no file to parse
+    if getattr(args, 'device_gt', False):
+        args.device_metrics = True
+    src = [] if device_gt else None
+    work = collect_work(args, calib, src)
     eng = Engine(parameters, calib, max_frames=args.batch,
                  max_persons_per_camera=max(4, args.persons + 1, max_skeletons_per_camera(work)))
     if getattr(args, 'gat_acc64', False) or getattr(args, 'mlp_precision', 'default') != 'default':
@@ -449,7 +535,16 @@ def run(args, mode):
 
     if getattr(args, 'device_metrics', False):
         t['eval'] = 0.0
-        metrics, n_data, n_results = evaluate_on_device(work, infer_device, mode, T_i1, args.batch)
+        dgt, T_d_files = None, None
+        if device_gt:
+            dgt = DeviceGT(eng, args.testfiles, src, args.datastep)
+            T_d_files = [torch.from_numpy(dataset_transform(args.tmdir[0], file).get_transform('root', parameters.camera_names[1])).type(torch.float32)
+                         for file in args.testfiles]
+        metrics, n_data, n_results = evaluate_on_device(work, infer_device, mode, T_i1, args.batch, dgt, T_d_files)
+        if dgt is not None:
+            print('Ground truth on the device: %d windows, %d redone on the host' % (dgt.windows, dgt.declined))
+            gt_windows = (dgt.windows, dgt.declined)
+            dgt.close()
     else:
         metrics, n_data, n_results = evaluate(work, infer, mode, T_i1, args.batch)
     out = metrics.report()
@@ -462,5 +557,7 @@ def run(args, mode):
         if 'eval' in t:
             print('Mean time for evaluation on the device', t['eval'] / n_data)
     out['n_data'] = n_data
+    if device_gt:
+        out['gt_windows'], out['gt_declined'] = gt_windows
     eng.close()
     return out

@@ -9,6 +9,8 @@ the '-1' key or without any GT are skipped (:131-132, :166-167); one label per h
 index of the proposal containing it, or len(proposals) for unassigned heads (:208-216);
 metrics averaged over frames (:218-229).  Matching itself runs batched on the device.
 
+With --device-gt (which implies --device-metrics) the bodies are parsed on the GPU from the file's bytes
+(Engine.bodies_from_json) and handed to Engine.group_bodies as they are, in place of partition.pack_bodies.
 With --device-metrics the scoring runs there too: the bodies of a batch are packed (partition.pack_bodies) and grouped by
 Engine.group_bodies, the proposals become labels in Engine.partition_labels, Engine.partition_scores scores the two, and
 one [B,4] array comes back per batch; the totals are added here in frame order.  harness/partition.py states the
@@ -58,7 +60,7 @@ def gt_labels(frame):
     return labels
 
 
-def collect_work(args, calib):
+def collect_work(args, calib, src=None):
     work = []
     if args.synthetic:
         spec = synthetic.FrameSpec(persons=args.persons, noise_px=args.noise_px)
@@ -69,13 +71,15 @@ def collect_work(args, calib):
     n_input = 0
     for file in args.testfiles:
         print(file)
-        for frame in json.load(open(file, 'rb')):
+        for k, frame in enumerate(json.load(open(file, 'rb'))):
             n_input += 1
             if (n_input - 1) % args.datastep == 0:
                 if len(frame[list(frame.keys())[0]]) != 4:
                     print('There is no ground truth in the specified file')
                     raise SystemExit
                 work.append((frame, None))
+                if src is not None:
+                    src.append((args.testfiles.index(file), k))
     return work
 
 
@@ -121,32 +125,54 @@ def evaluate(work, infer, batch=256):
 KEYS = ('rand score', 'homogeneity', 'completeness', 'v_measure')
 
 
-def evaluate_on_device(work, infer, batch=256):
+def device_bodies(device_gt, start, n):
+    """The bodies of a batch parsed on the device (--device-gt) -> (packed: Engine.group_bodies' arrays as device tensors, S
+    [n] bodies per frame, valid [n]), or None when a window of the batch has to be redone on the host."""
+    parts = []
+    for i, j, file_no, first in device_gt.runs(start, n):
+        pb = device_gt.bodies(file_no, first, j - i)
+        if pb is None:
+            return None
+        parts.append(pb.packed())
+    packed = {k: (torch.cat([p[k] for p in parts], 0) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+    S, m1 = packed['n'].cpu().numpy(), packed['m1'].cpu().numpy()
+    valid = np.array([S[i] > 0 and bool(m1[i, :S[i]].all()) for i in range(n)])
+    return packed, S, valid
+
+
+def evaluate_on_device(work, infer, batch=256, device_gt=None):
     """evaluate() with --device-metrics.  `infer(frames, owners, packed)` -> (scores [B,4] float64 of the batch as
     Engine.partition_scores left them, H [B], M [B], finish) with finish(f) -> the frame's (proposals as rows, their
     number).  The skip rules are evaluate()'s and are known here from the counts: no GT person or a body without '-1'
     (gt_labels gives None), no graph (M == 0), len(labels) != H.  A frame that counts but came back as NaN (over a compiled
-    cap of the kernels, or a batch whose bodies cannot be packed) is finished by the numpy statement."""
+    cap of the kernels, or a batch whose bodies cannot be packed) is finished by the numpy statement.  With device_gt
+    (common.DeviceGT, --device-gt) the bodies come from device_bodies() instead of pack_bodies and stay on the device."""
     tot = np.zeros(4, np.float64)
     n_data = 0
     for start in range(0, len(work), batch):
         chunk = work[start:start + batch]
-        try:
-            packed = P.pack_bodies([f for f, _ in chunk])
-            S = packed['n']
-            valid = np.array([S[i] > 0 and bool(packed['m1'][i, :S[i]].all()) for i in range(len(chunk))])
-        except ValueError:               # more joint keys than presence bits, or a value that is not a point: the host groups this batch
-            packed = None
-            gts = [gt_labels(f) for f, _ in chunk]
-            S = np.array([len(g) if g is not None else 0 for g in gts], np.int32)
-            valid = np.array([g is not None for g in gts])
+        parsed = device_bodies(device_gt, start, len(chunk)) if device_gt is not None else None
+        if parsed is not None:
+            packed, S, valid = parsed
+        else:
+            try:
+                packed = P.pack_bodies([f for f, _ in chunk])
+                S = packed['n']
+                valid = np.array([S[i] > 0 and bool(packed['m1'][i, :S[i]].all()) for i in range(len(chunk))])
+            except ValueError:           # more joint keys than presence bits, or a value that is not a point: the host groups this batch
+                packed = None
+                gts = [gt_labels(f) for f, _ in chunk]
+                S = np.array([len(g) if g is not None else 0 for g in gts], np.int32)
+                valid = np.array([g is not None for g in gts])
         if not valid.any():
             continue
         # as in evaluate(): only the frames gt_labels() accepts are packed and matched
         sel = np.flatnonzero(valid)
         chunk, S = [chunk[i] for i in sel], S[sel]
         if packed is not None:
-            packed = {k: (v[sel] if isinstance(v, np.ndarray) else v) for k, v in packed.items()}
+            pick = torch.from_numpy(sel)
+            packed = {k: (v[sel] if isinstance(v, np.ndarray) else v.index_select(0, pick.to(v.device)) if isinstance(v, torch.Tensor) else v)
+                      for k, v in packed.items()}
         frames = [{c: [f[c][0], f[c][1]] for c in f if json.loads(f[c][0])} for f, _ in chunk]
         scores, H, M, finish = infer(frames, [o for _, o in chunk], packed)
         counted = (M != 0) & (S == H)
@@ -167,7 +193,11 @@ def evaluate_on_device(work, infer, batch=256):
 def run(args):
     from .common import max_skeletons_per_camera
     calib = Calibration(parameters)
-    work = collect_work(args, calib)
+    device_gt = getattr(args, 'device_gt', False) and not args.synthetic
+    if getattr(args, 'device_gt', False):
+        args.device_metrics = True
+    src = [] if device_gt else None
+    work = collect_work(args, calib, src)
     eng = Engine(parameters, calib, max_frames=args.batch,
                  max_persons_per_camera=max(4, args.persons + 1, max_skeletons_per_camera([(f, None, None) for f, _ in work])))
     load_models(eng, args, need_mlp=False)
@@ -207,7 +237,13 @@ def run(args):
         return (scores.cpu().numpy() if scores is not None else None), H, M, lambda f: (persons[f].cpu().numpy(), int(n_persons[f]))
 
     if getattr(args, 'device_metrics', False):
-        out = evaluate_on_device(work, infer_device, args.batch)
+        from .common import DeviceGT
+        dgt = DeviceGT(eng, args.testfiles, src, args.datastep) if device_gt else None
+        out = evaluate_on_device(work, infer_device, args.batch, dgt)
+        if dgt is not None:
+            print('Ground truth on the device: %d windows, %d redone on the host' % (dgt.windows, dgt.declined))
+            out['gt_windows'], out['gt_declined'] = dgt.windows, dgt.declined
+            dgt.close()
     else:
         out = evaluate(work, infer, args.batch)
     eng.close()

@@ -112,6 +112,23 @@ class mpe_partition_scores_args(C.Structure):
                 ('d_scores', C.c_void_p), ('d_status', C.c_void_p)]
 
 
+class mpe_json_bodies_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('n_entries', C.c_int32), ('scap', C.c_int32), ('d_text', C.c_void_p), ('d_entries', C.c_void_p),
+                ('d_frame_entry_off', C.c_void_p), ('d_xyz', C.c_void_p), ('d_mask', C.c_void_p), ('d_nkeys', C.c_void_p),
+                ('d_order', C.c_void_p), ('d_m1', C.c_void_p), ('d_n', C.c_void_p), ('d_entry_count', C.c_void_p),
+                ('d_body_cam', C.c_void_p), ('d_status', C.c_void_p), ('d_scratch', C.c_void_p), ('scratch_bytes', C.c_size_t)]
+
+
+class mpe_gt_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('scap', C.c_int32), ('gcap', C.c_int32), ('n_joints', C.c_int32), ('n_files', C.c_int32),
+                ('d_entries', C.c_void_p), ('d_frame_entry_off', C.c_void_p), ('d_entry_count', C.c_void_p), ('d_xyz', C.c_void_p),
+                ('d_mask', C.c_void_p), ('d_m1', C.c_void_p), ('d_T_d', C.c_void_p), ('d_file_of_frame', C.c_void_p), ('T_i1', c_f32p),
+                ('d_gt_xyz', C.c_void_p), ('d_gt_joint', C.c_void_p), ('d_gt_valid', C.c_void_p), ('d_n_gt_in', C.c_void_p)]
+
+
+# key slots of mpe_json_parse_bodies_device: joint key "j" -> slot j (0..30), "-1" -> slot 31
+MPE_GT_KEY_SLOTS, MPE_GT_M1_SLOT = 32, 31
+
 # per-frame status bits and compiled caps of mpe_partition_labels / mpe_group_bodies / mpe_partition_scores
 MPE_PART_SKIPPED, MPE_PART_OVER_CAP = 1, 2
 MPE_PART_MAX_SAMPLES, MPE_PART_MAX_SKELETONS, MPE_PART_MAX_KEYS = 256, 1024, 32
@@ -188,6 +205,12 @@ SYMBOLS = {
     'mpe_json_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     'mpe_json_parse_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(mpe_batch), C.c_void_p, C.c_void_p]),
+    'mpe_json_stage_gt_window': (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    'mpe_json_bodies_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'mpe_json_parse_bodies_device': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_json_bodies_args)]),
+    'mpe_gt_from_bodies': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_gt_args)]),
     'mpe_packed_free': (None, [C.c_void_p]),
     'mpe_pack_last_error': (C.c_char_p, []),
     'mpe_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),

@@ -216,6 +216,56 @@ def stage_json_window(index, params, stage, frame_start=0, frame_step=1, max_fra
     return nf.value, ne.value, stage.off_text + tb.value
 
 
+def stage_gt_window(index, cameras, stage, frame_start=0, frame_step=1, max_frames=0, n_threads=0):
+    """First level of the wire format for the ground truth (mpe_json_stage_gt_window): element [3] of EVERY camera entry of
+    the window's frames, in the frames' key order; an entry's cam is its position in `cameras`, -1 outside it.  -> (n_frames,
+    n_entries, bytes of the staging buffer in use).  NeedsHostParser for a camera entry without a fourth element that is
+    a list; MemoryError when the staging buffer is too small (the caller grows it)."""
+    import ctypes as C
+
+    from . import lib as L
+    lib = L.load()
+    cameras = list(cameras)
+    names = (C.c_char_p * len(cameras))(*[c.encode() for c in cameras])
+    nf, ne, tb = C.c_int32(), C.c_int32(), C.c_size_t()
+    mf = stage.max_frames if max_frames <= 0 or max_frames > stage.max_frames else max_frames
+    rc = lib.mpe_json_stage_gt_window(index.handle, names, len(cameras), frame_start, frame_step, mf, n_threads,
+                                      C.c_void_p(stage.ptr('text')), stage.text_cap, C.c_void_p(stage.ptr('entries')), stage.entry_cap,
+                                      C.c_void_p(stage.ptr('frame_entry_off')), C.byref(nf), C.byref(ne), C.byref(tb))
+    if rc == L.MPE_ERR_UNSUPPORTED:
+        raise NeedsHostParser(lib.mpe_pack_last_error().decode())
+    if rc == -2:
+        raise MemoryError(lib.mpe_pack_last_error().decode())
+    if rc != 0:
+        raise ValueError('mpe_json_stage_gt_window: %s' % lib.mpe_pack_last_error().decode())
+    return nf.value, ne.value, stage.off_text + tb.value
+
+
+class ParsedBodies:
+    """bodies_3D of one window, parsed on the device (Engine.bodies_from_json).  status: 0, or bit 0 = the window holds
+    something the device leaves to the host parser (the tensors are then None or not to be used), bit 1 = a frame has
+    more than scap bodies.  Device tensors in the layout mpe_group_bodies takes (key slot j = joint key j, slot 31 = '-1'):
+    xyz [B,scap,32,3] f64, mask [B,scap] i32 (the bits of a uint32), nkeys [B,scap] i32, order [B,scap,32] u8, m1 [B,scap]
+    u8, n [B] i32 (bodies of configured cameras), entry_count [n_entries] i32, body_cam [B,scap] i32; entries [n_entries,4]
+    i32 (frame, cam, begin, end) and frame_entry_off [B+1] i32 as staged."""
+
+    FIELDS = ('xyz', 'mask', 'nkeys', 'order', 'm1', 'n', 'entry_count', 'body_cam', 'entries', 'frame_entry_off')
+
+    def __init__(self, status, n_frames=0, n_entries=0, scap=0, **tensors):
+        self.status, self.n_frames, self.n_entries, self.scap = int(status), int(n_frames), int(n_entries), int(scap)
+        for k in self.FIELDS:
+            setattr(self, k, tensors.get(k))
+
+    def packed(self):
+        """The arrays Engine.group_bodies takes (harness.partition.pack_bodies' names), still on the device."""
+        return {k: getattr(self, k) for k in ('xyz', 'mask', 'nkeys', 'order', 'm1', 'n')}
+
+    def numpy(self):
+        out = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}
+        out['mask'] = out['mask'].view('uint32')
+        return out
+
+
 class ParsedOnDevice:
     """A batch whose arrays exist on the device only (device-side parse): what Engine.match / mlp3d /
     triangulate need of a DeviceBatch.  `download()` brings the arrays back as a PackedBatch (tests)."""

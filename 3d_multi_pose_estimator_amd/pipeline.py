@@ -13,8 +13,8 @@ import torch
 from . import lib as L
 from .calibration import Calibration
 from .logtable import DEVICE_ENTRIES, log_table
-from .packing import (CapacityArena, DeviceBatch, JsonIndex, JsonStage, NeedsHostParser, PackedBatch, ParsedOnDevice, pack_frames,
-                      pack_json, pack_json_into, stage_json_window)
+from .packing import (CapacityArena, DeviceBatch, JsonIndex, JsonStage, NeedsHostParser, PackedBatch, ParsedBodies, ParsedOnDevice,
+                      pack_frames, pack_json, pack_json_into, stage_gt_window, stage_json_window)
 
 
 def _f32p(a):
@@ -89,6 +89,7 @@ class Engine:
         self._state = {}                 # what was loaded / set, so that sibling() can repeat it
         self._siblings = []
         self._json_streams = None
+        self._gt_bufs = None             # staging buffers of bodies_from_json, kept between calls
         self._log_table_set = False      # partition_scores hands the table of logarithms to the context at its first call
         if os.environ.get('MPE_JSON_STREAMS_EARLY', '0') == '1':           # diagnostics (see _make_json_streams)
             self._make_json_streams()
@@ -600,6 +601,105 @@ class Engine:
             if index is not text:
                 index.close()
 
+    # ---- ground-truth bodies parsed on the device ------------------------------------------------
+    def bodies_from_json(self, index_or_text, frame_start=0, frame_step=1, max_frames=0, scap=None, cameras=None, n_threads=0,
+                         entries_per_frame=None):
+        """bodies_3D (element [3] of every camera entry) of one window of a document, parsed on the device: host staging
+        of the first level (mpe_json_stage_gt_window), one copy, mpe_json_parse_bodies_device, the status word read back.
+        cameras: the configured cameras (default params.used_cameras); scap: rows per frame (default 2 * hpf);
+        entries_per_frame: camera keys a frame may hold (default 2 * V).  -> packing.ParsedBodies; with a non-zero status
+        the caller takes the host path for the window (json.load, harness.common.ground_truth / partition.pack_bodies)."""
+        index = index_or_text if isinstance(index_or_text, JsonIndex) else JsonIndex(index_or_text)
+        try:
+            B = int(max_frames) if max_frames > 0 else self.max_frames
+            cameras = list(self.params.used_cameras if cameras is None else cameras)
+            scap = int(scap) if scap else 2 * self.hpf
+            epf = int(entries_per_frame) if entries_per_frame else 2 * self.V
+            size = len(index.text)
+            bound = size + 16 * B * epf + 256                           # the whole document, every entry padded: always enough
+            bufs = self._gt_bufs
+            if bufs is None or bufs['B'] < B or bufs['epf'] < epf:
+                bufs = None
+            while True:
+                if bufs is None:
+                    cap = min(bound, max(1 << 20, B * epf * 4096))
+                    cap = (cap + 255) // 256 * 256
+                    bufs = {'B': B, 'epf': epf, 'cap': cap, 'host': JsonStage(epf, B, cap, 'pinned'), 'dev': JsonStage(epf, B, cap, self.device),
+                            'status_host': torch.zeros(1, dtype=torch.int32).pin_memory()}
+                try:
+                    nf, ne, used = stage_gt_window(index, cameras, bufs['host'], frame_start, frame_step, B, n_threads)
+                    break
+                except NeedsHostParser:
+                    return ParsedBodies(1)
+                except MemoryError:
+                    if bufs['cap'] >= bound:
+                        raise ValueError('a frame holds more than %d camera entries' % bufs['epf'])
+                    cap = (min(bound, 4 * bufs['cap']) + 255) // 256 * 256
+                    bufs = {'B': bufs['B'], 'epf': bufs['epf'], 'cap': cap, 'host': JsonStage(bufs['epf'], bufs['B'], cap, 'pinned'),
+                            'dev': JsonStage(bufs['epf'], bufs['B'], cap, self.device), 'status_host': bufs['status_host']}
+            self._gt_bufs = bufs
+            dev, d = bufs['dev'], self.device
+            dev.buf[:used].copy_(bufs['host'].buf[:used], non_blocking=True)
+            rows = (nf, scap)
+            t = {'xyz': torch.empty(rows + (L.MPE_GT_KEY_SLOTS, 3), dtype=torch.float64, device=d),
+                 'mask': torch.empty(rows, dtype=torch.int32, device=d), 'nkeys': torch.empty(rows, dtype=torch.int32, device=d),
+                 'order': torch.empty(rows + (L.MPE_GT_KEY_SLOTS,), dtype=torch.uint8, device=d), 'm1': torch.empty(rows, dtype=torch.uint8, device=d),
+                 'n': torch.empty((nf,), dtype=torch.int32, device=d), 'entry_count': torch.empty((max(1, ne),), dtype=torch.int32, device=d),
+                 'body_cam': torch.empty(rows, dtype=torch.int32, device=d)}
+            status = torch.empty((1,), dtype=torch.int32, device=d)
+            nsc = int(self.lib.mpe_json_bodies_scratch_bytes(ne, scap))
+            scratch = torch.empty(nsc, dtype=torch.uint8, device=d)
+            a = L.mpe_json_bodies_args()
+            a.n_frames, a.n_entries, a.scap = nf, ne, scap
+            a.d_text, a.d_entries, a.d_frame_entry_off = dev.ptr('text'), dev.ptr('entries'), dev.ptr('frame_entry_off')
+            a.d_xyz, a.d_mask, a.d_nkeys, a.d_order, a.d_m1 = (t[k].data_ptr() for k in ('xyz', 'mask', 'nkeys', 'order', 'm1'))
+            a.d_n, a.d_entry_count, a.d_body_cam = t['n'].data_ptr(), t['entry_count'].data_ptr(), t['body_cam'].data_ptr()
+            a.d_status, a.d_scratch, a.scratch_bytes = status.data_ptr(), scratch.data_ptr(), nsc
+            self._chk(self.lib.mpe_json_parse_bodies_device(self.ctx, self._stream(), C.byref(a)))
+            # the entry tables leave the staging buffer (it is reused by the next window)
+            t['entries'] = dev.buf[dev.off_entries: dev.off_entries + 16 * max(1, ne)].clone().view(torch.int32).reshape(-1, 4)
+            t['frame_entry_off'] = dev.buf[dev.off_feo: dev.off_feo + 4 * (nf + 1)].clone().view(torch.int32)
+            bufs['status_host'].copy_(status, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            t['entry_count'] = t['entry_count'][:ne] if ne else t['entry_count'][:0]
+            t['entries'] = t['entries'][:ne]
+            return ParsedBodies(int(bufs['status_host'][0]), nf, ne, scap, **t)
+        finally:
+            if index is not index_or_text:
+                index.close()
+
+    def ground_truth(self, bodies, T_d_list, file_of_frame, T_i1, gcap=None):
+        """The metrics scripts' ground truth of every frame of `bodies` (a ParsedBodies with status 0) on the device
+        (mpe_gt_from_bodies): the camera with the most bodies (the first of equals, any camera of the frame), centimetres
+        -> metres, then T_i1 @ (T_d @ x) in the fp32 arithmetic of torch's CPU matmul.  T_d_list: one 4x4 per file,
+        file_of_frame [B]: the file of every frame; T_i1: 4x4.  -> harness.common.pack_ground_truth's dict as device
+        tensors ('xyz' [B,gcap,J,3] f32, 'joint' [B,gcap,J] u8, 'valid' [B,gcap] u8, 'n' [B] i32), which Engine.evaluate
+        takes as it is; gcap defaults to bodies.scap."""
+        if bodies.status != 0:
+            raise ValueError('the window was not parsed on the device (status %d)' % bodies.status)
+        B, d = bodies.n_frames, self.device
+        gcap = int(gcap) if gcap else bodies.scap
+        Td = np.ascontiguousarray(np.stack([np.asarray(T, dtype=np.float32).reshape(4, 4) for T in T_d_list]), np.float32)
+        fof = np.ascontiguousarray(np.asarray(file_of_frame, dtype=np.int32).reshape(-1))
+        if len(fof) != B or (B and (fof.min() < 0 or fof.max() >= len(Td))):
+            raise ValueError('file_of_frame must name one of the %d transforms for each of the %d frames' % (len(Td), B))
+        Ti = np.ascontiguousarray(np.asarray(T_i1, dtype=np.float32).reshape(16))
+        Td_d, fof_d = torch.from_numpy(Td).to(d), torch.from_numpy(fof).to(d)
+        out = {'xyz': torch.empty((B, gcap, self.J, 3), dtype=torch.float32, device=d),
+               'joint': torch.empty((B, gcap, self.J), dtype=torch.uint8, device=d),
+               'valid': torch.empty((B, gcap), dtype=torch.uint8, device=d), 'n': torch.empty((B,), dtype=torch.int32, device=d)}
+        a = L.mpe_gt_args()
+        a.n_frames, a.scap, a.gcap, a.n_joints, a.n_files = B, bodies.scap, gcap, self.J, len(Td)
+        ec = bodies.entry_count if bodies.n_entries else torch.zeros(1, dtype=torch.int32, device=d)
+        en = bodies.entries if bodies.n_entries else torch.zeros((1, 4), dtype=torch.int32, device=d)
+        a.d_entries, a.d_frame_entry_off, a.d_entry_count = en.data_ptr(), bodies.frame_entry_off.data_ptr(), ec.data_ptr()
+        a.d_xyz, a.d_mask, a.d_m1 = bodies.xyz.data_ptr(), bodies.mask.data_ptr(), bodies.m1.data_ptr()
+        a.d_T_d, a.d_file_of_frame, a.T_i1 = Td_d.data_ptr(), fof_d.data_ptr(), _f32p(Ti)
+        a.d_gt_xyz, a.d_gt_joint, a.d_gt_valid, a.d_n_gt_in = (out[k].data_ptr() for k in ('xyz', 'joint', 'valid', 'n'))
+        self._chk(self.lib.mpe_gt_from_bodies(self.ctx, self._stream(), C.byref(a)))
+        out['_keep'] = (Td_d, fof_d, ec, en)
+        return out
+
     def run_pipelined(self, batches, mode='mlp', contexts=1):
         """Batches (DeviceBatch or PackedBatch) -> (poses, n_persons, persons) per batch, in order.
 
@@ -874,13 +974,20 @@ class Engine:
             raise ValueError('n_persons must be int32 [%d]' % B)
         if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous()):
             raise ValueError('poses, flags and n_persons must be contiguous')
-        if gt['xyz'].shape[0] != B or np.any(np.asarray(gt['n']) > gt['xyz'].shape[1]):
+        on_device = isinstance(gt['xyz'], torch.Tensor)          # Engine.ground_truth's tensors are taken as they are
+        if gt['xyz'].shape[0] != B or (not on_device and np.any(np.asarray(gt['n']) > gt['xyz'].shape[1])):
             raise ValueError('ground truth for %d frames, batch has %d' % (gt['xyz'].shape[0], B))
         if skip is None:
             skip = (np.diff(np.asarray(db.host.frame_en_off[:B + 1])) == 0).astype(np.uint8)
         dev = self.device
         gcap = max(1, gt['xyz'].shape[1])
-        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev, non_blocking=False)
+
+        def up(a, dt):
+            if isinstance(a, torch.Tensor):
+                if a.dtype != dt or a.device != dev:
+                    raise ValueError('ground-truth tensors must be %s on %s' % (dt, dev))
+                return a.contiguous()
+            return torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev, non_blocking=False)
         gx = up(gt['xyz'], torch.float32) if gt['xyz'].shape[1] else torch.zeros((B, 1, self.J, 3), dtype=torch.float32, device=dev)
         gj = up(gt['joint'], torch.uint8) if gt['xyz'].shape[1] else torch.zeros((B, 1, self.J), dtype=torch.uint8, device=dev)
         gv = up(gt['valid'], torch.uint8) if gt['xyz'].shape[1] else torch.zeros((B, 1), dtype=torch.uint8, device=dev)
@@ -988,7 +1095,8 @@ class Engine:
 
     def group_bodies(self, packed, skip_in=None):
         """Ground-truth persons of every frame by greedy 3D proximity on the device (mpe_group_bodies; test/sm_metrics.py:
-        125-157).  packed: harness.partition.pack_bodies' arrays; skip_in [B]: frames not to group.  -> dict of device
+        125-157).  packed: harness.partition.pack_bodies' arrays, or ParsedBodies.packed() (device tensors, taken as they
+        are); skip_in [B]: frames not to group.  -> dict of device
         tensors: labels [B,Scap] i32 (-1 beyond the frame's skeletons), count [B] i32 (skeletons), n_groups [B] i32,
         skip [B] u8 (no person, a body without '-1', or skip_in), status [B] i32."""
         B = len(packed['n'])
@@ -996,8 +1104,9 @@ class Engine:
         if kcap > L.MPE_PART_MAX_KEYS:
             raise ValueError('%d distinct joint keys, at most %d' % (kcap, L.MPE_PART_MAX_KEYS))
         dev = self.device
-        up = lambda v, dt: torch.as_tensor(np.ascontiguousarray(v, dtype=dt)).to(dev)
-        t = {'xyz': up(packed['xyz'], np.float64), 'mask': up(packed['mask'].view(np.int32), np.int32), 'nkeys': up(packed['nkeys'], np.int32),
+        up = lambda v, dt: v.contiguous() if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v, dtype=dt)).to(dev)
+        mask = packed['mask'] if isinstance(packed['mask'], torch.Tensor) else packed['mask'].view(np.int32)
+        t = {'xyz': up(packed['xyz'], np.float64), 'mask': up(mask, np.int32), 'nkeys': up(packed['nkeys'], np.int32),
              'order': up(packed['order'], np.uint8), 'm1': up(packed['m1'], np.uint8), 'n': up(packed['n'], np.int32)}
         sk = up(np.asarray(skip_in).astype(np.uint8), np.uint8) if skip_in is not None else None
         out = {'labels': torch.empty((B, scap), dtype=torch.int32, device=dev), 'count': t['n'],

@@ -564,6 +564,83 @@ int mpe_json_parse_device(mpe_ctx *ctx, void *stream, const char *d_text, const 
                           int32_t skeletons_per_string_cap, void *d_scratch, size_t scratch_bytes, const mpe_batch *out,
                           int32_t *d_skeleton_index, int32_t *d_totals);
 
+/* ---- ground-truth bodies of the frame JSON on the device (csrc/jsonparse.hip, csrc/gt.hip) -----------------
+ * The fourth element of every camera entry is bodies_3D: a JSON list (not a string) of dicts {"<joint>": [x, y, z],
+ * ..., "-1": [x, y, z]}, centimetres.  mpe_json_stage_gt_window is mpe_json_stage_window for that element: for every
+ * frame of the window and EVERY camera key of the frame, in the frame's key order, one mpe_json_entry with the extent
+ * of element [3] (cam = the position in camera_names, -1 for a key that is not configured: test/metrics_from_model.py:
+ * 126-138 looks at all keys), the extents copied 16-byte aligned into text_dst.  The host walks the first level only;
+ * it neither counts nor parses bodies.  MPE_ERR_UNSUPPORTED for a camera entry that is not a list of exactly four
+ * elements or whose element [3] is not a list: the caller then takes the host path (json.load), which keeps the
+ * reference's "There is no ground truth" behaviour. */
+int mpe_json_stage_gt_window(mpe_json_index *ix, const char *const *camera_names, int32_t n_cameras, int32_t frame_start,
+                             int32_t frame_step, int32_t max_frames, int32_t n_threads, char *text_dst, size_t text_cap,
+                             mpe_json_entry *entries, int32_t entry_cap, int32_t *frame_entry_off, int32_t *n_frames,
+                             int32_t *n_entries, size_t *text_bytes);
+
+/* The staged lists parsed on the device into the arrays mpe_group_bodies takes (kcap = MPE_GT_KEY_SLOTS; they can be
+ * passed to it as they are).  Row [f][s]: the bodies of frame f's CONFIGURED cameras in (entry order, list order) --
+ * d_n[f] of them, what harness/partition.py:pack_bodies packs -- and behind them the bodies of the entries with cam ==
+ * -1 in the same order (mpe_gt_from_bodies may select such a camera).  Key slots are fixed: joint key "j", j in
+ * 0..30, is slot j and "-1" is slot 31 (mpe_group_bodies sums over the founding skeleton's keys in d_order and does
+ * not depend on the numbering).  The numbers are the correctly rounded binary64 of the decimal text (Python's float()),
+ * untouched.  Accepted language per body: {"<key>": [n, n, n], ...} with blanks between tokens; any other key (a
+ * leading zero, "-0", 31 and up, text), a value that is not a list of exactly three numbers, null / NaN / Infinity,
+ * a number of more than 19 significant digits or outside the exact conversion's range, a duplicate key in a body and
+ * any nesting set bit 0 of *d_status ("host parser, please"); a frame with more than scap bodies sets bit 1 -- the two
+ * bits and the contract of mpe_json_parse_device's status word.  With a non-zero status the arrays are not to be used.
+ *   d_scratch  mpe_json_bodies_scratch_bytes(n_entries, scap) bytes of device memory */
+#define MPE_GT_KEY_SLOTS 32
+#define MPE_GT_M1_SLOT 31
+typedef struct {
+    int32_t n_frames, n_entries, scap;
+    const char *d_text;                   /* staged text                                            */
+    const mpe_json_entry *d_entries;      /* [n_entries]                                            */
+    const int32_t *d_frame_entry_off;     /* [n_frames+1]                                           */
+    double *d_xyz;                        /* [n_frames][scap][32][3], 0 where the key is absent     */
+    uint32_t *d_mask;                     /* [n_frames][scap] bit per key slot                      */
+    int32_t *d_nkeys;                     /* [n_frames][scap]                                       */
+    uint8_t *d_order;                     /* [n_frames][scap][32] key slots in the body's dict order*/
+    uint8_t *d_m1;                        /* [n_frames][scap] '-1' in body                          */
+    int32_t *d_n;                         /* [n_frames] bodies of configured cameras                */
+    int32_t *d_entry_count;               /* [n_entries] bodies of every entry, configured or not   */
+    int32_t *d_body_cam;                  /* [n_frames][scap] camera index of the row's entry; -1 for a non-configured camera and for unused rows */
+    int32_t *d_status;                    /* [1]                                                    */
+    void *d_scratch;
+    size_t scratch_bytes;
+} mpe_json_bodies_args;
+size_t mpe_json_bodies_scratch_bytes(int32_t n_entries_cap, int32_t scap);
+int mpe_json_parse_bodies_device(mpe_ctx *ctx, void *stream, const mpe_json_bodies_args *a);
+
+/* Ground truth of the metrics scripts from the parsed bodies (test/metrics_from_model.py:126-174), one workgroup per
+ * frame, written as mpe_eval_batch reads it.  Camera: the frame's first entry, replaced by a later entry only when its
+ * d_entry_count is STRICTLY greater (all keys of the frame, configured or not).  d_n_gt_in[f] = that entry's bodies
+ * (0: the frame the callers skip); body b of it, joint j < n_joints:
+ *   d_gt_joint[f][b][j] = key "j" present;  d_gt_valid[f][b] = '-1' present;  d_gt_xyz[f][b][j] = 0 when absent, else
+ *   g_k = (float)(v_k / 100.0)             an IEEE f64 division, then one rounding to f32;  x = (g_0, g_1, g_2, 1)
+ *   y = T_d[file_of_frame[f]] x ; w = T_i1 y   (the first three rows of w), every row of both products
+ *   acc = T[i][0] * x_0 ; acc = fmaf(T[i][k], x_k, acc) for k = 1, 2, 3    fp32, nothing else contracted
+ * which gives the bits of torch's fp32 matmul on the CPU (harness/groundtruth.py states it in numpy, exactly).
+ * T_i1 is HOST memory (16 floats, copied into the launch); d_T_d [n_files][4][4] f32 and d_file_of_frame [n_frames] are
+ * device arrays.  MPE_ERR_CAPACITY for gcap < scap or n_joints > 31. */
+typedef struct {
+    int32_t n_frames, scap, gcap, n_joints, n_files;
+    const mpe_json_entry *d_entries;
+    const int32_t *d_frame_entry_off;     /* [n_frames+1]                  */
+    const int32_t *d_entry_count;         /* [n_entries]                   */
+    const double *d_xyz;                  /* [n_frames][scap][32][3]       */
+    const uint32_t *d_mask;               /* [n_frames][scap]              */
+    const uint8_t *d_m1;                  /* [n_frames][scap]              */
+    const float *d_T_d;                   /* [n_files][16]                 */
+    const int32_t *d_file_of_frame;       /* [n_frames]                    */
+    const float *T_i1;                    /* HOST [16]                     */
+    float *d_gt_xyz;                      /* [n_frames][gcap][n_joints][3] */
+    uint8_t *d_gt_joint;                  /* [n_frames][gcap][n_joints]    */
+    uint8_t *d_gt_valid;                  /* [n_frames][gcap]              */
+    int32_t *d_n_gt_in;                   /* [n_frames]                    */
+} mpe_gt_args;
+int mpe_gt_from_bodies(mpe_ctx *ctx, void *stream, const mpe_gt_args *a);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

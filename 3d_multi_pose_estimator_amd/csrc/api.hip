@@ -1326,6 +1326,91 @@ int mpe_eval_batch(mpe_ctx *ctx, void *stream, const mpe_eval_args *a) {
     return MPE_OK;
 }
 
+int mpe_track_destroy(mpe_ctx *ctx, mpe_track_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    for (int i = 0; i < 2; ++i) {
+        dev_free(ctx, st->pose[i]);
+        dev_free(ctx, st->mask[i]);
+        dev_free(ctx, st->id[i]);
+        dev_free(ctx, st->child[i]);
+    }
+    dev_free(ctx, st->count);
+    dev_free(ctx, st->ws);
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_track_create(mpe_ctx *ctx, int32_t pcap, int32_t n_joints, int32_t max_gap, int32_t pose_f64, mpe_track_state **out) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_track_create: NULL argument");
+    *out = nullptr;
+    if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || max_gap < 0 || (pose_f64 & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_create: bad sizes or pose type");
+    if (pcap > MPE_TRACK_MAX_PERSONS || max_gap > MPE_TRACK_MAX_GAP)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_create: pcap %d / max_gap %d over %d / %d", pcap, max_gap, MPE_TRACK_MAX_PERSONS,
+                    MPE_TRACK_MAX_GAP);
+    DeviceGuard dg(ctx);
+    mpe_track_state *st = new (std::nothrow) mpe_track_state();
+    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_track_create: out of memory");
+    st->pcap = pcap;
+    st->J = n_joints;
+    st->H = max_gap + 1;
+    st->pose_f64 = pose_f64;
+    const size_t rows = (size_t)st->H * pcap;
+    int rc = MPE_OK;
+    for (int i = 0; i < 2 && !rc; ++i) {
+        rc = dev_alloc(ctx, &st->pose[i], rows * n_joints * 3);
+        if (!rc) rc = dev_alloc(ctx, &st->mask[i], rows);
+        if (!rc) rc = dev_alloc(ctx, &st->id[i], rows);
+        if (!rc) rc = dev_alloc(ctx, &st->child[i], rows);
+    }
+    if (!rc) rc = dev_alloc(ctx, &st->count, 2);
+    if (!rc) rc = dev_alloc(ctx, &st->ws, 1024);
+    if (!rc && track_prepare(pcap) != hipSuccess) rc = fail(ctx, MPE_ERR_HIP, "mpe_track_create: the stage kernel cannot have %d KB of LDS", pcap * pcap / 128);
+    if (rc) {
+        const std::string why = ctx->err;
+        mpe_track_destroy(ctx, st);
+        ctx->err = why;
+        return rc;
+    }
+    *out = st;
+    return MPE_OK;
+}
+
+int mpe_track_reset(mpe_ctx *ctx, void *stream, mpe_track_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_reset: NULL state");
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, launch_track_reset(static_cast<hipStream_t>(stream), st));
+    return MPE_OK;
+}
+
+int mpe_track_launches(mpe_ctx *ctx, const mpe_track_state *st, int64_t *n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_track_launches: NULL argument");
+    *n = st->launches;
+    return MPE_OK;
+}
+
+int mpe_track_batch(mpe_ctx *ctx, void *stream, mpe_track_state *st, const mpe_track_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->pcap != st->pcap || a->n_joints != st->J || a->pose_f64 != st->pose_f64)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: pcap %d / joints %d / pose_f64 %d, the state was made for %d / %d / %d", a->pcap,
+                    a->n_joints, a->pose_f64, st->pcap, st->J, st->pose_f64);
+    if (a->n_frames < 0 || (a->joint_flags & ~1) || !(a->gate > 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: bad frame count, flag mode or gate");
+    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_batch: %d frames over 2^23 per call", a->n_frames);
+    if (a->n_frames == 0) return MPE_OK;
+    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_link_cost || !a->d_link_gap || !a->d_issued)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: NULL argument");
+    HIPCHK(ctx, launch_track(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
 int mpe_reproject_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_reproject_args *a) {
     int rc = check_batch(ctx, b);
     if (rc) return rc;

@@ -177,6 +177,20 @@ struct mpe_ctx {
     int64_t bf_launches = 0;
 };
 
+// track.hip: what mpe_track_batch carries from call to call.  Two copies of the history ([H][pcap] rows each, H =
+// max_gap + 1 frames, oldest first): a call reads copy `cur`, writes the other one and makes it current.
+struct mpe_track_state {
+    int pcap = 0, J = 0, H = 0, pose_f64 = 0;
+    int cur = 0;
+    int64_t launches = 0;           // kernels enqueued since mpe_track_create
+    double *pose[2] = {};           // [H][pcap][J][3], widened to f64
+    uint32_t *mask[2] = {};         // [H][pcap] used joints present; 0: not a detection
+    int32_t *id[2] = {};            // [H][pcap]
+    uint8_t *child[2] = {};         // [H][pcap] 1: a later detection already continues this one
+    int32_t *count = nullptr;       // [2] ids issued so far
+    int32_t *ws = nullptr;          // [1024] scratch of the birth pass
+};
+
 namespace mpe {
 
 // gemm.hip
@@ -317,6 +331,11 @@ int cluster_table_cap(int hmax);
 
 // eval.hip
 hipError_t launch_eval(hipStream_t s, const mpe_eval_args &a);
+
+// track.hip
+hipError_t track_prepare(int pcap);                  // dynamic-LDS opt-in of the stage kernels for this device
+hipError_t launch_track_reset(hipStream_t s, mpe_track_state *st);
+hipError_t launch_track(hipStream_t s, mpe_track_state *st, const mpe_track_args &a);
 
 // reproject.hip
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);

@@ -59,6 +59,12 @@ def build_parser(description):
                         'parsed there from the files\' bytes (mpe_json_parse_bodies_device) and turned into the arrays the scoring kernels read '
                         '(mpe_gt_from_bodies in the metrics_from_* scripts, mpe_group_bodies in sm_metrics); a window the device declines is '
                         'redone on the host')
+    p.add_argument('--track', action='store_true',
+                   help='implies --device-metrics; the poses of the evaluated frames go through one tracker in order (mpe_track_batch: person '
+                        'identities over the frames, the state carried across --batch chunks) and one further line reports the tracks.  All '
+                        '--testfiles together are one sequence, in the order given: pass one recording per run')
+    p.add_argument('--track-gate', type=float, default=0.5, metavar='M', help='--track: largest mean joint distance of a link, metres')
+    p.add_argument('--track-gap', type=int, default=2, metavar='N', help='--track: frames a person may go undetected and keep the identity')
     return p
 
 
@@ -459,7 +465,7 @@ def max_skeletons_per_camera(work):
 def run(args, mode):
     calib = Calibration(parameters)
     device_gt = getattr(args, 'device_gt', False) and not args.synthetic       # synthetic frames have no file to parse
-    if getattr(args, 'device_gt', False):
+    if getattr(args, 'device_gt', False) or getattr(args, 'track', False):
         args.device_metrics = True
     src = [] if device_gt else None
     work = collect_work(args, calib, src)
@@ -472,6 +478,10 @@ def run(args, mode):
     T_i1 = torch.from_numpy(calib.T_i32[1])
     J = eng.J
     t = {'match': 0.0, '3d': 0.0}
+    tracker = summary = None
+    if getattr(args, 'track', False):
+        from .tracking import TrackSummary
+        tracker, summary = eng.tracker(mode, max_gap=args.track_gap, gate=args.track_gate), TrackSummary()
 
     def infer(frames, owners):
         db = eng.to_device(eng.pack(frames))
@@ -531,6 +541,11 @@ def run(args, mode):
         t['3d'] += t2 - t1
         t['eval'] += time.time() - t2
         eng.sync_status()
+        if tracker is not None:
+            # the frames that are evaluated (a cross-camera pair, as Engine.evaluate's skip rule has it), in order
+            keep = torch.from_numpy(np.flatnonzero(np.diff(np.asarray(db.host.frame_en_off[:db.n_frames + 1])) != 0)).to(poses.device)
+            tr = tracker.update(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
+            summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
         return ev
 
     if getattr(args, 'device_metrics', False):
@@ -556,6 +571,11 @@ def run(args, mode):
         print('Frames per second', n_data / max(1e-9, t['match'] + t['3d']))
         if 'eval' in t:
             print('Mean time for evaluation on the device', t['eval'] / n_data)
+    if tracker is not None:
+        out['tracks'] = summary.result()
+        print('Tracks (gate %g m, gap %d): %d, mean length %.3f frames, %d born after the first frame'
+              % (args.track_gate, args.track_gap, out['tracks']['tracks'], out['tracks']['mean_length'], out['tracks']['late_births']))
+        tracker.close()
     out['n_data'] = n_data
     if device_gt:
         out['gt_windows'], out['gt_declined'] = gt_windows

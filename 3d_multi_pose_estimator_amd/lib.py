@@ -83,6 +83,13 @@ class mpe_eval_args(C.Structure):
                 ('d_n_gt', C.c_void_p), ('d_n_res', C.c_void_p), ('d_status', C.c_void_p)]
 
 
+class mpe_track_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('used_joint_mask', C.c_uint32), ('gate', C.c_double),
+                ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p),
+                ('d_track_id', C.c_void_p), ('d_link_cost', C.c_void_p), ('d_link_gap', C.c_void_p), ('d_issued', C.c_void_p)]
+
+
 class mpe_reproject_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
                 ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float),
@@ -133,6 +140,9 @@ MPE_GT_KEY_SLOTS, MPE_GT_M1_SLOT = 32, 31
 MPE_PART_SKIPPED, MPE_PART_OVER_CAP = 1, 2
 MPE_PART_MAX_SAMPLES, MPE_PART_MAX_SKELETONS, MPE_PART_MAX_KEYS = 256, 1024, 32
 
+# compiled caps of mpe_track_create
+MPE_TRACK_MAX_PERSONS, MPE_TRACK_MAX_GAP = 128, 15
+
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
 
@@ -179,6 +189,11 @@ SYMBOLS = {
                                      C.c_void_p, C.c_int32, C.c_void_p]),
     'mpe_mlp_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     'mpe_eval_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_eval_args)]),
+    'mpe_track_create': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    'mpe_track_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_track_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_track_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_track_args)]),
+    'mpe_track_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),
     'mpe_partition_labels': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_partition_labels_args)]),

@@ -1011,6 +1011,13 @@ class Engine:
         out['_keep'] = (gx, gj, gv, gn, sk)          # inputs stay alive until the caller has synchronised
         return out
 
+    def tracker(self, mode, max_gap=2, gate=0.5, pcap=None):
+        """A Tracker for one sequence of poses in `mode` ('mlp': what mlp3d returns, 'tri': what triangulate returns):
+        person identities over the frames (mpe_track_batch).  A lost person is taken up again after up to `max_gap`
+        frames without a detection, within `gate` metres of mean joint distance.  pcap: rows per frame when the poses
+        are not this engine's (default: the engine's Pcap)."""
+        return Tracker(self, mode, max_gap, gate, self.pcap if pcap is None else int(pcap))
+
     def reproject(self, db, persons, n_persons, poses, flags, kind, joint_mask=None, threshold=0.5):
         """Reprojection residuals on the device (mpe_reproject_batch): how far every joint of every 3D pose lands from
         the 2D detection it came from, per camera -- a quality signal that needs no ground truth.  kind 'est': what mlp3d
@@ -1226,6 +1233,82 @@ class Engine:
         self._chk(self.lib.mpe_profile_read_bf16(self.ctx, C.byref(ms), C.byref(fl), C.byref(n)))
         out.update({'bf16_ms': ms.value, 'bf16_flop': fl.value, 'bf16_launches': n.value})       # plain bf16 launches (reduced modes)
         return out
+
+
+class Tracker:
+    """Engine.tracker's object: the device state of one sequence (the detections of the last max_gap + 1 frames with
+    their ids, and the id count).  update() takes the frames of the sequence in order, in chunks of any size; the ids
+    do not depend on the chunking.  Everything stays on the device and on the current stream: update() neither
+    synchronises nor reads anything back."""
+
+    def __init__(self, eng, mode, max_gap, gate, pcap):
+        if mode not in ('mlp', 'tri'):
+            raise ValueError('mode must be mlp or tri')
+        if not gate > 0:
+            raise ValueError('gate must be > 0')
+        self.eng, self.mode, self.max_gap, self.gate, self.pcap = eng, mode, int(max_gap), float(gate), pcap
+        self.state, self._issued = C.c_void_p(), None
+        eng._chk(eng.lib.mpe_track_create(eng.ctx, self.pcap, eng.J, self.max_gap, int(mode == 'tri'), C.byref(self.state)))
+
+    def update(self, poses, flags, n_persons):
+        """poses / flags / n_persons of the next B >= 0 frames, as mlp3d or triangulate returned them (shapes and types
+        as Engine.evaluate takes them).  -> {'ids' [B,Pcap] i32 (-1: no detection), 'cost' [B,Pcap] f64 (the link's
+        cost; -1.0 for a birth or no detection), 'gap' [B,Pcap] i32 (frames back to the parent; 0 birth, -1 no
+        detection), 'issued' [1] i32 (ids issued so far)}, device tensors."""
+        eng, tri = self.eng, self.mode == 'tri'
+        if not self.state:
+            raise RuntimeError('the tracker is closed')
+        B = int(poses.shape[0]) if poses.dim() == 4 else -1
+        want = torch.float64 if tri else torch.float32
+        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, eng.J, 3):
+            raise ValueError('poses must be %s [B,%d,%d,3]' % (want, self.pcap, eng.J))
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if tri else (B, self.pcap)):
+            raise ValueError('flags do not match mode %s' % self.mode)
+        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
+            raise ValueError('n_persons must be int32 [%d]' % B)
+        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous()):
+            raise ValueError('poses, flags and n_persons must be contiguous')
+        if any(t.device != eng.device for t in (poses, flags, n_persons)):
+            raise ValueError('poses, flags and n_persons must be on %s' % eng.device)
+        dev = eng.device
+        out = {'ids': torch.empty((B, self.pcap), dtype=torch.int32, device=dev),
+               'cost': torch.empty((B, self.pcap), dtype=torch.float64, device=dev),
+               'gap': torch.empty((B, self.pcap), dtype=torch.int32, device=dev)}
+        if B:
+            self._issued = torch.empty((1,), dtype=torch.int32, device=dev)
+        elif self._issued is None:                       # nothing tracked yet: the count is 0
+            self._issued = torch.zeros((1,), dtype=torch.int32, device=dev)
+        out['issued'] = self._issued
+        a = L.mpe_track_args()
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, self.pcap, eng.J, int(tri), int(tri)
+        a.used_joint_mask = sum(1 << j for j in eng.params.used_joints)
+        a.gate = self.gate
+        a.d_poses, a.d_flags, a.d_n_persons = poses.data_ptr(), flags.data_ptr(), n_persons.data_ptr()
+        a.d_track_id, a.d_link_cost, a.d_link_gap, a.d_issued = (out[k].data_ptr() for k in ('ids', 'cost', 'gap', 'issued'))
+        eng._chk(eng.lib.mpe_track_batch(eng.ctx, eng._stream(), self.state, C.byref(a)))
+        return out
+
+    def launches(self):
+        """Kernels this tracker has enqueued so far."""
+        n = C.c_int64()
+        self.eng._chk(self.eng.lib.mpe_track_launches(self.eng.ctx, self.state, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Start a new sequence (ordered on the current stream)."""
+        self.eng._chk(self.eng.lib.mpe_track_reset(self.eng.ctx, self.eng._stream(), self.state))
+        self._issued = None
+
+    def close(self):
+        if getattr(self, 'state', None) and self.eng.ctx:
+            self.eng.lib.mpe_track_destroy(self.eng.ctx, self.state)
+        self.state = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def explicit_m_cap(max_heads_per_frame):

@@ -270,6 +270,38 @@ def make_frame(calib, frame_index, spec=None, seed=1234):
     return frame, {'persons': pts, 'owner': owner}
 
 
+def frame_from_bodies(calib, frame_index, bodies, orders=None, hidden=()):
+    """make_frame's wire format for bodies the caller chooses: `bodies` [P,J,3] world metres, projected without noise
+    into every camera; person p's detections carry prob = 0.3 + 0.1 p (FrameSpec.identity_prob).  orders: {camera: the
+    order of the persons in its skeleton list}; hidden: persons no camera sees.  -> (frame, {camera: person of every
+    skeleton})."""
+    params = calib.params
+    bodies = np.asarray(bodies, np.float64)
+    P, J = bodies.shape[:2]
+    W, H = params.image_width, params.image_height
+    frame, owner = {}, {}
+    for cam in params.camera_names:
+        k = calib.index(cam)
+        order = list(orders[cam]) if orders and cam in orders else list(range(P))
+        skeletons, own = [], []
+        for p in order:
+            if p in hidden:
+                continue
+            uv, z = project_panoptic(bodies[p].T, calib.K32[k].astype(np.float64), calib.T_d[k], calib.dist[k])
+            sk = {}
+            for j in range(J):
+                x, y = float(uv[0, j]), float(uv[1, j])
+                if z[j] <= 0.1 or x < 0 or x >= W or y < 0 or y >= H:
+                    continue
+                sk[str(j)] = [j, x, y, 1, float(np.float32(0.3 + 0.1 * p))]
+            skeletons.append(sk)
+            own.append(p)
+        gt_cm = [{('-1' if j == 2 else str(j)): [float(c) * 100.0 for c in bodies[o, j]] for j in range(J)} for o in own]
+        frame[cam] = [json.dumps(skeletons), float(frame_index), 'no_image', gt_cm]
+        owner[cam] = own
+    return frame, owner
+
+
 def make_frames(calib, n, spec=None, seed=1234, start=0):
     frames, gts = [], []
     for i in range(start, start + n):

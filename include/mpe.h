@@ -641,6 +641,57 @@ typedef struct {
 } mpe_gt_args;
 int mpe_gt_from_bodies(mpe_ctx *ctx, void *stream, const mpe_gt_args *a);
 
+/* Tracking: one identity per person over the frames of a recording.  Row p of one frame's poses has nothing to do with
+ * row p of the next (person order is the clustering's; the reference's viewers colour by that row,
+ * test/show_results_from_model.py:276,321,329); mpe_track_batch gives every detection a track id that follows the person.
+ * The rule (harness/tracking.py states it in numpy, frame by frame, and the two agree exactly):
+ *   Detections of frame f: as in mpe_eval_batch.  joint_flags == 0: persons p < d_n_persons[f] with d_flags[f][p] != 0,
+ *   all joints present; joint_flags == 1: every p < d_n_persons[f], joint j present when d_flags[f][p][j] != 0.  Only
+ *   joints of used_joint_mask count; a person with no present used joint is not a detection.
+ *   Cost of a newer detection a against an older one b: over the used joints both have, in increasing j, the stored
+ *   coordinates widened to f64: dx, dy, dz = a - b; s = dx*dx; s = s + dy*dy; s = s + dz*dz (every product and sum
+ *   rounded on its own); d = sqrt(s), correctly rounded; the left-fold sum of d divided by the count.  No common joint:
+ *   +inf.  A pair is linkable when cost < gate (strict; a NaN never links).
+ *   Cascade, g = 1 .. max_gap + 1 (the tracks seen last choose first): for every frame t, rows = its detections without
+ *   a parent, columns = the detections of frame t - g without a child; take the linkable pair of least cost (ties: the
+ *   lowest row, then the lowest column, in detection order), link it, remove both, until none is left.  Within one g
+ *   the frames are independent; the result is that of the frame-by-frame online cascade.
+ *   Ids: a detection without a parent starts a track; ids are consecutive in birth order (frame, then detection order)
+ *   from the state's count; every other detection takes its parent's id.
+ * Outputs per row [n_frames][pcap]: d_track_id (-1: not a detection); d_link_cost f64 (-1.0 for a birth and for rows
+ * that are no detection); d_link_gap (g of the link, 0 for a birth, -1 no detection); *d_issued = ids issued so far.
+ * The state holds the detections of the last max_gap + 1 frames with their ids and has-child marks and the count, so a
+ * sequence may arrive in any chunking (one frame per call included) and gets the same ids; joint_flags, used_joint_mask
+ * and gate are per call.  mpe_track_create allocates all device memory the calls need (MPE_ERR_CAPACITY for pcap >
+ * MPE_TRACK_MAX_PERSONS or max_gap > MPE_TRACK_MAX_GAP); mpe_track_reset starts a new sequence, ordered on `stream`;
+ * mpe_track_batch is ordered on `stream` like the other batch entry points and neither synchronises nor allocates: max_gap + 7
+ * kernels whatever n_frames is (mpe_track_launches: the launches of a state that the runtime accepted, counted on the host).  n_frames == 0 does
+ * nothing.  Sizes or a pose type other than the state's: MPE_ERR_INVALID (the code this header has for a bad argument),
+ * with the three values in mpe_last_error; n_frames > 2^23: MPE_ERR_CAPACITY.  Calls on one state belong on one stream,
+ * in sequence order. */
+#define MPE_TRACK_MAX_PERSONS 128
+#define MPE_TRACK_MAX_GAP 15
+typedef struct mpe_track_state mpe_track_state;
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t used_joint_mask;
+    double gate;                   /* metres, > 0 */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    const int32_t *d_n_persons;    /* [n_frames] */
+    int32_t *d_track_id;           /* [n_frames][pcap] */
+    double *d_link_cost;           /* [n_frames][pcap] */
+    int32_t *d_link_gap;           /* [n_frames][pcap] */
+    int32_t *d_issued;             /* [1] */
+} mpe_track_args;
+int mpe_track_create(mpe_ctx *ctx, int32_t pcap, int32_t n_joints, int32_t max_gap, int32_t pose_f64, mpe_track_state **out);
+int mpe_track_reset(mpe_ctx *ctx, void *stream, mpe_track_state *state);
+int mpe_track_destroy(mpe_ctx *ctx, mpe_track_state *state);
+int mpe_track_batch(mpe_ctx *ctx, void *stream, mpe_track_state *state, const mpe_track_args *a);
+int mpe_track_launches(mpe_ctx *ctx, const mpe_track_state *state, int64_t *n);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

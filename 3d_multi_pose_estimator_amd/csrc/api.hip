@@ -1425,6 +1425,26 @@ int mpe_reproject_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mp
     return MPE_OK;
 }
 
+int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_refine_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames != b->n_frames || a->pcap < 1 || a->n_joints != ctx->cfg.n_joints || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: bad sizes or modes (%d frames, the batch has %d; %d joints, the context has %d)",
+                    a->n_frames, b->n_frames, a->n_joints, ctx->cfg.n_joints);
+    if (a->max_iters < 1 || a->max_iters > MPE_REFINE_MAX_ITERS)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: max_iters %d outside 1..%d", a->max_iters, MPE_REFINE_MAX_ITERS);
+    if (!(a->step_tol >= 0.0) || !(a->huber_px >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: step_tol %g and huber_px %g must not be negative", a->step_tol, a->huber_px);
+    if (b->n_frames == 0) return MPE_OK;
+    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags || !a->d_poses_out || !a->d_status || !a->d_cost0 || !a->d_cost1 ||
+        !a->d_iters || !a->d_n_views)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: NULL argument");
+    HIPCHK(ctx, launch_refine(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
+    return MPE_OK;
+}
+
 int mpe_residual_stats(mpe_ctx *ctx, void *stream, const mpe_residual_stats_args *a) {
     if (!ctx) return MPE_ERR_INVALID;
     if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_residual_stats: NULL argument");

@@ -339,6 +339,8 @@ hipError_t launch_track(hipStream_t s, mpe_track_state *st, const mpe_track_args
 
 // reproject.hip
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);
+// refine.hip
+hipError_t launch_refine(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_refine_args &a);
 // partition.hip
 hipError_t launch_partition_labels(hipStream_t s, int V, const mpe_batch &b, const mpe_partition_labels_args &a);
 hipError_t launch_group_bodies(hipStream_t s, const mpe_group_bodies_args &a);

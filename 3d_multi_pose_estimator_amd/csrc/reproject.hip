@@ -15,6 +15,7 @@
 // rank, narrows the prefix, clears the bins).  The sum is reduced in a fixed order (k_res_sum: a fixed stride per
 // thread, an LDS tree per workgroup, the partials folded by one wave): same input, same bits.
 #include "mpe_internal.h"
+#include "reproject_select.h"
 
 #pragma clang fp contract(off)
 
@@ -28,16 +29,10 @@ __device__ inline float div_rn(float a, float b) { return (float)((double)a / (d
 __device__ inline float sqrt_rn(float a) { return (float)sqrt((double)a); }
 
 struct ReprojK {
-    int n_frames, pcap, V, J, pose_f64, joint_flags;
-    uint32_t joint_mask;
-    float threshold;
-    const int32_t *frame_head_off;
-    const uint32_t *head_joint_mask;
+    int n_frames, pcap, V, J, pose_f64;
+    Selection sel;                            // which entries count (reproject_select.h)
     const double *xy;
-    const float *vp;
-    const int32_t *persons, *n_persons;
     const void *poses;
-    const uint8_t *flags;
     double *res;
 };
 
@@ -50,26 +45,12 @@ __global__ void __launch_bounds__(32 * RP_GROUPS) k_reproject(const DevCfg *__re
         const int f = (int)(fp / a.pcap);
         int head = -1;
         uint32_t present = 0;
-        if (j == 0) {
-            const int p = (int)(fp - (long long)f * a.pcap);
-            const int np = a.n_persons[f];
-            if (p < np) {
-                const int h0 = a.frame_head_off[f], h1 = a.frame_head_off[f + 1];
-                const int id = a.persons[g];
-                if (id >= 0 && id < h1 - h0 && (a.joint_flags || a.flags[fp] != 0)) {
-                    head = h0 + id;
-                    present = a.head_joint_mask[head] & a.joint_mask;
-                }
-            }
-        }
+        if (j == 0 && sel_person(a.sel, f, (int)(fp - (long long)f * a.pcap), fp)) head = sel_head(a.sel, f, fp, c, &present);
         head = __shfl(head, 0, 32);
         present = __shfl(present, 0, 32);
         if (j >= a.J) continue;
         double out = -1.0;
-        bool take = head >= 0 && ((present >> j) & 1u);
-        if (take && a.joint_flags) take = a.flags[fp * a.J + j] != 0;
-        if (take) take = a.vp[((size_t)head * a.J + j) * 2] > a.threshold;
-        if (take) {
+        if (sel_joint(a.sel, fp, j, head, present)) {
             float X, Y, Z;
             if (a.pose_f64) {
                 const double *q = static_cast<const double *>(a.poses) + ((size_t)fp * a.J + j) * 3;
@@ -244,8 +225,10 @@ __global__ void __launch_bounds__(256) k_res_pick(ResidualState *st, uint32_t *h
 }  // namespace
 
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &x) {
-    ReprojK a{x.n_frames, x.pcap, V, x.n_joints, x.pose_f64, x.joint_flags, x.joint_mask, x.threshold, b.d_frame_head_off,
-              b.d_joint_mask, b.d_xy, b.d_vp, x.d_persons, x.d_n_persons, x.d_poses, x.d_flags, x.d_res};
+    ReprojK a{x.n_frames, x.pcap, V, x.n_joints, x.pose_f64,
+              Selection{V, x.n_joints, x.joint_flags, x.joint_mask, x.threshold, b.d_frame_head_off, b.d_joint_mask, b.d_vp, x.d_persons,
+                        x.d_n_persons, x.d_flags},
+              b.d_xy, x.d_poses, x.d_res};
     const long long groups = (long long)x.n_frames * x.pcap * V;
     const long long blocks = (groups + RP_GROUPS - 1) / RP_GROUPS;
     hipLaunchKernelGGL(k_reproject, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(32 * RP_GROUPS), 0, s, cfg, a);

@@ -65,6 +65,11 @@ def build_parser(description):
                         '--testfiles together are one sequence, in the order given: pass one recording per run')
     p.add_argument('--track-gate', type=float, default=0.5, metavar='M', help='--track: largest mean joint distance of a link, metres')
     p.add_argument('--track-gap', type=int, default=2, metavar='N', help='--track: frames a person may go undetected and keep the identity')
+    p.add_argument('--refine', type=int, default=0, metavar='ITERS',
+                   help='implies --device-metrics; every joint is moved to the minimum of its reprojection error over the cameras that saw it '
+                        '(mpe_refine_batch: at most ITERS Levenberg-Marquardt iterations per joint, 1..64) and the refined poses are scored; '
+                        'one further line reports the solved joints, the share that moved and the mean cost before and after')
+    p.add_argument('--refine-huber', type=float, default=0.0, metavar='PX', help='--refine: Huber threshold in pixels (0: plain least squares)')
     return p
 
 
@@ -465,7 +470,8 @@ def max_skeletons_per_camera(work):
 def run(args, mode):
     calib = Calibration(parameters)
     device_gt = getattr(args, 'device_gt', False) and not args.synthetic       # synthetic frames have no file to parse
-    if getattr(args, 'device_gt', False) or getattr(args, 'track', False):
+    refine = int(getattr(args, 'refine', 0) or 0)
+    if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
         args.device_metrics = True
     src = [] if device_gt else None
     work = collect_work(args, calib, src)
@@ -479,6 +485,7 @@ def run(args, mode):
     J = eng.J
     t = {'match': 0.0, '3d': 0.0}
     tracker = summary = None
+    refined = []
     if getattr(args, 'track', False):
         from .tracking import TrackSummary
         tracker, summary = eng.tracker(mode, max_gap=args.track_gap, gate=args.track_gate), TrackSummary()
@@ -533,6 +540,10 @@ def run(args, mode):
             poses, flags = eng.mlp3d(db, persons, n_persons)
         else:
             poses, flags = eng.triangulate(db, persons, n_persons)
+        if refine:
+            ref = eng.refine(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', max_iters=refine,
+                             huber_px=args.refine_huber, out=poses)
+            refined.append({k: ref[k].cpu().numpy() for k in ('status', 'cost0', 'cost1')})
         torch.cuda.synchronize()
         t2 = time.time()
         ev = eng.evaluate(db, poses, flags, n_persons, gt, mode)
@@ -571,6 +582,11 @@ def run(args, mode):
         print('Frames per second', n_data / max(1e-9, t['match'] + t['3d']))
         if 'eval' in t:
             print('Mean time for evaluation on the device', t['eval'] / n_data)
+    if refine:
+        from .refine import summary as refine_summary
+        out['refine'] = r = refine_summary(refined)
+        print('Refined (at most %d iterations, Huber %g px): %d joints solved, %.1f %% moved, mean cost %.6g -> %.6g px^2'
+              % (refine, args.refine_huber, r['solved'], 100.0 * r['moved_share'], r['mean_cost0'], r['mean_cost1']))
     if tracker is not None:
         out['tracks'] = summary.result()
         print('Tracks (gate %g m, gap %d): %d, mean length %.3f frames, %d born after the first frame'

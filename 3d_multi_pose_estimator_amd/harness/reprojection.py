@@ -82,16 +82,14 @@ def pixel_distance(px, py, x, y):
         return dx * dx + dy * dy, np.sqrt(dx * dx + dy * dy)
 
 
-def residuals(calib, pb, persons, n_persons, poses, flags, joint_mask, threshold=0.5, squared=False):
-    """pb: the packed batch (host arrays); persons [F,Pcap,V] / n_persons [F] as the matching stage wrote them; poses
-    [F,Pcap,J,3] float32 or float64 (rounded to float32 first, :405); flags [F,Pcap] (per person) or [F,Pcap,J] (per
-    joint); joint_mask: bit j selects joint j.  -> res [F,Pcap,V,J] float64 (squared=True: the squared distances)."""
+def selection(pb, persons, n_persons, flags, joint_mask, threshold=0.5):
+    """The module docstring's selection -> (sel [F,Pcap,V,J] bool, xy [F,Pcap,V,J,2] float64: the detection each counted
+    entry is compared with; unspecified where sel is False).  harness/refine.py takes its observing cameras from here."""
     persons = np.asarray(persons)
     F, Pcap, V = persons.shape
     J = pb.J
-    if F == 0:
-        return np.zeros((0, Pcap, V, J), np.float64)
-    poses = np.asarray(poses).astype(np.float32)
+    if F == 0 or pb.n_heads == 0:
+        return np.zeros((F, Pcap, V, J), bool), np.zeros((F, Pcap, V, J, 2), np.float64)
     flags = np.asarray(flags) != 0
     n_persons = np.asarray(n_persons).astype(np.int64)
     off = np.asarray(pb.frame_head_off).astype(np.int64)
@@ -99,14 +97,26 @@ def residuals(calib, pb, persons, n_persons, poses, flags, joint_mask, threshold
     ok = (np.arange(Pcap)[None, :, None] < n_persons[:, None, None]) & (persons >= 0) & (persons < n_heads)
     head = np.where(ok, off[:F, None, None] + persons, 0)
     j = np.arange(J)
-    if pb.n_heads == 0:
-        return np.full((F, Pcap, V, J), SENTINEL)
     in_dict = ((np.asarray(pb.joint_mask)[head][..., None] >> j.astype(np.uint32)) & 1) != 0
     xy = np.asarray(pb.xy, np.float64).reshape(-1, J, 2)[head]                # [F,Pcap,V,J,2]
     valid = np.asarray(pb.vp, np.float32).reshape(-1, J, 2)[head][..., 0]
     picked = ((int(joint_mask) >> j) & 1) != 0
     flag = flags[:, :, None, :] if flags.ndim == 3 else flags[:, :, None, None]
-    sel = ok[..., None] & in_dict & picked & flag & (valid > np.float32(threshold))
+    return ok[..., None] & in_dict & picked & flag & (valid > np.float32(threshold)), xy
+
+
+def residuals(calib, pb, persons, n_persons, poses, flags, joint_mask, threshold=0.5, squared=False):
+    """pb: the packed batch (host arrays); persons [F,Pcap,V] / n_persons [F] as the matching stage wrote them; poses
+    [F,Pcap,J,3] float32 or float64 (rounded to float32 first, :405); flags [F,Pcap] (per person) or [F,Pcap,J] (per
+    joint); joint_mask: bit j selects joint j.  -> res [F,Pcap,V,J] float64 (squared=True: the squared distances)."""
+    F, Pcap, V = np.asarray(persons).shape
+    J = pb.J
+    if F == 0:
+        return np.zeros((0, Pcap, V, J), np.float64)
+    if pb.n_heads == 0:
+        return np.full((F, Pcap, V, J), SENTINEL)
+    poses = np.asarray(poses).astype(np.float32)
+    sel, xy = selection(pb, persons, n_persons, flags, joint_mask, threshold)
     T, kd, K = camera_constants(calib)
     px, py = project(T[None, None, :, None], kd[None, None, :, None], K[None, None, :, None],
                      poses[:, :, None, :, 0], poses[:, :, None, :, 1], poses[:, :, None, :, 2])

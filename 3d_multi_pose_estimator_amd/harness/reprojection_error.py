@@ -99,6 +99,7 @@ def collect_work_showgt(args, calib):
 
 
 KINDS = ('est', 'GT', 'triang')               # the order the script prints its rows in (:426-430)
+REFINED = ('est+refine', 'triang+refine')     # --refine: the rows of the refined poses, after the script's own
 
 
 def report(stats_of_kind):
@@ -108,7 +109,7 @@ def report(stats_of_kind):
     out = {}
     for c, cam in enumerate(names):
         print('------------------', 'CAMERA', cam, '------------------')
-        for kind in KINDS:
+        for kind in KINDS + REFINED:
             st = stats_of_kind.get(kind)
             if st is not None and st['count'][c] > 0:
                 print(kind, st['mean'][c], st['median'][c])
@@ -174,10 +175,12 @@ def device_gt_poses(eng, poses, valid, n_persons, gt):
     return gp, ok.to(torch.uint8).contiguous()
 
 
-def evaluate_on_device(work, eng, infer_device, calib, showgt=False, batch=256):
+def evaluate_on_device(work, eng, infer_device, calib, showgt=False, batch=256, refine=0, huber_px=0.0):
     """--device-metrics: `infer_device(frames, owners)` -> (db, persons, n_persons, poses, valid, tri, jv) on the device;
     the residuals of every batch stay there (8 bytes x B x Pcap x V x J each) and the statistics come from one call at
-    the end."""
+    the end.  refine > 0 (--refine): both pose sets also go through Engine.refine (at most `refine` iterations) and are
+    projected again -- two more rows per camera, and the dictionary gains 'squared_sum': per kind the sum over all
+    counted entries of the squared residual, the quantity the refinement minimises."""
     T_i1 = torch.from_numpy(calib.T_i32[1])
     res = {'est': [], 'triang': []}
     if showgt:
@@ -191,11 +194,18 @@ def evaluate_on_device(work, eng, infer_device, calib, showgt=False, batch=256):
             gt = pack_ground_truth([w[0] for w in chunk], [w[2] for w in chunk], T_i1)
             gp, ok = device_gt_poses(eng, poses, valid, n_persons, gt)
             res['GT'].append(eng.reproject(db, persons, n_persons, gp, ok, 'gt'))
+        if refine:
+            for kind, p, f in (('est', poses, valid), ('triang', tri, jv)):
+                better = eng.refine(db, persons, n_persons, p, f, kind, max_iters=refine, huber_px=huber_px)['poses']
+                res.setdefault(kind + '+refine', []).append(eng.reproject(db, persons, n_persons, better, f, kind))
         eng.sync_status()
     if not work:
         empty = torch.zeros((0, eng.pcap, eng.V, eng.J), dtype=torch.float64, device=eng.device)
         res = {k: [empty] for k in res}
-    return report({k: eng.residual_stats(v) for k, v in res.items()})
+    out = report({k: eng.residual_stats(v) for k, v in res.items()})
+    if refine:
+        out['squared_sum'] = {k: float(sum((r.clamp(min=0.0) ** 2).sum() for r in v)) for k, v in res.items()}
+    return out
 
 
 def evaluate(work, infer, calib, batch=256):
@@ -282,8 +292,9 @@ def run(args):
         keys = ('persons', 'n_persons', 'poses', 'valid', 'tri', 'jv')
         return dict({k: v.cpu().numpy() for k, v in zip(keys, dev)}, pb=db.host)
 
-    if getattr(args, 'device_metrics', False):
-        out = evaluate_on_device(work, eng, infer_device, calib, showgt, args.batch)
+    if getattr(args, 'device_metrics', False) or getattr(args, 'refine', 0):
+        out = evaluate_on_device(work, eng, infer_device, calib, showgt, args.batch, int(getattr(args, 'refine', 0) or 0),
+                                 float(getattr(args, 'refine_huber', 0.0)))
     elif showgt:
         out = evaluate_arrays(work, infer_arrays, calib, True, args.batch)
     else:

@@ -97,6 +97,15 @@ class mpe_reproject_args(C.Structure):
                 ('d_res', C.c_void_p)]
 
 
+class mpe_refine_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float), ('max_iters', C.c_int32),
+                ('step_tol', C.c_double), ('huber_px', C.c_double),
+                ('d_persons', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_poses', C.c_void_p), ('d_flags', C.c_void_p),
+                ('d_poses_out', C.c_void_p), ('d_status', C.c_void_p), ('d_cost0', C.c_void_p), ('d_cost1', C.c_void_p),
+                ('d_iters', C.c_void_p), ('d_n_views', C.c_void_p)]
+
+
 class mpe_residual_stats_args(C.Structure):
     _fields_ = [('n_buffers', C.c_int32), ('n_joints', C.c_int32), ('d_res', C.POINTER(C.c_void_p)), ('n_groups', C.POINTER(C.c_int64)),
                 ('d_count', C.c_void_p), ('d_nonfinite', C.c_void_p), ('d_sum', C.c_void_p), ('d_mid', C.c_void_p)]
@@ -142,6 +151,10 @@ MPE_PART_MAX_SAMPLES, MPE_PART_MAX_SKELETONS, MPE_PART_MAX_KEYS = 256, 1024, 32
 
 # compiled caps of mpe_track_create
 MPE_TRACK_MAX_PERSONS, MPE_TRACK_MAX_GAP = 128, 15
+
+# per-joint status bits and the iteration cap of mpe_refine_batch
+MPE_REFINE_SOLVED, MPE_REFINE_MOVED, MPE_REFINE_CONVERGED, MPE_REFINE_FEW_VIEWS, MPE_REFINE_BAD_START = 1, 2, 4, 8, 16
+MPE_REFINE_MAX_ITERS = 64
 
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
@@ -195,6 +208,7 @@ SYMBOLS = {
     'mpe_track_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_track_args)]),
     'mpe_track_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
+    'mpe_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_args)]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),
     'mpe_partition_labels': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_partition_labels_args)]),
     'mpe_group_bodies': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_group_bodies_args)]),

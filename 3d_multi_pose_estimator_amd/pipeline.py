@@ -1018,15 +1018,11 @@ class Engine:
         are not this engine's (default: the engine's Pcap)."""
         return Tracker(self, mode, max_gap, gate, self.pcap if pcap is None else int(pcap))
 
-    def reproject(self, db, persons, n_persons, poses, flags, kind, joint_mask=None, threshold=0.5):
-        """Reprojection residuals on the device (mpe_reproject_batch): how far every joint of every 3D pose lands from
-        the 2D detection it came from, per camera -- a quality signal that needs no ground truth.  kind 'est': what mlp3d
-        returned (f32 poses, person flags; the used joints); 'triang': what triangulate returned (f64 poses, joint flags;
-        all joints); 'gt': f32 poses with person flags and the script's one GT joint (the last of joint_list).
-        joint_mask overrides the kind's joints.  -> res [B,Pcap,V,J] f64 pixels, -1 where nothing is counted."""
+    def _pose_args(self, db, persons, n_persons, poses, flags, kind, joint_mask, kinds):
+        """The argument checks reproject and refine share -> (B, tri, joint_mask)."""
         B = db.n_frames
-        if kind not in ('est', 'triang', 'gt'):
-            raise ValueError('kind must be est, triang or gt')
+        if kind not in kinds:
+            raise ValueError('kind must be ' + ' or '.join((', '.join(kinds[:-1]), kinds[-1])))
         tri = kind == 'triang'
         want = torch.float64 if tri else torch.float32
         if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, self.J, 3):
@@ -1042,6 +1038,15 @@ class Engine:
         if joint_mask is None:
             joint_mask = {'est': sum(1 << j for j in self.params.used_joints), 'triang': (1 << self.J) - 1,
                           'gt': 1 << int(list(self.params.joint_list)[-1])}[kind]
+        return B, tri, int(joint_mask)
+
+    def reproject(self, db, persons, n_persons, poses, flags, kind, joint_mask=None, threshold=0.5):
+        """Reprojection residuals on the device (mpe_reproject_batch): how far every joint of every 3D pose lands from
+        the 2D detection it came from, per camera -- a quality signal that needs no ground truth.  kind 'est': what mlp3d
+        returned (f32 poses, person flags; the used joints); 'triang': what triangulate returned (f64 poses, joint flags;
+        all joints); 'gt': f32 poses with person flags and the script's one GT joint (the last of joint_list).
+        joint_mask overrides the kind's joints.  -> res [B,Pcap,V,J] f64 pixels, -1 where nothing is counted."""
+        B, tri, joint_mask = self._pose_args(db, persons, n_persons, poses, flags, kind, joint_mask, ('est', 'triang', 'gt'))
         res = torch.empty((B, self.pcap, self.V, self.J), dtype=torch.float64, device=self.device)
         a = L.mpe_reproject_args()
         a.n_frames, a.pcap, a.n_joints = B, self.pcap, self.J
@@ -1049,6 +1054,38 @@ class Engine:
         a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
         a.d_res = res.data_ptr()
         self._chk(self.lib.mpe_reproject_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return res
+
+    def refine(self, db, persons, n_persons, poses, flags, kind, joint_mask=None, threshold=0.5, max_iters=10, step_tol=1e-6,
+               huber_px=0.0, out=None):
+        """Every joint moved to the minimum of its reprojection cost over the cameras that saw it (mpe_refine_batch: one
+        Levenberg-Marquardt problem of three unknowns per joint, binary64; include/mpe.h has the rule, harness/refine.py
+        states it in numpy and the two agree bit for bit).  kind 'est': what mlp3d returned (f32 poses, person flags; the
+        used joints); 'triang': what triangulate returned (f64 poses, joint flags; all joints); the observing cameras of
+        a joint are the entries reproject would count.  huber_px > 0 bounds the pull of an outlying detection; out: the
+        tensor that takes the poses (`poses` itself refines in place).  -> dict of device tensors: poses [B,Pcap,J,3] in
+        the type of the input (joints that are not solved are copied through), status u8 (MPE_REFINE_* bits), cost0 /
+        cost1 f64 (-1 where not solved), iters u8, n_views u8, all [B,Pcap,J]; one launch on the current stream.  The
+        poses feed evaluate, reproject and Tracker.update like the ones that went in."""
+        B, tri, joint_mask = self._pose_args(db, persons, n_persons, poses, flags, kind, joint_mask, ('est', 'triang'))
+        if out is None:
+            out = torch.empty_like(poses)
+        elif out.dtype != poses.dtype or tuple(out.shape) != tuple(poses.shape) or not out.is_contiguous() or out.device != poses.device:
+            raise ValueError('out must be a contiguous tensor of the type, shape and device of poses')
+        shape = (B, self.pcap, self.J)
+        res = {'poses': out, 'status': torch.empty(shape, dtype=torch.uint8, device=self.device),
+               'cost0': torch.empty(shape, dtype=torch.float64, device=self.device),
+               'cost1': torch.empty(shape, dtype=torch.float64, device=self.device),
+               'iters': torch.empty(shape, dtype=torch.uint8, device=self.device),
+               'n_views': torch.empty(shape, dtype=torch.uint8, device=self.device)}
+        a = L.mpe_refine_args()
+        a.n_frames, a.pcap, a.n_joints = B, self.pcap, self.J
+        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
+        a.max_iters, a.step_tol, a.huber_px = int(max_iters), float(step_tol), float(huber_px)
+        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
+        a.d_poses_out, a.d_status, a.d_cost0, a.d_cost1 = out.data_ptr(), res['status'].data_ptr(), res['cost0'].data_ptr(), res['cost1'].data_ptr()
+        a.d_iters, a.d_n_views = res['iters'].data_ptr(), res['n_views'].data_ptr()
+        self._chk(self.lib.mpe_refine_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
         return res
 
     def residual_stats(self, res_list):

@@ -318,6 +318,80 @@ typedef struct {
 } mpe_residual_stats_args;
 int mpe_residual_stats(mpe_ctx *ctx, void *stream, const mpe_residual_stats_args *a);
 
+/* Refinement: every joint of every pose moved to the point that minimises its reprojection error over all cameras that saw
+ * it (the non-linear "optimal triangulation" step; the DLT stage is a median of two-view solutions, the MLP never looks at
+ * the pixels again).  One 3-unknown Levenberg-Marquardt problem per (frame, person, joint), all binary64, every operation
+ * named below rounded on its own (nothing fused), quotients and roots correctly rounded.  harness/refine.py states the same
+ * in numpy, and the two agree bit for bit.
+ * Observations.  Camera c observes joint j of person p of frame f exactly when mpe_reproject_batch, given the same
+ *   d_persons / d_n_persons / d_poses / d_flags / pose_f64 / joint_flags / joint_mask / threshold, would count
+ *   d_res[f][p][c][j] (the rule above).  n_views = the number of such cameras; x, y = that detection (d_xy, f64).
+ * Projection of X = (X0, X1, X2) into camera c, with T = cfg.P[c] as stored, kd0, kd1, kd2 = cfg.dist[c][0], [1], [4] and
+ *   K = (double) cfg.K[c] (all three rows as stored):
+ *   pc_i = ((T[i][0]*X0 + T[i][1]*X1) + T[i][2]*X2) + T[i][3]             i = 0..2
+ *   h0 = pc_0 / pc_2 ; h1 = pc_1 / pc_2 ; r = h0*h0 + h1*h1
+ *   f  = ((1 + kd0*r) + (kd1*r)*r) + ((kd2*r)*r)*r ; d0 = h0*f ; d1 = h1*f
+ *   u_i = (K[i][0]*d0 + K[i][1]*d1) + K[i][2] ; px = u_0 / u_2 ; py = u_1 / u_2
+ *   rx = px - x ; ry = py - y ; e = sqrt(rx*rx + ry*ry)
+ * Jacobian of (px, py) by X_k, k = 0..2 (the derivative of exactly the lines above):
+ *   fd = (kd0 + (2*kd1)*r) + ((3*kd2)*r)*r
+ *   a_k = (T[0][k] - h0*T[2][k]) / pc_2 ; b_k = (T[1][k] - h1*T[2][k]) / pc_2
+ *   q_k = fd * (2 * (h0*a_k + h1*b_k)) ; m_k = a_k*f + h0*q_k ; n_k = b_k*f + h1*q_k
+ *   v_ik = K[i][0]*m_k + K[i][1]*n_k                                      i = 0..2
+ *   jx_k = (v_0k - px*v_2k) / u_2 ; jy_k = (v_1k - py*v_2k) / u_2
+ * Cost.  C(X) = the left-fold sum, over the observing cameras in increasing c from 0.0, of rho(e_c):
+ *   rho(e) = e*e when huber_px <= 0 or e <= huber_px, else (2*huber_px)*e - huber_px*huber_px;
+ *   the weight w_c is 1 in the first case and huber_px / e in the second.  huber_px = 0 is plain least squares.
+ * Iteration.  X = the input joint widened to f64, lambda = 1e-3, C = C(X).  At most max_iters times:
+ *   A_kl (k <= l) and g_k start at 0.0 and take, per observing camera in increasing c,
+ *     A_kl = A_kl + w_c * (jx_k*jx_l + jy_k*jy_l) ; g_k = g_k + w_c * (jx_k*rx + jy_k*ry)
+ *   M_kk = A_kk + lambda*A_kk, M_kl = A_kl; (A + lambda diag A) delta = -g by LDL^T:
+ *     D0 = M_00 ; L10 = M_01 / D0 ; L20 = M_02 / D0 ; D1 = M_11 - L10*M_01 ; t = M_12 - L20*M_01 ; L21 = t / D1
+ *     D2 = (M_22 - L20*M_02) - L21*t
+ *     z0 = -g_0 ; z1 = -g_1 - L10*z0 ; z2 = (-g_2 - L20*z0) - L21*z1
+ *     delta_2 = z2 / D2 ; delta_1 = z1 / D1 - L21*delta_2 ; delta_0 = (z0 / D0 - L10*delta_1) - L20*delta_2
+ *   A pivot D0, D1 or D2 that is not > 0, or a delta that is not finite, rejects the iteration.  Otherwise the trial point
+ *   is X + delta; it is accepted only if pc_2 > 0 there in every observing camera and C(trial) < C (strict; a NaN rejects).
+ *   Accepted: X = trial, C = C(trial), lambda = max(lambda / 10, 1e-12), and the loop ends when max |delta_k| < step_tol
+ *   (metres; step_tol = 0 runs every iteration).  Rejected: lambda = lambda * 10.
+ * The result is X in the type of d_poses (f32: rounded once); a joint that never moved keeps its input bits.
+ * Not solved -- the joint is copied through bit for bit, d_cost0 = d_cost1 = -1, d_iters = 0: no observing camera (status
+ *   0); one observing camera (MPE_REFINE_FEW_VIEWS); a start that is not finite, or that has pc_2 <= 0 (or NaN) in an
+ *   observing camera (MPE_REFINE_BAD_START).
+ * Outputs per [n_frames][pcap][J]: d_status (bits below; MPE_REFINE_MOVED: at least one accepted step; _CONVERGED: ended
+ *   by step_tol), d_cost0 / d_cost1 (C at the start and at the result, on the f64 point; d_cost1 <= d_cost0 and, without
+ *   _MOVED, equal), d_iters (iterations run, rejected ones included), d_n_views.  d_poses_out may be d_poses itself.
+ * One launch, ordered on `stream`; neither synchronises nor allocates; n_frames == 0 does nothing.  MPE_ERR_INVALID for
+ * max_iters outside 1..64, a negative (or NaN) step_tol or huber_px, n_frames other than the batch's or n_joints other
+ * than the context's. */
+enum {
+    MPE_REFINE_SOLVED = 1,
+    MPE_REFINE_MOVED = 2,
+    MPE_REFINE_CONVERGED = 4,
+    MPE_REFINE_FEW_VIEWS = 8,
+    MPE_REFINE_BAD_START = 16
+};
+#define MPE_REFINE_MAX_ITERS 64
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t joint_mask;           /* bit j: joint j is refined                                      */
+    float threshold;               /* 0.5, as for mpe_reproject_batch                                */
+    int32_t max_iters;             /* 1 .. MPE_REFINE_MAX_ITERS                                      */
+    double step_tol;               /* metres, >= 0                                                   */
+    double huber_px;               /* pixels, >= 0; 0: plain least squares                           */
+    const int32_t *d_persons;      /* [n_frames][pcap][V]                                            */
+    const int32_t *d_n_persons;    /* [n_frames]                                                     */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    void *d_poses_out;             /* [n_frames][pcap][J][3], the type of d_poses                    */
+    uint8_t *d_status;             /* [n_frames][pcap][J]                                            */
+    double *d_cost0, *d_cost1;     /* [n_frames][pcap][J]                                            */
+    uint8_t *d_iters, *d_n_views;  /* [n_frames][pcap][J]                                            */
+} mpe_refine_args;
+int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_refine_args *a);
+
 /* Clustering quality of the matching stage (test/sm_metrics.py:125-229, test/sm_metrics_without_gt.py:131-170): labels
  * from proposals, the ground-truth grouping of a frame's bodies_3D, and the four scores of two labelings.
  * harness/partition.py states all three on the host; host and device agree bit for bit.  Per-frame status words: */

@@ -47,14 +47,16 @@ struct DeviceGuard {
     }
 };
 
-void dev_free(mpe_ctx *ctx, void *p) {
-    if (!p) return;
+// frees p if the context owns it; says whether it did
+bool dev_free(mpe_ctx *ctx, void *p) {
+    if (!p) return false;
     for (size_t i = 0; i < ctx->owned.size(); ++i)
         if (ctx->owned[i] == p) {
             (void)hipFree(p);
             ctx->owned.erase(ctx->owned.begin() + i);
-            return;
+            return true;
         }
+    return false;
 }
 
 template <typename T>
@@ -142,84 +144,129 @@ struct GemmProf {
     }
 };
 
-int linear(mpe_ctx *ctx, hipStream_t s, const float *A, int lda, const Linear &L, float *C, int ldc, int m,
-           const int32_t *d_m, bool leaky, float slope, bool acc64 = false, const int32_t *a_rows = nullptr,
-           const int32_t *c_rows = nullptr, double flop_override = -1.0, const AttnCoef *coef = nullptr,
-           bool *coef_done = nullptr, bool out_half = false) {
-    if (coef_done) *coef_done = false;
-    if (m <= 0) return MPE_OK;
-    if (lda < L.ldw) return fail(ctx, MPE_ERR_INVALID, "activation stride %d < padded K %d", lda, L.ldw);
-    const bool host_m = !d_m || flop_override >= 0.0;
-    GemmProf gp(ctx, s, flop_override >= 0.0 ? flop_override : (d_m ? 0.0 : 2.0 * m * (double)L.out_dim * L.in_dim),
-                host_m ? 0 : L.out_dim, host_m ? 0 : L.in_dim);
-    HIPCHK(ctx, launch_linear(s, A, lda, L.w, L.ldw, L.b, C, ldc, m, d_m, L.out_dim, L.ldw, leaky, slope, acc64, a_rows,
-                              c_rows, coef, coef_done, out_half));
-    return MPE_OK;
-}
-
 // MPE_LATENCY_PATH=0: small batches through the batch path's own small-batch kernels (read per call: tests toggle it)
 bool latency_path_on() {
     const char *e = getenv("MPE_LATENCY_PATH");
     return !(e && e[0] == '0');
 }
 
-unsigned short f32_to_bf16(float f);
-int ensure_bf16_weights(mpe_ctx *ctx, Linear *L);
-int ensure_split_weights(mpe_ctx *ctx, hipStream_t s, Linear *L);
+unsigned short f32_to_bf16(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (unsigned short)((u >> 16) | 0x40);   // NaN stays NaN
+    u += 0x7FFFu + ((u >> 16) & 1u);          // round to nearest even
+    return (unsigned short)(u >> 16);
+}
 
-// GEMM of a GAT layer: fp32 MFMA (parity) or, in the reduced-precision mode, bf16 MFMA with an
-// optional fp16 result (`out_half`: C is the same buffer seen as fp16 rows, ldc in halves)
+int ensure_bf16_weights(mpe_ctx *ctx, Linear *L) {
+    if (L->w16) return MPE_OK;
+    const int rows = weight_rows(L->out_dim);
+    L->ldw16 = round_up(L->in_dim, 128);
+    std::vector<float> w((size_t)rows * L->ldw);
+    HIPCHK(ctx, hipMemcpy(w.data(), L->w, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<unsigned short> wb((size_t)rows * L->ldw16, 0);
+    for (int r = 0; r < rows; ++r)
+        for (int k = 0; k < L->in_dim; ++k) wb[(size_t)r * L->ldw16 + k] = f32_to_bf16(w[(size_t)r * L->ldw + k]);
+    int rc = dev_alloc(ctx, &L->w16, wb.size(), false);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(L->w16, wb.data(), wb.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+    return MPE_OK;
+}
+
+// the three bf16 planes of a weight matrix (split on the device from the padded fp32 copy, stream-ordered)
+int ensure_split_weights(mpe_ctx *ctx, hipStream_t s, Linear *L) {
+    if (L->w3) return MPE_OK;
+    const size_t count = plane_elems(*L);
+    int rc = dev_alloc(ctx, &L->w3, 3 * count, false);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_split_planes(s, L->w, count, L->w3));
+    return MPE_OK;
+}
+
+// One nn.Linear launch, whatever its form: act(A W^T + b) -> C
+struct GemmCall {
+    const float *A;
+    int lda;
+    float *C;
+    int ldc;
+    int m;
+    const int32_t *d_m;                    // optional device-side row count (<= m)
+    bool leaky;
+    float slope;
+    const int32_t *a_rows = nullptr, *c_rows = nullptr;      // gathered rows (fp32 MFMA and plain bf16 forms)
+    double flop_override = -1.0;           // >= 0: the profile record's FLOP, for a launch whose row count the host knows better
+    const AttnCoef *coef = nullptr;        // fc2 of a GAT layer: a1 | a2 from the epilogue where the launch has one (*coef_done)
+    bool *coef_done = nullptr;
+    bool out_half = false;                 // C is the same buffer seen as fp16 rows, ldc in halves
+    int flush_stages = 2;                  // SB16_F64: K stages per f64 flush
+    const DecodeEpi *dec = nullptr;        // SB16_F64: the decoded poses from the epilogue where the launch has one (*dec_done)
+    bool *dec_done = nullptr;
+    int bf16_min_ld = 0;                   // BF16: the launch reads this many columns of a row (whole 128-deep stages); 0 = L.ldw, as every other form
+};
+
+// The one place an nn.Linear is launched from (which form: gemm_form.h).  The order matters: nothing is made for an empty launch.
+int gemm(mpe_ctx *ctx, hipStream_t s, GemmForm form, Linear &L, const GemmCall &c) {
+    if (c.coef_done) *c.coef_done = false;
+    if (c.dec_done) *c.dec_done = false;
+    if (c.m <= 0) return MPE_OK;
+    const bool sb16 = form == GemmForm::SB16 || form == GemmForm::SB16_F64, bf16 = form == GemmForm::BF16;
+    int rc;
+    if (sb16 && (rc = ensure_split_weights(ctx, s, &L))) return rc;
+    if (bf16 && (rc = ensure_bf16_weights(ctx, &L))) return rc;
+    // Every form reads L.ldw columns of an activation row.  The plain bf16 kernel works in 128-deep stages and zero-fills what lies
+    // beyond the columns it is told to read: the MLP's strides are multiples of 128 and its launches read whole stages (L.ldw16),
+    // the GAT's act_ld is a multiple of 32, not of 128, so its launches stop at L.ldw.
+    const bool whole_stages = bf16 && c.bf16_min_ld;
+    if (whole_stages && c.lda < c.bf16_min_ld) return fail(ctx, MPE_ERR_INVALID, "bf16 GEMM needs an input stride >= %d", c.bf16_min_ld);
+    if (!whole_stages && c.lda < L.ldw) return fail(ctx, MPE_ERR_INVALID, "activation stride %d < padded K %d", c.lda, L.ldw);
+    // the profile record: FLOP known on the host, or 2 * (device-side row count) * dev_n * dev_k
+    const bool host_m = !c.d_m || c.flop_override >= 0.0;
+    const double flop = c.flop_override >= 0.0 ? c.flop_override : c.d_m ? 0.0 : 2.0 * c.m * (double)L.out_dim * L.in_dim;
+    const int kind = sb16 ? 1 : bf16 ? 2 : form == GemmForm::F64MM ? 3 : 0;
+    GemmProf gp(ctx, s, flop, host_m ? 0 : L.out_dim, host_m ? 0 : L.in_dim, kind);
+    switch (form) {
+    case GemmForm::F32:
+    case GemmForm::F32_ACC64:
+        HIPCHK(ctx, launch_linear(s, c.A, c.lda, L.w, L.ldw, L.b, c.C, c.ldc, c.m, c.d_m, L.out_dim, L.ldw, c.leaky, c.slope,
+                                  form == GemmForm::F32_ACC64, c.a_rows, c.c_rows, c.coef, c.coef_done, c.out_half));
+        break;
+    case GemmForm::SB16:
+    case GemmForm::SB16_F64: {
+        const bool f64 = form == GemmForm::SB16_F64;           // (the f64-sum kernels have no coefficient epilogue)
+        HIPCHK(ctx, launch_linear_sb16(s, c.A, c.lda, L.w3, plane_elems(L), L.ldw, L.b, c.C, c.ldc, c.m, c.d_m, L.out_dim, L.ldw, c.leaky, c.slope,
+                                       f64, f64 ? nullptr : c.coef, c.coef_done, c.out_half, c.flush_stages, c.dec, c.dec_done));
+        break;
+    }
+    case GemmForm::BF16:
+        HIPCHK(ctx, launch_linear_bf16(s, c.A, c.lda, L.w16, L.ldw16, L.b, c.C, c.ldc, c.m, c.d_m, L.out_dim, L.ldw16, c.leaky, c.slope,
+                                       whole_stages ? c.bf16_min_ld : L.ldw, c.out_half, c.a_rows, c.c_rows));
+        break;
+    case GemmForm::F64MM:
+        HIPCHK(ctx, launch_linear_f64(s, c.A, c.lda, L.w, L.ldw, L.b, c.C, c.ldc, c.m, c.d_m, L.out_dim, L.ldw, c.leaky, c.slope));
+        break;
+    }
+    return MPE_OK;
+}
+
+// GEMM of a GAT layer, in the form the precision mode and the launch's shape select (gemm_form.h: gat_gemm_form)
 int gat_linear(mpe_ctx *ctx, hipStream_t s, const float *A, int lda, Linear &L, float *C, int ldc, int m,
                const int32_t *d_m, bool leaky, float slope, bool out_half, const int32_t *a_rows = nullptr,
                const int32_t *c_rows = nullptr, double flop_override = -1.0, const AttnCoef *coef = nullptr,
                bool *coef_done = nullptr) {
-    if (coef_done) *coef_done = false;
     static const int mink = getenv("MPE_GAT_ACC64_MINK") ? atoi(getenv("MPE_GAT_ACC64_MINK")) : 512;
-    const bool sb_f64 = ctx->gat_acc64 || (mink > 0 && L.in_dim > mink);
-    // (fp16 result rows exist in the split TILE kernel only: the fc2 launches at batch sizes the tile kernel takes, without f64
-    // sums; every other launch of the fp16-attention mode stays on the fp32 MFMA, whose tile and wave-per-tile kernels all store
-    // fp16 rows)
-    const bool sb_half_ok = !out_half || (!leaky && !sb_f64 && linear_sb16_uses_tile_kernel(m, L.out_dim, false));
-    // (launches with gathered rows -- layer-0 fc1 per camera -- stay on the fp32 MFMA; the grouped layer-0 launch does not come here)
-    // In the explicit f64-sum mode (mpe_set_precision GAT 1 on top of the split form) layer 0's fc2 keeps the fp32 MFMA with a
-    // flush per 32-deep stage: the split form flushes every second stage, and on the K = 902 sum of the steep layer-0 features
-    // that cadence left one 5x4 fixture frame 1.46x the reference's own distance from the f64 network where the mode promises
-    // <= 1 (tests/test_gpu_stages.py::test_score_noise_against_the_f64_network; 0.79 with the flush per stage).
-    const bool l0_fc2_f64_mode = ctx->gat_acc64 && &L == &ctx->gat[0].fc2;
-    if (ctx->gat_split && !ctx->gat_reduced && sb_half_ok && !a_rows && !c_rows && L.w != ctx->l0_w && !l0_fc2_f64_mode) {
-        // split-bf16 form (gemm_sb16.hip): fp32-accurate products on the bf16 matrix pipe; f64 sums where the fp32 path has them
-        const bool f64 = sb_f64;
-        if (m <= 0) return MPE_OK;
-        int rc = ensure_split_weights(ctx, s, &L);
-        if (rc) return rc;
-        if (lda < L.ldw) return fail(ctx, MPE_ERR_INVALID, "activation stride %d < padded K %d", lda, L.ldw);
-        const bool host_m = !d_m || flop_override >= 0.0;
-        GemmProf gp(ctx, s, flop_override >= 0.0 ? flop_override : (d_m ? 0.0 : 2.0 * m * (double)L.out_dim * L.in_dim),
-                    host_m ? 0 : L.out_dim, host_m ? 0 : L.in_dim, 1);
-        HIPCHK(ctx, launch_linear_sb16(s, A, lda, L.w3, (size_t)weight_rows(L.out_dim) * L.ldw, L.ldw, L.b, C, ldc, m, d_m, L.out_dim, L.ldw,
-                                       leaky, slope, f64, f64 ? nullptr : coef, coef_done, out_half));
-        return MPE_OK;
-    }
-    if (!ctx->gat_reduced) {
-        // Long sums (K > 512: fc2 of layer 0, K = 902 / 1082, on head rows only -- no measurable cost) always
-        // run with f64 running sums: a single fp32 chain of that length was the largest contribution to the
-        // score noise (ARPLAB frames of random shape: 3.2e-5 from the reference with it, 2.3e-5 without, where
-        // the reference's own fp32 scores sit 1.8e-5 from the float64 network).  MPE_GAT_ACC64_MINK overrides
-        // the threshold (0 = never), mpe_set_precision(ctx, 1, .) extends it to every GAT GEMM.
-        const bool acc64 = sb_f64;
-        // out_half here = the fp16-attention mode (fp32 MFMA GEMM, result rows stored as fp16)
-        return linear(ctx, s, A, lda, L, C, ldc, m, d_m, leaky, slope, acc64, a_rows, c_rows, flop_override, coef, coef_done, out_half);
-    }
-    if (m <= 0) return MPE_OK;
-    int rc = ensure_bf16_weights(ctx, &L);
-    if (rc) return rc;
-    if (lda < L.ldw) return fail(ctx, MPE_ERR_INVALID, "activation stride %d < padded K %d", lda, L.ldw);
-    const bool host_m = !d_m || flop_override >= 0.0;
-    GemmProf gp(ctx, s, flop_override >= 0.0 ? flop_override : (d_m ? 0.0 : 2.0 * m * (double)L.out_dim * L.in_dim),
-                host_m ? 0 : L.out_dim, host_m ? 0 : L.in_dim, 2);
-    HIPCHK(ctx, launch_linear_bf16(s, A, lda, L.w16, L.ldw16, L.b, C, ldc, m, d_m, L.out_dim, L.ldw16, leaky, slope,
-                                   L.ldw, out_half, a_rows, c_rows));
-    return MPE_OK;
+    GatGemmQuery q;
+    q.gat_split = ctx->gat_split;
+    q.gat_reduced = ctx->gat_reduced;
+    q.gat_acc64 = ctx->gat_acc64;
+    q.acc64_mink = mink;
+    q.in_dim = L.in_dim;
+    q.out_half = out_half;
+    q.leaky = leaky;
+    q.gathered = a_rows || c_rows;
+    q.l0_view = L.w == ctx->l0_w;
+    q.is_l0_fc2 = &L == &ctx->gat[0].fc2;
+    q.sb16_tile = out_half && linear_sb16_uses_tile_kernel(m, L.out_dim, false);       // (asked only where it decides)
+    return gemm(ctx, s, gat_gemm_form(q), L, {A, lda, C, ldc, m, d_m, leaky, slope, a_rows, c_rows, flop_override, coef, coef_done, out_half});
 }
 
 void drop_gat_workspace(mpe_ctx *ctx) {
@@ -296,7 +343,7 @@ int ensure_gat_workspace(mpe_ctx *ctx) {
     HIPCHK(ctx, hipMemcpy(d_c1, c1.data(), c1.size() * sizeof(float), hipMemcpyHostToDevice));
     const bool was = ctx->profiling;
     ctx->profiling = false;
-    rc = linear(ctx, nullptr, d_c1, ctx->feat_ld, g0.fc2, ctx->en0_ft2, ctx->act_ld, 1, nullptr, false, 0.f);
+    rc = gemm(ctx, nullptr, GemmForm::F32, ctx->gat[0].fc2, {d_c1, ctx->feat_ld, ctx->en0_ft2, ctx->act_ld, 1, nullptr, false, 0.f});
     ctx->profiling = was;
     if (rc) return rc;
     HIPCHK(ctx, launch_attn_coef(nullptr, ctx->en0_ft2, ctx->act_ld, 1, g0.heads, g0.out_dim, g0.attn_l, g0.attn_r,
@@ -341,37 +388,12 @@ int ensure_gat_workspace(mpe_ctx *ctx) {
     return MPE_OK;
 }
 
-unsigned short f32_to_bf16(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (unsigned short)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7FFFu + ((u >> 16) & 1u);          // round to nearest even
-    return (unsigned short)(u >> 16);
-}
-
-int ensure_bf16_weights(mpe_ctx *ctx, Linear *L) {
-    if (L->w16) return MPE_OK;
-    const int rows = weight_rows(L->out_dim);
-    L->ldw16 = round_up(L->in_dim, 128);
-    std::vector<float> w((size_t)rows * L->ldw);
-    HIPCHK(ctx, hipMemcpy(w.data(), L->w, w.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<unsigned short> wb((size_t)rows * L->ldw16, 0);
-    for (int r = 0; r < rows; ++r)
-        for (int k = 0; k < L->in_dim; ++k) wb[(size_t)r * L->ldw16 + k] = f32_to_bf16(w[(size_t)r * L->ldw + k]);
-    int rc = dev_alloc(ctx, &L->w16, wb.size(), false);
+// caller-provided dense rows of layer 0 and their fc1 output (the API mirrors only: allocated at first use)
+int ensure_dense_workspace(mpe_ctx *ctx) {
+    if (ctx->xdense) return MPE_OK;
+    int rc = dev_alloc(ctx, &ctx->xdense, (size_t)ctx->max_nodes * ctx->feat_ld);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy(L->w16, wb.data(), wb.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    return MPE_OK;
-}
-
-// the three bf16 planes of a weight matrix (split on the device from the padded fp32 copy, stream-ordered)
-int ensure_split_weights(mpe_ctx *ctx, hipStream_t s, Linear *L) {
-    if (L->w3) return MPE_OK;
-    const size_t count = (size_t)weight_rows(L->out_dim) * L->ldw;
-    int rc = dev_alloc(ctx, &L->w3, 3 * count, false);
-    if (rc) return rc;
-    HIPCHK(ctx, launch_split_planes(s, L->w, count, L->w3));
-    return MPE_OK;
+    return dev_alloc(ctx, &ctx->hdense, (size_t)ctx->max_nodes * ctx->feat_ld);
 }
 
 int ensure_mlp_workspace(mpe_ctx *ctx) {
@@ -498,6 +520,15 @@ AggArgs gat_agg_args(const mpe_ctx *ctx, int l) {
     return a;
 }
 
+// the last layer's attention stage writes the scores: edge-nodes to d_scores_en, heads (optional) to d_scores_heads
+void agg_scores_out(const mpe_ctx *ctx, AggArgs *a, float *d_scores_en, float *d_scores_heads) {
+    a->out_mode = ctx->gat_out_mode;
+    a->score_mode = 1;
+    a->out = d_scores_en;
+    a->out_heads = d_scores_heads;
+    a->ld_out = 1;
+}
+
 int gat_attention(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, int l, const AggArgs &a, int n_rows_ft2) {
     const GatLayer &g = ctx->gat[l];
     HIPCHK(ctx, launch_gat_attention(s, *b, ctx->cfg.n_cameras, ctx->cfg.max_heads_per_frame, ctx->node_off,
@@ -602,34 +633,27 @@ int run_gat_lat(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, float *d_scores
             if (lat_gemm_fusable(g.fc1.ldw, g.in_dim, g.fc2.ldw, hd, g.out_dim)) {
                 // the last layer: fc1 and the one-row fc2 in one launch (k_lat_gemm<.., FUSE2>)
                 GemmProf gp(ctx, s, 2.0 * n_nodes * (double)g.in_dim * (g.in_dim + hd), 0, 0, 1);
-                HIPCHK(ctx, launch_lat_gemm_fused(s, ctx->gat_pl[0], ctx->act_ld, ctx->gat_pl_plane, g.fc1.w3, (size_t)weight_rows(g.fc1.out_dim) * g.fc1.ldw,
-                                                  g.fc1.ldw, g.fc1.b, n_nodes, g.in_dim, ctx->gat_alpha, g.fc2.w3,
-                                                  (size_t)weight_rows(g.fc2.out_dim) * g.fc2.ldw, g.fc2.ldw, g.fc2.b, ctx->act[2], ctx->act_ld, g.attn_l, g.attn_r,
-                                                  ctx->a12));
+                HIPCHK(ctx, launch_lat_gemm_fused(s, ctx->gat_pl[0], ctx->act_ld, ctx->gat_pl_plane, g.fc1.w3, plane_elems(g.fc1), g.fc1.ldw, g.fc1.b,
+                                                  n_nodes, g.in_dim, ctx->gat_alpha, g.fc2.w3, plane_elems(g.fc2), g.fc2.ldw, g.fc2.b, ctx->act[2],
+                                                  ctx->act_ld, g.attn_l, g.attn_r, ctx->a12));
                 coef = true;
             } else {
-            {
-                GemmProf gp(ctx, s, 2.0 * n_nodes * (double)g.in_dim * g.in_dim, 0, 0, 1);
-                HIPCHK(ctx, launch_lat_gemm(s, ctx->gat_pl[0], ctx->act_ld, ctx->gat_pl_plane, g.fc1.w3, (size_t)weight_rows(g.fc1.out_dim) * g.fc1.ldw,
-                                            g.fc1.ldw, g.fc1.b, nullptr, 0, ctx->gat_pl[1], ctx->act_ld, ctx->gat_pl_plane, n_nodes, g.in_dim, g.fc1.ldw,
-                                            false, ctx->gat_alpha, nullptr, nullptr, nullptr, 0));
-            }
-            {
+                {
+                    GemmProf gp(ctx, s, 2.0 * n_nodes * (double)g.in_dim * g.in_dim, 0, 0, 1);
+                    HIPCHK(ctx, launch_lat_gemm(s, ctx->gat_pl[0], ctx->act_ld, ctx->gat_pl_plane, g.fc1.w3, plane_elems(g.fc1), g.fc1.ldw, g.fc1.b,
+                                                nullptr, 0, ctx->gat_pl[1], ctx->act_ld, ctx->gat_pl_plane, n_nodes, g.in_dim, g.fc1.ldw, false,
+                                                ctx->gat_alpha, nullptr, nullptr, nullptr, 0));
+                }
                 GemmProf gp(ctx, s, 2.0 * n_nodes * (double)hd * g.in_dim, 0, 0, 1);
-                HIPCHK(ctx, launch_lat_gemm(s, ctx->gat_pl[1], ctx->act_ld, ctx->gat_pl_plane, g.fc2.w3, (size_t)weight_rows(g.fc2.out_dim) * g.fc2.ldw,
-                                            g.fc2.ldw, g.fc2.b, ctx->act[2], ctx->act_ld, nullptr, 0, 0, n_nodes, hd, g.fc2.ldw, true, 0.f, g.attn_l,
-                                            g.attn_r, ctx->a12, g.out_dim, &coef));
-            }
+                HIPCHK(ctx, launch_lat_gemm(s, ctx->gat_pl[1], ctx->act_ld, ctx->gat_pl_plane, g.fc2.w3, plane_elems(g.fc2), g.fc2.ldw, g.fc2.b,
+                                            ctx->act[2], ctx->act_ld, nullptr, 0, 0, n_nodes, hd, g.fc2.ldw, true, 0.f, g.attn_l, g.attn_r, ctx->a12,
+                                            g.out_dim, &coef));
             }
             a.ft2 = ctx->act[2];
         }
         a.a12_ready = coef ? 1 : 0;
         if (l == L - 1) {
-            a.out_mode = ctx->gat_out_mode;
-            a.score_mode = 1;
-            a.out = d_scores_en;
-            a.out_heads = d_scores_heads;
-            a.ld_out = 1;
+            agg_scores_out(ctx, &a, d_scores_en, d_scores_heads);
             if (tail && coef && !d_scores_heads && g.heads == 1 && g.out_dim == 1) {
                 tail->deferred = true;
                 tail->ft2 = a.ft2;
@@ -662,11 +686,7 @@ int run_gat(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, float *d_scores_en,
     const bool dense_in = d_feats != nullptr;   // caller-provided N x F rows (GAT2.forward(inputs, g))
     if (dense_in) {
         if (ld_feats < ctx->gat[0].in_dim) return fail(ctx, MPE_ERR_INVALID, "feature stride too small");
-        if (!ctx->xdense) {
-            int rc2 = dev_alloc(ctx, &ctx->xdense, (size_t)ctx->max_nodes * ctx->feat_ld);
-            if (rc2) return rc2;
-            if ((rc2 = dev_alloc(ctx, &ctx->hdense, (size_t)ctx->max_nodes * ctx->feat_ld))) return rc2;
-        }
+        if ((rc = ensure_dense_workspace(ctx))) return rc;
         HIPCHK(ctx, hipMemcpy2DAsync(ctx->xdense, (size_t)ctx->feat_ld * sizeof(float), d_feats,
                                      (size_t)ld_feats * sizeof(float), (size_t)ctx->gat[0].in_dim * sizeof(float),
                                      n_nodes, hipMemcpyDeviceToDevice, s));
@@ -686,11 +706,7 @@ int run_gat(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, float *d_scores_en,
                                    &n_rows_ft2)))
             return rc;
         if (last) {
-            a.out_mode = ctx->gat_out_mode;
-            a.score_mode = 1;
-            a.out = d_scores_en;
-            a.out_heads = d_scores_heads;
-            a.ld_out = 1;
+            agg_scores_out(ctx, &a, d_scores_en, d_scores_heads);
         } else {
             a.out_mode = 0;
             a.out = ctx->act[0];
@@ -891,13 +907,7 @@ int mpe_upload_linear(mpe_ctx *ctx, const float *w, const float *b, int32_t out_
 int mpe_free_device(mpe_ctx *ctx, void *d_ptr) {
     if (!ctx) return MPE_ERR_INVALID;
     DeviceGuard dg(ctx);
-    for (size_t i = 0; i < ctx->owned.size(); ++i)
-        if (ctx->owned[i] == d_ptr) {
-            (void)hipFree(d_ptr);
-            ctx->owned.erase(ctx->owned.begin() + i);
-            return MPE_OK;
-        }
-    return fail(ctx, MPE_ERR_INVALID, "pointer not owned by this context");
+    return dev_free(ctx, d_ptr) ? MPE_OK : fail(ctx, MPE_ERR_INVALID, "pointer not owned by this context");
 }
 
 int mpe_linear(mpe_ctx *ctx, void *stream, const float *d_a, int32_t lda, const float *d_w, int32_t ldw,
@@ -927,7 +937,7 @@ int mpe_linear(mpe_ctx *ctx, void *stream, const float *d_a, int32_t lda, const 
         hipStream_t s = static_cast<hipStream_t>(stream);
         // (d_w must hold weight_rows(n) = round_up(n, 16) + 208 rows of ldw floats, zero padded, as mpe_upload_linear prepares
         // them: the planes are made of all of them, and the loader's 32-bit per-lane offset covers 3 planes of that size)
-        const size_t count = (size_t)weight_rows(n) * ldw;
+        const size_t count = plane_elems(L);
         if (3 * count * sizeof(unsigned short) >= ((size_t)1 << 32))
             return fail(ctx, MPE_ERR_INVALID, "mpe_linear (split form): n x ldw too large for the 32-bit plane offsets");
         unsigned short *planes = nullptr;
@@ -941,8 +951,8 @@ int mpe_linear(mpe_ctx *ctx, void *stream, const float *d_a, int32_t lda, const 
         HIPCHK(ctx, e);
         return MPE_OK;
     }
-    return linear(ctx, static_cast<hipStream_t>(stream), d_a, lda, L, d_c, ldc, m, d_m, (slope_on & 1) != 0, slope,
-                  (slope_on & 2) != 0);
+    return gemm(ctx, static_cast<hipStream_t>(stream), (slope_on & 2) ? GemmForm::F32_ACC64 : GemmForm::F32, L,
+                {d_a, lda, d_c, ldc, m, d_m, (slope_on & 1) != 0, slope});
 }
 
 int mpe_head_features(mpe_ctx *ctx, void *stream, const mpe_batch *b, float *d_feat) {
@@ -1058,10 +1068,7 @@ int mpe_gat_layer(mpe_ctx *ctx, void *stream, const mpe_batch *b, int32_t layer,
     const int n_nodes = b->n_heads + b->n_edge_nodes;
     if ((rc = gat_topology(ctx, s, b))) return rc;
     if (layer == 0) {
-        if (!ctx->xdense) {
-            if ((rc = dev_alloc(ctx, &ctx->xdense, (size_t)ctx->max_nodes * ctx->feat_ld))) return rc;
-            if ((rc = dev_alloc(ctx, &ctx->hdense, (size_t)ctx->max_nodes * ctx->feat_ld))) return rc;
-        }
+        if ((rc = ensure_dense_workspace(ctx))) return rc;
         if ((rc = copy_rows_in(ctx, s, ctx->xdense, ctx->feat_ld, d_in, ld_in, g.in_dim, n_nodes))) return rc;
     } else if ((rc = copy_rows_in(ctx, s, ctx->act[0], ctx->act_ld, d_in, ld_in, g.in_dim, n_nodes)))
         return rc;
@@ -1203,33 +1210,18 @@ static int mlp_chain(mpe_ctx *ctx, hipStream_t s, const float *x, int ld_x, int 
     if (dec_done) *dec_done = false;
     const float *in = x;
     int ld_in = ld_x;
-    int rc;
+    const GemmForm form = mlp_gemm_form(ctx->mlp_mode);
     for (int l = 0; l < ctx->mlp_layers; ++l) {
+        Linear &L = ctx->mlp[l];
         float *out = ctx->mlp_act[l & 1];
         const bool last = l == ctx->mlp_layers - 1;
-        if (ctx->mlp_f64mm) {
-            Linear &L = ctx->mlp[l];
-            if (ld_in < L.ldw) return fail(ctx, MPE_ERR_INVALID, "activation stride %d < padded K %d", ld_in, L.ldw);
-            GemmProf gp(ctx, s, d_m ? 0.0 : 2.0 * m * (double)L.out_dim * L.in_dim, d_m ? L.out_dim : 0, d_m ? L.in_dim : 0, 3);
-            HIPCHK(ctx, launch_linear_f64(s, in, ld_in, L.w, L.ldw, L.b, out, ctx->mlp_ld_hidden, m, d_m, L.out_dim, L.ldw, !last, ctx->mlp_slope));
-        } else if (ctx->mlp_split) {
-            Linear &L = ctx->mlp[l];
-            if ((rc = ensure_split_weights(ctx, s, &L))) return rc;
-            if (ld_in < L.ldw) return fail(ctx, MPE_ERR_INVALID, "activation stride %d < padded K %d", ld_in, L.ldw);
-            GemmProf gp(ctx, s, d_m ? 0.0 : 2.0 * m * (double)L.out_dim * L.in_dim, d_m ? L.out_dim : 0, d_m ? L.in_dim : 0, 1);
-            HIPCHK(ctx, launch_linear_sb16(s, in, ld_in, L.w3, (size_t)weight_rows(L.out_dim) * L.ldw, L.ldw, L.b, out, ctx->mlp_ld_hidden, m,
-                                           d_m, L.out_dim, L.ldw, !last, ctx->mlp_slope, true, nullptr, nullptr, false, ctx->mlp_flush,
-                                           last ? dec : nullptr, last ? dec_done : nullptr));
-        } else if (ctx->mlp_bf16) {
-            Linear &L = ctx->mlp[l];
-            if ((rc = ensure_bf16_weights(ctx, &L))) return rc;
-            if (ld_in < L.ldw16) return fail(ctx, MPE_ERR_INVALID, "bf16 GEMM needs an input stride >= %d", L.ldw16);
-            GemmProf gp(ctx, s, d_m ? 0.0 : 2.0 * m * (double)L.out_dim * L.in_dim, d_m ? L.out_dim : 0, d_m ? L.in_dim : 0, 2);
-            HIPCHK(ctx, launch_linear_bf16(s, in, ld_in, L.w16, L.ldw16, L.b, out, ctx->mlp_ld_hidden, m, d_m, L.out_dim,
-                                           L.ldw16, !last, ctx->mlp_slope));
-        } else if ((rc = linear(ctx, s, in, ld_in, ctx->mlp[l], out, ctx->mlp_ld_hidden, m, d_m, !last, ctx->mlp_slope,
-                                ctx->mlp_acc64)))
-            return rc;
+        GemmCall c{in, ld_in, out, ctx->mlp_ld_hidden, m, d_m, !last, ctx->mlp_slope};
+        c.flush_stages = split_flush_stages(ctx->mlp_mode);
+        c.dec = last ? dec : nullptr;
+        c.dec_done = last ? dec_done : nullptr;
+        c.bf16_min_ld = round_up(L.in_dim, 128);               // (= L.ldw16: the bf16 launches of the MLP read whole K stages)
+        const int rc = gemm(ctx, s, form, L, c);
+        if (rc) return rc;
         in = out;
         ld_in = ctx->mlp_ld_hidden;
     }
@@ -1523,23 +1515,19 @@ int mpe_dlt_pairs(mpe_ctx *ctx, void *stream, const double *d_pts, const int32_t
     return MPE_OK;
 }
 
-int mpe_set_precision(mpe_ctx *ctx, int32_t gat_acc64, int32_t mlp_acc64) {
+int mpe_set_precision(mpe_ctx *ctx, int32_t gat_mode, int32_t mlp_mode) {
     if (!ctx) return MPE_ERR_INVALID;
     DeviceGuard dg(ctx);
-    if (gat_acc64 < 0 || gat_acc64 > 6 || mlp_acc64 < 0 || mlp_acc64 > 5)
+    if (gat_mode < 0 || gat_mode > 6 || mlp_mode < 0 || mlp_mode > 5)
         return fail(ctx, MPE_ERR_INVALID, "precision modes: GAT 0..6, MLP 0..5");
     // GAT modes 4 / 5: modes 0 / 1 with the GEMMs of layers >= 1 in the split-bf16 form (4 = the default); 6 = mode 3 likewise
-    // (fp16 rows: from the split tile kernel's coefficient epilogue where gat_linear finds it applicable, the fp32 MFMA otherwise)
-    ctx->gat_split = gat_acc64 >= 4;
-    if (gat_acc64 >= 4) gat_acc64 = gat_acc64 == 4 ? 0 : gat_acc64 == 5 ? 1 : 3;
-    ctx->gat_acc64 = gat_acc64 == 1;
-    ctx->gat_reduced = gat_acc64 == 2;
-    ctx->gat_attn_fp16 = gat_acc64 == 3;
-    ctx->mlp_acc64 = mlp_acc64 == 1;
-    ctx->mlp_bf16 = mlp_acc64 == 2;
-    ctx->mlp_split = mlp_acc64 == 3 || mlp_acc64 == 4;
-    ctx->mlp_f64mm = mlp_acc64 == 5;               // MLP mode 5: exact products + f64 accumulation on the f64 matrix pipe
-    ctx->mlp_flush = mlp_acc64 == 4 ? 1 : 2;       // MLP mode 4: the split form with an f64 flush per K stage (maximum accuracy)
+    // (fp16 rows: from the split tile kernel's coefficient epilogue where gat_gemm_form finds it applicable, the fp32 MFMA otherwise)
+    ctx->gat_split = gat_mode >= 4;
+    if (gat_mode >= 4) gat_mode = gat_mode == 4 ? 0 : gat_mode == 5 ? 1 : 3;
+    ctx->gat_acc64 = gat_mode == 1;
+    ctx->gat_reduced = gat_mode == 2;
+    ctx->gat_attn_fp16 = gat_mode == 3;
+    ctx->mlp_mode = static_cast<MlpMode>(mlp_mode);      // (which form each mode runs on: gemm_form.h)
     return MPE_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/mpe.h"
+#include "gemm_form.h"
 
 namespace mpe {
 
@@ -28,6 +29,8 @@ struct Linear {                // one nn.Linear, zero padded on the device
     unsigned short *w3 = nullptr;    // optional: the three bf16 planes of w, [3][weight_rows(out)][ldw] (split-bf16 mode, gemm_sb16.hip)
     int in_dim = 0, out_dim = 0, ldw = 0;
 };
+// elements of the padded weight matrix = stride between the bf16 planes of w3
+inline size_t plane_elems(const Linear &L) { return (size_t)weight_rows(L.out_dim) * L.ldw; }
 
 struct GatLayer {
     Linear fc1, fc2;
@@ -102,11 +105,7 @@ struct mpe_ctx {
     bool en0_ready = false;
     int mlp_layers = 0;
     float mlp_slope = 0.1f;
-    bool mlp_acc64 = true;         // fp32 MFMA with f64 running sums per K stage in the MLP GEMMs (MLP mode 1; the parity mode of rounds 1-3)
-    bool mlp_bf16 = false;         // reduced precision: bf16 MFMA for the MLP GEMMs
-    bool mlp_f64mm = false;        // MLP mode 5: every launch on the f64 matrix pipe (gemm_f64.hip)
-    int mlp_flush = 2;             // MLP modes 3 / 4: K stages per f64 flush of the split form (2 = default, 1 = the maximum-accuracy mode)
-    bool mlp_split = true;         // DEFAULT (MLP mode 3): fp32-accurate MLP GEMMs on the bf16 MFMA (three bf16 planes per operand, six products, f64 sums every second stage)
+    mpe::MlpMode mlp_mode = mpe::MlpMode::Split;   // which form the MLP GEMMs run on (mpe_set_precision; gemm_form.h)
     bool gat_acc64 = false;
     bool gat_reduced = false;      // reduced precision: bf16 MFMA GEMMs + fp16 feature rows in the attention stage
     bool gat_attn_fp16 = false;    // configs[4] as BASELINE words it: fp16 feature rows (ft2) in the attention stage, GEMMs stay fp32

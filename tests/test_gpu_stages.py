@@ -890,3 +890,36 @@ def test_run_pipelined_gives_the_same_bits_as_sequential_calls():
         assert np.array_equal(first[1].cpu().numpy(), want[0][1])
     eng.close()
     assert eng._siblings == []
+
+
+def test_gemm_launch_census_is_the_parents():
+    """Which GEMM launches every precision mode makes (tools/gemm_census.py: 7 GAT and 6 MLP settings x MPE_LATENCY_PATH unset / 0 x
+    MPE_NO_COEF_EPILOGUE unset / set x batches of 1, 17 and 40 frames, one match + mlp3d each): the launch counts and the FLOP
+    figures of the fp32 MFMA, split-bf16 and plain bf16 forms must equal, exactly, what the commit before the dispatch became one
+    function (csrc/api.hip: gemm(), csrc/gemm_form.h) gave -- tests/golden/harness/gemm_census.json is that tool's output there.
+    The counts are integers and the FLOP figures sums of integers below 2^53; the millisecond fields are not compared."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('gemm_census', os.path.join(ROOT, 'tools', 'gemm_census.py'))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(ROOT, 'tests', 'golden', 'harness', 'gemm_census.json')) as fh:
+        want = json.load(fh)
+    e = env('panoptic')
+    eng = pkg('pipeline').Engine(e.params, e.calib, max_frames=64, max_persons_per_camera=10)
+    saved = {k: os.environ.get(k) for k in ('MPE_LATENCY_PATH', 'MPE_NO_COEF_EPILOGUE')}
+    try:
+        eng.load_gat(*e.gat)
+        eng.load_mlp(e.mlp)
+        got = tool.census(eng, e.calib)
+    finally:
+        eng.set_precision()
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        eng.close()
+    assert sorted(got) == sorted(want) and len(want) == 13 * 4 * 3
+    diff = {k: ([got[k][f] for f in tool.COMPARED], [want[k][f] for f in tool.COMPARED])
+            for k in want if any(got[k][f] != want[k][f] for f in tool.COMPARED)}
+    assert not diff, diff

@@ -885,6 +885,24 @@ def test_eisel_lemire_against_strtod(tmp_path):
     assert m and int(m.group(3)) == 0 and int(m.group(1)) > 2000000 and int(m.group(2)) < int(m.group(1)) // 2
 
 
+def test_gemm_form_choice_against_its_truth_table(tmp_path):
+    """csrc/gemm_form.h (which GEMM form an nn.Linear launch runs on) built for the host: every combination of the GAT
+    precision mode and launch shape with K in {40, 512, 513, 902} and the f64 threshold 0 / 512 against the rule written
+    out a second time in tests/native/gemm_form_test.cpp, the six MLP modes, and the deployed layer-0 launches by name."""
+    import shutil
+    import subprocess
+    gxx = shutil.which('g++')
+    if not gxx:
+        pytest.skip('g++ not available')
+    exe = str(tmp_path / 'gemm_form_test')
+    subprocess.run([gxx, '-O1', '-Wall', '-Werror', '-I', os.path.join(ROOT, '3d_multi_pose_estimator_amd', 'csrc'),
+                    os.path.join(ROOT, 'tests', 'native', 'gemm_form_test.cpp'), '-o', exe], check=True, capture_output=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r'tested (\d+) bad (\d+)', r.stdout)
+    assert m and int(m.group(1)) == 4096 and int(m.group(2)) == 0, r.stdout
+
+
 def test_lib_leaves_the_hardware_queue_setting_to_the_host_unless_asked():
     """Importing lib.py does not touch the host's environment (round 5: opt-in).  With MPE_SET_HW_QUEUES=1 it sets
     GPU_MAX_HW_QUEUES=8 before HIP initialises (two busy streams of a pipeline on one of HIP's default four hardware queues

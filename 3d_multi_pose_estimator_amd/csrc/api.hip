@@ -1403,6 +1403,87 @@ int mpe_track_batch(mpe_ctx *ctx, void *stream, mpe_track_state *st, const mpe_t
     return MPE_OK;
 }
 
+int mpe_smooth_destroy(mpe_ctx *ctx, mpe_smooth_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    for (int i = 0; i < 2; ++i) {
+        dev_free(ctx, st->pose[i]);
+        dev_free(ctx, st->mask[i]);
+        dev_free(ctx, st->id[i]);
+    }
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_smooth_create(mpe_ctx *ctx, int32_t pcap, int32_t n_joints, int32_t window, int32_t pose_f64, mpe_smooth_state **out) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_create: NULL argument");
+    *out = nullptr;
+    if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || window < 0 || window > MPE_SMOOTH_MAX_WINDOW || (pose_f64 & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_create: pcap %d / joints %d / window %d / pose_f64 %d; joints 1 .. %d, window 0 .. %d", pcap,
+                    n_joints, window, pose_f64, MPE_MAX_JOINTS, MPE_SMOOTH_MAX_WINDOW);
+    if (pcap > MPE_TRACK_MAX_PERSONS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_smooth_create: pcap %d over %d", pcap, MPE_TRACK_MAX_PERSONS);
+    DeviceGuard dg(ctx);
+    mpe_smooth_state *st = new (std::nothrow) mpe_smooth_state();
+    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_smooth_create: out of memory");
+    st->pcap = pcap;
+    st->J = n_joints;
+    st->W = window;
+    st->pose_f64 = pose_f64;
+    const size_t rows = (size_t)window * pcap;
+    int rc = MPE_OK;
+    for (int i = 0; i < 2 && !rc; ++i) {
+        rc = dev_alloc(ctx, &st->pose[i], rows * n_joints * 3);
+        if (!rc) rc = dev_alloc(ctx, &st->mask[i], rows);
+        if (!rc) rc = dev_alloc(ctx, &st->id[i], rows);
+        if (!rc && rows && hipMemset(st->id[i], 0xFF, rows * sizeof(int32_t)) != hipSuccess)          // -1: nobody is seen yet
+            rc = fail(ctx, MPE_ERR_HIP, "mpe_smooth_create: hipMemset failed");
+    }
+    if (rc) {
+        const std::string why = ctx->err;
+        mpe_smooth_destroy(ctx, st);
+        ctx->err = why;
+        return rc;
+    }
+    *out = st;
+    return MPE_OK;
+}
+
+int mpe_smooth_reset(mpe_ctx *ctx, void *stream, mpe_smooth_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_reset: NULL state");
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, launch_smooth_reset(static_cast<hipStream_t>(stream), st));
+    return MPE_OK;
+}
+
+int mpe_smooth_launches(mpe_ctx *ctx, const mpe_smooth_state *st, int64_t *n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_launches: NULL argument");
+    *n = st->launches;
+    return MPE_OK;
+}
+
+int mpe_smooth_batch(mpe_ctx *ctx, void *stream, mpe_smooth_state *st, const mpe_smooth_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->pcap != st->pcap || a->n_joints != st->J || a->pose_f64 != st->pose_f64)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: pcap %d / joints %d / pose_f64 %d, the state was made for %d / %d / %d", a->pcap,
+                    a->n_joints, a->pose_f64, st->pcap, st->J, st->pose_f64);
+    if (a->n_frames < 0 || (a->joint_flags & ~1) || !(a->lambda >= 0.25 && a->lambda <= 1.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: n_frames %d / joint_flags %d / lambda %g; lambda is within [0.25, 1]", a->n_frames,
+                    a->joint_flags, a->lambda);
+    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "mpe_smooth_batch: %d frames over 2^23 per call", a->n_frames);
+    if (a->n_frames == 0) return MPE_OK;
+    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_poses_out || !a->d_flags_out || !a->d_vel || !a->d_n_samples)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: NULL argument");
+    if (a->d_poses_out == a->d_poses) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: d_poses_out is d_poses (the window reads the raw poses)");
+    HIPCHK(ctx, launch_smooth(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
 int mpe_reproject_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_reproject_args *a) {
     int rc = check_batch(ctx, b);
     if (rc) return rc;

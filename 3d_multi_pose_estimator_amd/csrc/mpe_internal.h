@@ -190,6 +190,17 @@ struct mpe_track_state {
     int32_t *ws = nullptr;          // [1024] scratch of the birth pass
 };
 
+// smooth.hip: what mpe_smooth_batch carries from call to call, the raw input of the last W frames.  Two copies
+// ([W][pcap] rows each, oldest first) used as mpe_track_state's are; a slot no frame has filled holds the id -1.
+struct mpe_smooth_state {
+    int pcap = 0, J = 0, W = 0, pose_f64 = 0;
+    int cur = 0;
+    int64_t launches = 0;           // kernels enqueued since mpe_smooth_create
+    double *pose[2] = {};           // [W][pcap][J][3], widened to f64
+    uint32_t *mask[2] = {};         // [W][pcap] joints present; 0 where the row is no detection
+    int32_t *id[2] = {};            // [W][pcap] track id, -1: no detection
+};
+
 namespace mpe {
 
 // gemm.hip
@@ -335,6 +346,10 @@ hipError_t launch_eval(hipStream_t s, const mpe_eval_args &a);
 hipError_t track_prepare(int pcap);                  // dynamic-LDS opt-in of the stage kernels for this device
 hipError_t launch_track_reset(hipStream_t s, mpe_track_state *st);
 hipError_t launch_track(hipStream_t s, mpe_track_state *st, const mpe_track_args &a);
+
+// smooth.hip
+hipError_t launch_smooth_reset(hipStream_t s, mpe_smooth_state *st);
+hipError_t launch_smooth(hipStream_t s, mpe_smooth_state *st, const mpe_smooth_args &a);
 
 // reproject.hip
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);

@@ -65,6 +65,13 @@ def build_parser(description):
                         '--testfiles together are one sequence, in the order given: pass one recording per run')
     p.add_argument('--track-gate', type=float, default=0.5, metavar='M', help='--track: largest mean joint distance of a link, metres')
     p.add_argument('--track-gap', type=int, default=2, metavar='N', help='--track: frames a person may go undetected and keep the identity')
+    p.add_argument('--smooth', type=int, default=0, metavar='W',
+                   help='implies --track; the tracked poses are fitted with a line per track and joint over the current frame and the W frames '
+                        'before it, 1..15 (mpe_smooth_batch, the state carried across --batch chunks), the fitted poses are scored, and one '
+                        'further line reports the joints fitted, the joints filled and the mean displacement')
+    p.add_argument('--smooth-decay', type=float, default=0.8, metavar='L', help='--smooth: weight ratio of consecutive frames, within [0.25, 1]')
+    p.add_argument('--smooth-fill', action='store_true',
+                   help='--smooth: a triangulated joint that is missing now but was seen twice or more in the window gets the value of the line')
     p.add_argument('--refine', type=int, default=0, metavar='ITERS',
                    help='implies --device-metrics; every joint is moved to the minimum of its reprojection error over the cameras that saw it '
                         '(mpe_refine_batch: at most ITERS Levenberg-Marquardt iterations per joint, 1..64) and the refined poses are scored; '
@@ -471,6 +478,9 @@ def run(args, mode):
     calib = Calibration(parameters)
     device_gt = getattr(args, 'device_gt', False) and not args.synthetic       # synthetic frames have no file to parse
     refine = int(getattr(args, 'refine', 0) or 0)
+    smooth = int(getattr(args, 'smooth', 0) or 0)
+    if smooth:
+        args.track = True
     if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
         args.device_metrics = True
     src = [] if device_gt else None
@@ -484,11 +494,14 @@ def run(args, mode):
     T_i1 = torch.from_numpy(calib.T_i32[1])
     J = eng.J
     t = {'match': 0.0, '3d': 0.0}
-    tracker = summary = None
+    tracker = summary = smoother = smoothed = None
     refined = []
     if getattr(args, 'track', False):
         from .tracking import TrackSummary
         tracker, summary = eng.tracker(mode, max_gap=args.track_gap, gate=args.track_gate), TrackSummary()
+    if smooth:
+        from .smoothing import SmoothSummary
+        smoother, smoothed = eng.smoother(mode, window=smooth, decay=args.smooth_decay, fill=args.smooth_fill), SmoothSummary(mode)
 
     def infer(frames, owners):
         db = eng.to_device(eng.pack(frames))
@@ -546,15 +559,27 @@ def run(args, mode):
             refined.append({k: ref[k].cpu().numpy() for k in ('status', 'cost0', 'cost1')})
         torch.cuda.synchronize()
         t2 = time.time()
+        if tracker is not None:
+            # the frames that are evaluated (a cross-camera pair, as Engine.evaluate's skip rule has it), in order
+            keep = torch.from_numpy(np.flatnonzero(np.diff(np.asarray(db.host.frame_en_off[:db.n_frames + 1])) != 0)).to(poses.device)
+        if smoother is not None:
+            # track, then smooth, then scoring: the fitted poses of the tracked frames take the place of the raw ones
+            p_in, f_in, n_in = poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep)
+            tr = tracker.update(p_in, f_in, n_in)
+            sm = smoother.update(p_in, f_in, n_in, tr['ids'])
+            poses, flags = poses.index_copy(0, keep, sm['poses']), flags.index_copy(0, keep, sm['flags'])
+            torch.cuda.synchronize()
+        t3 = time.time()
         ev = eng.evaluate(db, poses, flags, n_persons, gt, mode)
         torch.cuda.synchronize()
         t['match'] += t1 - t0
         t['3d'] += t2 - t1
-        t['eval'] += time.time() - t2
+        t['eval'] += time.time() - t3
         eng.sync_status()
-        if tracker is not None:
-            # the frames that are evaluated (a cross-camera pair, as Engine.evaluate's skip rule has it), in order
-            keep = torch.from_numpy(np.flatnonzero(np.diff(np.asarray(db.host.frame_en_off[:db.n_frames + 1])) != 0)).to(poses.device)
+        if smoother is not None:
+            summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
+            smoothed.add(p_in.cpu().numpy(), f_in.cpu().numpy(), {k: sm[k].cpu().numpy() for k in ('poses', 'flags', 'n_samples')})
+        elif tracker is not None:
             tr = tracker.update(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
         return ev
@@ -592,6 +617,11 @@ def run(args, mode):
         print('Tracks (gate %g m, gap %d): %d, mean length %.3f frames, %d born after the first frame'
               % (args.track_gate, args.track_gap, out['tracks']['tracks'], out['tracks']['mean_length'], out['tracks']['late_births']))
         tracker.close()
+    if smoother is not None:
+        out['smooth'] = r = smoothed.result()
+        print('Smoothed (window %d, decay %g%s): %d joints fitted, %d filled, mean displacement %.3f mm'
+              % (smooth, args.smooth_decay, ', fill' if args.smooth_fill else '', r['fitted'], r['filled'], r['mean_move_mm']))
+        smoother.close()
     out['n_data'] = n_data
     if device_gt:
         out['gt_windows'], out['gt_declined'] = gt_windows

@@ -90,6 +90,13 @@ class mpe_track_args(C.Structure):
                 ('d_track_id', C.c_void_p), ('d_link_cost', C.c_void_p), ('d_link_gap', C.c_void_p), ('d_issued', C.c_void_p)]
 
 
+class mpe_smooth_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('fill', C.c_int32), ('joint_mask', C.c_uint32), ('lambda_', C.c_double),
+                ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p),
+                ('d_poses_out', C.c_void_p), ('d_flags_out', C.c_void_p), ('d_vel', C.c_void_p), ('d_n_samples', C.c_void_p)]
+
+
 class mpe_reproject_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
                 ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float),
@@ -152,6 +159,9 @@ MPE_PART_MAX_SAMPLES, MPE_PART_MAX_SKELETONS, MPE_PART_MAX_KEYS = 256, 1024, 32
 # compiled caps of mpe_track_create
 MPE_TRACK_MAX_PERSONS, MPE_TRACK_MAX_GAP = 128, 15
 
+# the window cap of mpe_smooth_create and the output flag of a joint that mpe_smooth_batch filled in
+MPE_SMOOTH_MAX_WINDOW, MPE_SMOOTH_FILLED = 15, 2
+
 # per-joint status bits and the iteration cap of mpe_refine_batch
 MPE_REFINE_SOLVED, MPE_REFINE_MOVED, MPE_REFINE_CONVERGED, MPE_REFINE_FEW_VIEWS, MPE_REFINE_BAD_START = 1, 2, 4, 8, 16
 MPE_REFINE_MAX_ITERS = 64
@@ -207,6 +217,11 @@ SYMBOLS = {
     'mpe_track_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
     'mpe_track_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_track_args)]),
     'mpe_track_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_smooth_create': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    'mpe_smooth_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_smooth_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_smooth_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_smooth_args)]),
+    'mpe_smooth_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_args)]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),

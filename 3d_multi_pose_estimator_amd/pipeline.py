@@ -1018,6 +1018,14 @@ class Engine:
         are not this engine's (default: the engine's Pcap)."""
         return Tracker(self, mode, max_gap, gate, self.pcap if pcap is None else int(pcap))
 
+    def smoother(self, mode, window=6, decay=0.8, fill=False, pcap=None):
+        """A Smoother for one tracked sequence of poses in `mode` ('mlp' or 'tri', as Engine.tracker takes it): every
+        joint of every track is fitted with a line over the current frame and the `window` frames before it, weighted
+        by decay ** age (mpe_smooth_batch), which gives a position with less jitter and a velocity.  fill (mode 'tri'):
+        a joint that is missing now but was seen twice or more in the window gets the line's value and the flag 2.
+        pcap: rows per frame when the poses are not this engine's (default: the engine's Pcap)."""
+        return Smoother(self, mode, window, decay, fill, self.pcap if pcap is None else int(pcap))
+
     def _pose_args(self, db, persons, n_persons, poses, flags, kind, joint_mask, kinds):
         """The argument checks reproject and refine share -> (B, tri, joint_mask)."""
         B = db.n_frames
@@ -1339,6 +1347,80 @@ class Tracker:
     def close(self):
         if getattr(self, 'state', None) and self.eng.ctx:
             self.eng.lib.mpe_track_destroy(self.eng.ctx, self.state)
+        self.state = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Smoother:
+    """Engine.smoother's object: the device state of one sequence (the raw poses, presence and ids of the last `window`
+    frames).  update() takes the frames of the sequence in order, in chunks of any size, with the ids Tracker.update
+    gave them; the result does not depend on the chunking.  Everything stays on the device and on the current stream:
+    update() neither synchronises nor reads anything back."""
+
+    def __init__(self, eng, mode, window, decay, fill, pcap):
+        if mode not in ('mlp', 'tri'):
+            raise ValueError('mode must be mlp or tri')
+        if not 0 <= int(window) <= L.MPE_SMOOTH_MAX_WINDOW:
+            raise ValueError('window must be within 0 .. %d' % L.MPE_SMOOTH_MAX_WINDOW)
+        if not 0.25 <= decay <= 1.0:
+            raise ValueError('decay must be within [0.25, 1]')
+        self.eng, self.mode, self.window, self.decay, self.fill, self.pcap = eng, mode, int(window), float(decay), bool(fill), pcap
+        self.state = C.c_void_p()
+        eng._chk(eng.lib.mpe_smooth_create(eng.ctx, self.pcap, eng.J, self.window, int(mode == 'tri'), C.byref(self.state)))
+
+    def update(self, poses, flags, n_persons, ids, joint_mask=None):
+        """poses / flags / n_persons of the next B >= 0 frames as Tracker.update took them, and the 'ids' it returned.
+        joint_mask: the joints to process (default: all).  -> {'poses', 'flags' (the types and shapes of the inputs,
+        new tensors; flags 2: a filled joint), 'vel' [B,Pcap,J,3] f64 (metres per frame), 'n_samples' [B,Pcap,J] u8
+        (samples the window held)}, device tensors."""
+        eng, tri = self.eng, self.mode == 'tri'
+        if not self.state:
+            raise RuntimeError('the smoother is closed')
+        B = int(poses.shape[0]) if poses.dim() == 4 else -1
+        want = torch.float64 if tri else torch.float32
+        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, eng.J, 3):
+            raise ValueError('poses must be %s [B,%d,%d,3]' % (want, self.pcap, eng.J))
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if tri else (B, self.pcap)):
+            raise ValueError('flags do not match mode %s' % self.mode)
+        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
+            raise ValueError('n_persons must be int32 [%d]' % B)
+        if ids.dtype != torch.int32 or tuple(ids.shape) != (B, self.pcap):
+            raise ValueError('ids must be int32 [%d,%d]' % (B, self.pcap))
+        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous() and ids.is_contiguous()):
+            raise ValueError('poses, flags, n_persons and ids must be contiguous')
+        if any(t.device != eng.device for t in (poses, flags, n_persons, ids)):
+            raise ValueError('poses, flags, n_persons and ids must be on %s' % eng.device)
+        dev = eng.device
+        out = {'poses': torch.empty_like(poses), 'flags': torch.empty_like(flags),
+               'vel': torch.empty((B, self.pcap, eng.J, 3), dtype=torch.float64, device=dev),
+               'n_samples': torch.empty((B, self.pcap, eng.J), dtype=torch.uint8, device=dev)}
+        a = L.mpe_smooth_args()
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags, a.fill = B, self.pcap, eng.J, int(tri), int(tri), int(self.fill)
+        a.joint_mask = (1 << eng.J) - 1 if joint_mask is None else int(joint_mask)
+        a.lambda_ = self.decay
+        a.d_poses, a.d_flags, a.d_n_persons, a.d_track_id = poses.data_ptr(), flags.data_ptr(), n_persons.data_ptr(), ids.data_ptr()
+        a.d_poses_out, a.d_flags_out, a.d_vel, a.d_n_samples = (out[k].data_ptr() for k in ('poses', 'flags', 'vel', 'n_samples'))
+        eng._chk(eng.lib.mpe_smooth_batch(eng.ctx, eng._stream(), self.state, C.byref(a)))
+        return out
+
+    def launches(self):
+        """Kernels this smoother has enqueued so far."""
+        n = C.c_int64()
+        self.eng._chk(self.eng.lib.mpe_smooth_launches(self.eng.ctx, self.state, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Start a new sequence (ordered on the current stream)."""
+        self.eng._chk(self.eng.lib.mpe_smooth_reset(self.eng.ctx, self.eng._stream(), self.state))
+
+    def close(self):
+        if getattr(self, 'state', None) and self.eng.ctx:
+            self.eng.lib.mpe_smooth_destroy(self.eng.ctx, self.state)
         self.state = None
 
     def __del__(self):

@@ -766,6 +766,69 @@ int mpe_track_destroy(mpe_ctx *ctx, mpe_track_state *state);
 int mpe_track_batch(mpe_ctx *ctx, void *stream, mpe_track_state *state, const mpe_track_args *a);
 int mpe_track_launches(mpe_ctx *ctx, const mpe_track_state *state, int64_t *n);
 
+/* Smoothing: tracked poses filtered over time.  A causal, windowed, weighted line fit per (track, joint, axis) over the
+ * RAW poses of the current frame and the `window` (W) frames before it: no feedback, so every output is a function of
+ * W + 1 frames of input and all (frame, person, joint) outputs of a call are independent.  It follows d_track_id, not
+ * person rows.  The rule (harness/smoothing.py states it in numpy, and the two agree bit for bit):
+ *   Detections and joint presence as in mpe_track_batch.  Row p of frame f is a detection when p < d_n_persons[f],
+ *   d_track_id[f][p] >= 0 and, with joint_flags == 0, d_flags[f][p] != 0; joint_flags == 0: all joints of a detection
+ *   are present; joint_flags == 1: joint j is present when d_flags[f][p][j] != 0.  Only joints of joint_mask are
+ *   processed.
+ *   Samples of joint j of a detection with id t: for age a = 0 .. W the sample of age a exists when frame f - a exists
+ *   in the sequence (frames count over the whole sequence; the state supplies those before the call), that frame has a
+ *   detection with id t (the lowest such row; for a = 0 row p itself, which it is when ids are unique within a frame,
+ *   as the tracker's are), joint j is present in that row by the INPUT flags and its three stored coordinates are
+ *   finite.  Value: the stored input coordinate widened to f64.  Weight: w_0 = 1, w_a = w_(a-1) * lambda, every
+ *   product rounded on its own.
+ *   Sums: n = the number of samples, r = the youngest one.  Per axis, y_a = x_a - x_r, u_a = (double)a, c_a = w_a * u_a;
+ *   left-fold sums from 0.0 over the samples in increasing a, nothing contracted:
+ *   S0 += w_a; S1 += c_a; S2 += c_a * u_a; T0 += w_a * y_a; T1 += c_a * y_a.
+ *   Fit (IEEE f64 divisions): D = S0*S2 - S1*S1; alpha = x_r + (S2*T0 - S1*T1) / D; beta = (S0*T1 - S1*T0) / D.  A fit
+ *   exists when n >= 2, D > 0 and alpha and beta are finite on all three axes.
+ *   Joint present now (the sample of age 0 exists): with a fit d_poses_out = alpha, rounded once to the pose type, and
+ *   d_vel = -beta (metres per frame); without one the input bits are copied and d_vel = 0.  A joint that is present
+ *   but not finite now is copied likewise.  d_flags_out is 1 for a present joint with joint_flags == 1; with
+ *   joint_flags == 0 it is the input flag.
+ *   Joint missing now (joint_flags == 1 only): with fill != 0 and a fit, d_poses_out = alpha, d_vel = -beta and
+ *   d_flags_out = MPE_SMOOTH_FILLED; otherwise the input bits, d_flags_out = 0, d_vel = 0.
+ *   d_n_samples = n for every processed joint.  Rows that are no detection and joints outside joint_mask are copied
+ *   through bit for bit with d_vel = 0, d_n_samples = 0 and the input flag.  window == 0 copies everything.
+ * A person who has no row at all in a frame gets none here either.  The state holds, for the last W frames, the
+ * coordinates widened to f64, the presence masks and the ids: a sequence cut into any chunks, one frame per call
+ * included, gives the same bits.  window is fixed at create time; lambda, fill, joint_flags and joint_mask are per call.
+ * mpe_smooth_create allocates all device memory the calls need (MPE_ERR_CAPACITY for pcap > MPE_TRACK_MAX_PERSONS,
+ * MPE_ERR_INVALID for a window outside 0 .. MPE_SMOOTH_MAX_WINDOW); mpe_smooth_reset starts a new sequence, ordered on
+ * `stream`; mpe_smooth_batch is ordered on `stream` and neither synchronises nor allocates: two kernels whatever n_frames
+ * is, the filter and the carry of the last W frames into the other half of the state (one when window == 0;
+ * mpe_smooth_launches counts them as mpe_track_launches does).  n_frames == 0 does nothing.  MPE_ERR_INVALID, with the
+ * values in mpe_last_error: sizes or a pose type other than the state's, lambda outside [0.25, 1], joint_flags outside
+ * {0, 1}, d_poses_out == d_poses; n_frames > 2^23: MPE_ERR_CAPACITY.  Calls on one state belong on one stream, in
+ * sequence order. */
+#define MPE_SMOOTH_MAX_WINDOW 15
+#define MPE_SMOOTH_FILLED 2
+typedef struct mpe_smooth_state mpe_smooth_state;
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    int32_t fill;
+    uint32_t joint_mask;
+    double lambda;                 /* weight ratio of consecutive ages, within [0.25, 1] */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    const int32_t *d_n_persons;    /* [n_frames] */
+    const int32_t *d_track_id;     /* [n_frames][pcap], mpe_track_batch's */
+    void *d_poses_out;             /* the type and shape of d_poses, another buffer */
+    uint8_t *d_flags_out;          /* the shape of d_flags */
+    double *d_vel;                 /* [n_frames][pcap][J][3] */
+    uint8_t *d_n_samples;          /* [n_frames][pcap][J] */
+} mpe_smooth_args;
+int mpe_smooth_create(mpe_ctx *ctx, int32_t pcap, int32_t n_joints, int32_t window, int32_t pose_f64, mpe_smooth_state **out);
+int mpe_smooth_reset(mpe_ctx *ctx, void *stream, mpe_smooth_state *state);
+int mpe_smooth_destroy(mpe_ctx *ctx, mpe_smooth_state *state);
+int mpe_smooth_batch(mpe_ctx *ctx, void *stream, mpe_smooth_state *state, const mpe_smooth_args *a);
+int mpe_smooth_launches(mpe_ctx *ctx, const mpe_smooth_state *state, int64_t *n);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

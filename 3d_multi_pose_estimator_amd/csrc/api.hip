@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "mpe_internal.h"
+#include "assign_int.h"
 
 using namespace mpe;
 
@@ -1481,6 +1482,154 @@ int mpe_smooth_batch(mpe_ctx *ctx, void *stream, mpe_smooth_state *st, const mpe
         return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: NULL argument");
     if (a->d_poses_out == a->d_poses) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: d_poses_out is d_poses (the window reads the raw poses)");
     HIPCHK(ctx, launch_smooth(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
+int mpe_track_score_destroy(mpe_ctx *ctx, mpe_track_score_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    dev_free(ctx, st->totals);
+    dev_free(ctx, st->ident);
+    dev_free(ctx, st->pred_count);
+    dev_free(ctx, st->table);
+    dev_free(ctx, st->rec);
+    dev_free(ctx, st->fstat);
+    dev_free(ctx, st->mmask);
+    dev_free(ctx, st->merr);
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_track_score_create(mpe_ctx *ctx, int32_t pcap, int32_t gcap, int32_t gid_cap, int32_t tid_cap, int32_t max_frames,
+                           mpe_track_score_state **out) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_create: NULL argument");
+    *out = nullptr;
+    if (pcap < 1 || gcap < 1 || gid_cap < 1 || tid_cap < 1 || max_frames < 1)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_create: pcap %d / gcap %d / gid_cap %d / tid_cap %d / max_frames %d, all >= 1", pcap, gcap,
+                    gid_cap, tid_cap, max_frames);
+    if (pcap > MPE_TRACK_MAX_PERSONS || gcap > MPE_TRACK_MAX_PERSONS)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_score_create: pcap %d / gcap %d over %d", pcap, gcap, MPE_TRACK_MAX_PERSONS);
+    if ((int64_t)gid_cap * tid_cap > MPE_TRACK_SCORE_MAX_TABLE)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_score_create: gid_cap %d * tid_cap %d over %d", gid_cap, tid_cap, MPE_TRACK_SCORE_MAX_TABLE);
+    DeviceGuard dg(ctx);
+    mpe_track_score_state *st = new (std::nothrow) mpe_track_score_state();
+    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_track_score_create: out of memory");
+    st->pcap = pcap;
+    st->gcap = gcap;
+    st->gid_cap = gid_cap;
+    st->tid_cap = tid_cap;
+    st->max_frames = max_frames;
+    int rc = dev_alloc(ctx, &st->totals, MPE_TS_TOTALS);
+    if (!rc) rc = dev_alloc(ctx, &st->ident, (size_t)4 * gid_cap);
+    if (!rc) rc = dev_alloc(ctx, &st->pred_count, tid_cap);
+    if (!rc) rc = dev_alloc(ctx, &st->table, (size_t)gid_cap * tid_cap);
+    if (!rc) rc = dev_alloc(ctx, &st->rec, (size_t)max_frames * gid_cap, false);
+    if (!rc) rc = dev_alloc(ctx, &st->fstat, (size_t)max_frames * 8, false);
+    if (!rc) rc = dev_alloc(ctx, &st->mmask, (size_t)max_frames * 2, false);
+    if (!rc) rc = dev_alloc(ctx, &st->merr, (size_t)max_frames * pcap, false);
+    if (!rc && hipMemset(st->ident, 0xFF, gid_cap * sizeof(int32_t)) != hipSuccess)                  // last = -1: no track yet
+        rc = fail(ctx, MPE_ERR_HIP, "mpe_track_score_create: hipMemset failed");
+    if (rc) {
+        const std::string why = ctx->err;
+        mpe_track_score_destroy(ctx, st);
+        ctx->err = why;
+        return rc;
+    }
+    *out = st;
+    return MPE_OK;
+}
+
+int mpe_track_score_reset(mpe_ctx *ctx, void *stream, mpe_track_score_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_reset: NULL state");
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, launch_track_score_reset(static_cast<hipStream_t>(stream), st));
+    return MPE_OK;
+}
+
+int mpe_track_score_launches(mpe_ctx *ctx, const mpe_track_score_state *st, int64_t *n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_launches: NULL argument");
+    *n = st->launches;
+    return MPE_OK;
+}
+
+int mpe_track_score_batch(mpe_ctx *ctx, void *stream, mpe_track_score_state *st, const mpe_track_score_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->pcap != st->pcap || a->gcap != st->gcap)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_batch: pcap %d / gcap %d, the state was made for %d / %d", a->pcap, a->gcap, st->pcap,
+                    st->gcap);
+    if (a->n_frames < 0 || (a->joint_flags & ~1) || !(a->threshold_mm > 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_batch: n_frames %d / joint_flags %d / threshold_mm %g; the threshold is > 0", a->n_frames,
+                    a->joint_flags, a->threshold_mm);
+    if (a->n_frames > st->max_frames)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_score_batch: %d frames, the state was made for %d per call", a->n_frames, st->max_frames);
+    if (a->n_frames == 0) return MPE_OK;
+    if ((!a->joint_flags && !a->d_flags) || !a->d_n_persons || !a->d_track_id || !a->d_assign || !a->d_err || !a->d_n_res || !a->d_n_gt ||
+        !a->d_gt_id || !a->d_gt_valid || !a->d_frame_counts || !a->d_match_tid || !a->d_status)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_batch: NULL argument");
+    HIPCHK(ctx, launch_track_score(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
+int mpe_track_score_read(mpe_ctx *ctx, void *stream, mpe_track_score_state *st, int32_t *h_ident, int32_t *h_pred_count, int32_t *h_table) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_read: NULL state");
+    DeviceGuard dg(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t G = (size_t)st->gid_cap, T = (size_t)st->tid_cap;
+    if (h_ident) HIPCHK(ctx, hipMemcpyAsync(h_ident, st->ident, 4 * G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (h_pred_count) HIPCHK(ctx, hipMemcpyAsync(h_pred_count, st->pred_count, T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (h_table) HIPCHK(ctx, hipMemcpyAsync(h_table, st->table, G * T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return MPE_OK;
+}
+
+int mpe_track_score_result(mpe_ctx *ctx, void *stream, mpe_track_score_state *st, mpe_track_score_totals *out) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !out) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_result: NULL argument");
+    const size_t G = (size_t)st->gid_cap, T = (size_t)st->tid_cap;
+    std::vector<int32_t> ident, pred, table;
+    try {
+        ident.resize(4 * G);
+        pred.resize(T);
+        table.resize(G * T);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, MPE_ERR_NOMEM, "mpe_track_score_result: out of memory");
+    }
+    int64_t tot[MPE_TS_TOTALS];
+    {
+        DeviceGuard dg(ctx);
+        HIPCHK(ctx, hipMemcpyAsync(tot, st->totals, sizeof(tot), hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
+    }
+    const int rc = mpe_track_score_read(ctx, stream, st, ident.data(), pred.data(), table.data());
+    if (rc) return rc;
+    mpe_track_score_totals r{};
+    r.frames = tot[0]; r.n_gt = tot[1]; r.n_pred = tot[2]; r.tp = tot[3]; r.fp = tot[4]; r.fn = tot[5]; r.idsw = tot[6]; r.frag = tot[7];
+    r.ignored = tot[8]; r.over_ids = tot[9];
+    std::memcpy(&r.err_sum, &tot[10], sizeof(double));
+    r.status = (int32_t)tot[11];
+    for (size_t o = 0; o < G; ++o) {
+        const int64_t present = ident[G + o], matched = ident[2 * G + o];
+        if (present <= 0) continue;
+        ++r.n_ids;
+        if (5 * matched >= 4 * present) ++r.mt;
+        else if (5 * matched < present) ++r.ml;
+        else ++r.pt;
+    }
+    for (size_t h = 0; h < T; ++h) r.n_tracks += pred[h] > 0;
+    r.idtp = assign_int_max(table.data(), G, T, T);             // host work, once per recording (assign_int.h)
+    const double nan = std::nan("");
+    r.mota = r.n_gt ? 1.0 - (double)(r.fn + r.fp + r.idsw) / (double)r.n_gt : nan;
+    r.motp_mm = r.tp ? r.err_sum * 1000. / (double)r.tp : nan;
+    r.idp = r.n_pred ? (double)r.idtp / (double)r.n_pred : nan;
+    r.idr = r.n_gt ? (double)r.idtp / (double)r.n_gt : nan;
+    r.idf1 = (r.n_gt + r.n_pred) ? 2.0 * (double)r.idtp / (double)(r.n_gt + r.n_pred) : nan;
+    *out = r;
     return MPE_OK;
 }
 

@@ -201,6 +201,22 @@ struct mpe_smooth_state {
     int32_t *id[2] = {};            // [W][pcap] track id, -1: no detection
 };
 
+// track_score.hip: what mpe_track_score_batch carries from call to call (everything mpe_track_score_result reads back) and
+// the per-call scratch, sized for max_frames frames at create time.
+struct mpe_track_score_state {
+    int pcap = 0, gcap = 0, gid_cap = 0, tid_cap = 0, max_frames = 0;
+    int64_t launches = 0;           // kernels enqueued since mpe_track_score_create
+    int64_t *totals = nullptr;      // [MPE_TS_TOTALS]: the ten int64 totals, err_sum's bits, the sticky status
+    int32_t *ident = nullptr;       // [4][gid_cap]: last, present, matched, bits
+    int32_t *pred_count = nullptr;  // [tid_cap]
+    int32_t *table = nullptr;       // [gid_cap][tid_cap]
+    int32_t *rec = nullptr;         // scratch [max_frames][gid_cap]: h of the frame's record of o, -1 miss, -2 none
+    int32_t *fstat = nullptr;       // scratch [max_frames][8]: tp, fp, fn, ignored, n_gt, n_pred, over_ids, frame counted
+    uint64_t *mmask = nullptr;      // scratch [max_frames][2]: detections that are matches
+    double *merr = nullptr;         // scratch [max_frames * pcap]: their errors, packed in (frame, detection) order
+};
+#define MPE_TS_TOTALS 12
+
 namespace mpe {
 
 // gemm.hip
@@ -350,6 +366,10 @@ hipError_t launch_track(hipStream_t s, mpe_track_state *st, const mpe_track_args
 // smooth.hip
 hipError_t launch_smooth_reset(hipStream_t s, mpe_smooth_state *st);
 hipError_t launch_smooth(hipStream_t s, mpe_smooth_state *st, const mpe_smooth_args &a);
+
+// track_score.hip
+hipError_t launch_track_score_reset(hipStream_t s, mpe_track_score_state *st);
+hipError_t launch_track_score(hipStream_t s, mpe_track_score_state *st, const mpe_track_score_args &a);
 
 // reproject.hip
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);

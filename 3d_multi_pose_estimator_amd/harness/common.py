@@ -29,6 +29,7 @@ from ..pipeline import Engine
 from .assignment import assign_bnb, frame_records
 
 THRESHOLDS_MM = np.arange(25, 155, 25)
+TRACK_SCORE_GCAP = 32          # --track-score: ground-truth rows per frame of the GT tracker and the scorer
 
 
 def build_parser(description):
@@ -65,6 +66,12 @@ def build_parser(description):
                         '--testfiles together are one sequence, in the order given: pass one recording per run')
     p.add_argument('--track-gate', type=float, default=0.5, metavar='M', help='--track: largest mean joint distance of a link, metres')
     p.add_argument('--track-gap', type=int, default=2, metavar='N', help='--track: frames a person may go undetected and keep the identity')
+    p.add_argument('--track-score', action='store_true',
+                   help='implies --track; the track ids are scored against ground-truth identities (mpe_track_score_batch: MOTA, MOTP, '
+                        'IDF1, ID switches, fragmentations, MT/PT/ML), the identities being those a second tracker with the same gate '
+                        'and gap gives the ground-truth bodies, and one further line reports the score')
+    p.add_argument('--track-score-mm', type=float, default=150., metavar='MM',
+                   help='--track-score: a detection matches its ground-truth body below this error (default: the largest AP threshold)')
     p.add_argument('--smooth', type=int, default=0, metavar='W',
                    help='implies --track; the tracked poses are fitted with a line per track and joint over the current frame and the W frames '
                         'before it, 1..15 (mpe_smooth_batch, the state carried across --batch chunks), the fitted poses are scored, and one '
@@ -430,11 +437,12 @@ def evaluate(work, infer, mode, T_i1, batch=256):
     return metrics, n_data, n_results
 
 
-def evaluate_on_device(work, infer, mode, T_i1, batch=256, device_gt=None, T_d_files=None):
+def evaluate_on_device(work, infer, mode, T_i1, batch=256, device_gt=None, T_d_files=None, scored=None):
     """evaluate() with --device-metrics: `infer(frames, owners, gt)` runs the inference path and Engine.evaluate on
     the device and returns its tensors; the frames and the skip rules are evaluate()'s.  With device_gt (a DeviceGT,
     --device-gt) the ground truth of a batch is built on the device from the files' bytes and stays there; only the body
-    counts and the '-1' flags of the batch come back.  Returns (DeviceMetrics, n_data, n_results)."""
+    counts and the '-1' flags of the batch come back.  scored(ev, h): called once per batch with the device tensors and
+    the host records DeviceMetrics.add_batch finished.  Returns (DeviceMetrics, n_data, n_results)."""
     metrics = DeviceMetrics()
     n_data = n_results = 0
     for start in range(0, len(work), batch):
@@ -458,6 +466,8 @@ def evaluate_on_device(work, infer, mode, T_i1, batch=256, device_gt=None, T_d_f
         frames = [{c: [frame[c][0], frame[c][1]] for c in frame if json.loads(frame[c][0])} for frame, _, _ in keep]
         ev = infer(frames, [o for _, _, o in keep], gt)
         h = metrics.add_batch(ev, gt_valid, triangulation=(mode != 'mlp'))
+        if scored is not None:
+            scored(ev, h)
         done = (h['status'] & MPE_EVAL_SKIPPED) == 0
         n_data += int(done.sum())
         n_results += int(h['n_res'][done].sum())
@@ -479,7 +489,8 @@ def run(args, mode):
     device_gt = getattr(args, 'device_gt', False) and not args.synthetic       # synthetic frames have no file to parse
     refine = int(getattr(args, 'refine', 0) or 0)
     smooth = int(getattr(args, 'smooth', 0) or 0)
-    if smooth:
+    track_score = bool(getattr(args, 'track_score', False))
+    if smooth or track_score:
         args.track = True
     if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
         args.device_metrics = True
@@ -494,7 +505,8 @@ def run(args, mode):
     T_i1 = torch.from_numpy(calib.T_i32[1])
     J = eng.J
     t = {'match': 0.0, '3d': 0.0}
-    tracker = summary = smoother = smoothed = None
+    tracker = summary = smoother = smoothed = gt_tracker = scorer = None
+    last = {}                                                # what the track score of a batch needs from infer_device
     refined = []
     if getattr(args, 'track', False):
         from .tracking import TrackSummary
@@ -502,6 +514,10 @@ def run(args, mode):
     if smooth:
         from .smoothing import SmoothSummary
         smoother, smoothed = eng.smoother(mode, window=smooth, decay=args.smooth_decay, fill=args.smooth_fill), SmoothSummary(mode)
+    if track_score:
+        # GT identities: the GT bodies of the evaluated frames through a tracker of their own, same gate and gap
+        gt_tracker = eng.tracker('gt', max_gap=args.track_gap, gate=args.track_gate, pcap=TRACK_SCORE_GCAP)
+        scorer = eng.track_scorer(mode, threshold_mm=args.track_score_mm, gcap=TRACK_SCORE_GCAP)
 
     def infer(frames, owners):
         db = eng.to_device(eng.pack(frames))
@@ -582,7 +598,35 @@ def run(args, mode):
         elif tracker is not None:
             tr = tracker.update(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
+        if scorer is not None:
+            last.update(flags=flags, n_persons=n_persons, ids=tr['ids'])
         return ev
+
+    def score_tracks(ev, h):
+        """refine, track, smooth, evaluate, then this: the batch's frames through the scorer, the ones evaluate skipped
+        marked as such.  Frames the device search declined carry the rows add_batch finished on the host."""
+        dev = last['ids'].device
+        B, P, G = len(h['status']), last['ids'].shape[1], TRACK_SCORE_GCAP
+        gx, gj, gv, gn, _ = ev['_keep']
+        if gx.shape[1] > G:
+            raise RuntimeError('--track-score holds %d ground-truth bodies per frame, a frame has %d' % (G, gx.shape[1]))
+        if (h['status'] & (MPE_EVAL_OVER_CAP | MPE_EVAL_OVER_BUDGET)).any():
+            ev = dict(ev, assign=torch.from_numpy(h['assign']).to(dev), err=torch.from_numpy(h['err']).to(dev))
+        skipped = (h['status'] & MPE_EVAL_SKIPPED) != 0
+        keep = torch.from_numpy(np.flatnonzero(~skipped)).to(dev)
+        if len(keep) != last['ids'].shape[0]:
+            raise RuntimeError('the tracker saw %d frames, the evaluation %d' % (last['ids'].shape[0], len(keep)))
+
+        def padded(t):
+            out = torch.zeros((len(keep), G) + tuple(t.shape[2:]), dtype=t.dtype, device=dev)
+            out[:, :t.shape[1]] = t.index_select(0, keep)
+            return out
+        gt_ids = torch.full((B, G), -1, dtype=torch.int32, device=dev)
+        gt_ids.index_copy_(0, keep, gt_tracker.update(padded(gx), padded(gj), gn.index_select(0, keep))['ids'])
+        gt_valid = torch.zeros((B, G), dtype=torch.uint8, device=dev)
+        gt_valid[:, :gv.shape[1]] = gv
+        ids = torch.full((B, P), -1, dtype=torch.int32, device=dev).index_copy_(0, keep, last['ids'])
+        scorer.update(ev, last['flags'], last['n_persons'], ids, gt_ids, gt_valid, skip=torch.from_numpy(skipped.astype(np.uint8)).to(dev))
 
     if getattr(args, 'device_metrics', False):
         t['eval'] = 0.0
@@ -591,7 +635,8 @@ def run(args, mode):
             dgt = DeviceGT(eng, args.testfiles, src, args.datastep)
             T_d_files = [torch.from_numpy(dataset_transform(args.tmdir[0], file).get_transform('root', parameters.camera_names[1])).type(torch.float32)
                          for file in args.testfiles]
-        metrics, n_data, n_results = evaluate_on_device(work, infer_device, mode, T_i1, args.batch, dgt, T_d_files)
+        metrics, n_data, n_results = evaluate_on_device(work, infer_device, mode, T_i1, args.batch, dgt, T_d_files,
+                                                        score_tracks if scorer is not None else None)
         if dgt is not None:
             print('Ground truth on the device: %d windows, %d redone on the host' % (dgt.windows, dgt.declined))
             gt_windows = (dgt.windows, dgt.declined)
@@ -622,6 +667,12 @@ def run(args, mode):
         print('Smoothed (window %d, decay %g%s): %d joints fitted, %d filled, mean displacement %.3f mm'
               % (smooth, args.smooth_decay, ', fill' if args.smooth_fill else '', r['fitted'], r['filled'], r['mean_move_mm']))
         smoother.close()
+    if scorer is not None:
+        from .track_score import report_line
+        out['track_score'] = scorer.result()
+        print(report_line(out['track_score'], args.track_score_mm))
+        scorer.close()
+        gt_tracker.close()
     out['n_data'] = n_data
     if device_gt:
         out['gt_windows'], out['gt_declined'] = gt_windows

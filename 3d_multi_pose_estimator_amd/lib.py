@@ -97,6 +97,20 @@ class mpe_smooth_args(C.Structure):
                 ('d_poses_out', C.c_void_p), ('d_flags_out', C.c_void_p), ('d_vel', C.c_void_p), ('d_n_samples', C.c_void_p)]
 
 
+class mpe_track_score_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('gcap', C.c_int32), ('joint_flags', C.c_int32), ('threshold_mm', C.c_double),
+                ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p), ('d_assign', C.c_void_p),
+                ('d_err', C.c_void_p), ('d_invalid', C.c_void_p), ('d_n_res', C.c_void_p), ('d_n_gt', C.c_void_p), ('d_gt_id', C.c_void_p),
+                ('d_gt_valid', C.c_void_p), ('d_skip', C.c_void_p), ('d_frame_counts', C.c_void_p), ('d_match_tid', C.c_void_p),
+                ('d_status', C.c_void_p)]
+
+
+class mpe_track_score_totals(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ('frames', 'n_gt', 'n_pred', 'tp', 'fp', 'fn', 'idsw', 'frag', 'ignored', 'over_ids',
+                                         'idtp', 'n_ids', 'n_tracks', 'mt', 'pt', 'ml')] + \
+               [(k, C.c_double) for k in ('err_sum', 'mota', 'motp_mm', 'idp', 'idr', 'idf1')] + [('status', C.c_int32), ('reserved', C.c_int32)]
+
+
 class mpe_reproject_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
                 ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float),
@@ -162,6 +176,9 @@ MPE_TRACK_MAX_PERSONS, MPE_TRACK_MAX_GAP = 128, 15
 # the window cap of mpe_smooth_create and the output flag of a joint that mpe_smooth_batch filled in
 MPE_SMOOTH_MAX_WINDOW, MPE_SMOOTH_FILLED = 15, 2
 
+# the sticky status bit of mpe_track_score_batch and the cap on gid_cap * tid_cap of mpe_track_score_create
+MPE_TRACK_SCORE_OVER_IDS, MPE_TRACK_SCORE_MAX_TABLE = 1, 1 << 22
+
 # per-joint status bits and the iteration cap of mpe_refine_batch
 MPE_REFINE_SOLVED, MPE_REFINE_MOVED, MPE_REFINE_CONVERGED, MPE_REFINE_FEW_VIEWS, MPE_REFINE_BAD_START = 1, 2, 4, 8, 16
 MPE_REFINE_MAX_ITERS = 64
@@ -222,6 +239,13 @@ SYMBOLS = {
     'mpe_smooth_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
     'mpe_smooth_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_smooth_args)]),
     'mpe_smooth_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_track_score_create': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    'mpe_track_score_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_track_score_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_track_score_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_track_score_args)]),
+    'mpe_track_score_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_track_score_result': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_track_score_totals)]),
+    'mpe_track_score_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_args)]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),

@@ -1012,11 +1012,21 @@ class Engine:
         return out
 
     def tracker(self, mode, max_gap=2, gate=0.5, pcap=None):
-        """A Tracker for one sequence of poses in `mode` ('mlp': what mlp3d returns, 'tri': what triangulate returns):
+        """A Tracker for one sequence of poses in `mode` ('mlp': what mlp3d returns, 'tri': what triangulate returns,
+        'gt': ground-truth arrays, f32 poses with per-joint flags and pcap = Gcap):
         person identities over the frames (mpe_track_batch).  A lost person is taken up again after up to `max_gap`
         frames without a detection, within `gate` metres of mean joint distance.  pcap: rows per frame when the poses
         are not this engine's (default: the engine's Pcap)."""
         return Tracker(self, mode, max_gap, gate, self.pcap if pcap is None else int(pcap))
+
+    def track_scorer(self, mode, threshold_mm=150., gid_cap=256, tid_cap=4096, max_frames=None, gcap=None, pcap=None):
+        """A TrackScore for one recording of poses in `mode` ('mlp' or 'tri'): CLEAR-MOT and identity measures of the
+        track ids against ground-truth identities (mpe_track_score_batch).  A detection matches its assigned GT body
+        below threshold_mm.  gid_cap / tid_cap: identities and track ids the tables hold (gid_cap * tid_cap <= 2^22);
+        max_frames: frames per update (default: the engine's); gcap / pcap: GT rows and pose rows per frame (default:
+        the engine's Pcap)."""
+        return TrackScore(self, mode, threshold_mm, gid_cap, tid_cap, self.max_frames if max_frames is None else int(max_frames),
+                          self.pcap if gcap is None else int(gcap), self.pcap if pcap is None else int(pcap))
 
     def smoother(self, mode, window=6, decay=0.8, fill=False, pcap=None):
         """A Smoother for one tracked sequence of poses in `mode` ('mlp' or 'tri', as Engine.tracker takes it): every
@@ -1282,13 +1292,14 @@ class Engine:
 
 class Tracker:
     """Engine.tracker's object: the device state of one sequence (the detections of the last max_gap + 1 frames with
-    their ids, and the id count).  update() takes the frames of the sequence in order, in chunks of any size; the ids
+    their ids, and the id count).  Mode 'gt' takes the ground-truth arrays as they are -- f32 poses [B,Gcap,J,3] with
+    joint flags [B,Gcap,J], pcap = Gcap -- and gives the GT bodies the identities the wire format does not carry.  update() takes the frames of the sequence in order, in chunks of any size; the ids
     do not depend on the chunking.  Everything stays on the device and on the current stream: update() neither
     synchronises nor reads anything back."""
 
     def __init__(self, eng, mode, max_gap, gate, pcap):
-        if mode not in ('mlp', 'tri'):
-            raise ValueError('mode must be mlp or tri')
+        if mode not in ('mlp', 'tri', 'gt'):
+            raise ValueError('mode must be mlp, tri or gt')
         if not gate > 0:
             raise ValueError('gate must be > 0')
         self.eng, self.mode, self.max_gap, self.gate, self.pcap = eng, mode, int(max_gap), float(gate), pcap
@@ -1301,13 +1312,14 @@ class Tracker:
         cost; -1.0 for a birth or no detection), 'gap' [B,Pcap] i32 (frames back to the parent; 0 birth, -1 no
         detection), 'issued' [1] i32 (ids issued so far)}, device tensors."""
         eng, tri = self.eng, self.mode == 'tri'
+        per_joint = self.mode != 'mlp'                   # 'gt': f32 poses like 'mlp', per-joint flags like 'tri'
         if not self.state:
             raise RuntimeError('the tracker is closed')
         B = int(poses.shape[0]) if poses.dim() == 4 else -1
         want = torch.float64 if tri else torch.float32
         if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, eng.J, 3):
             raise ValueError('poses must be %s [B,%d,%d,3]' % (want, self.pcap, eng.J))
-        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if tri else (B, self.pcap)):
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if per_joint else (B, self.pcap)):
             raise ValueError('flags do not match mode %s' % self.mode)
         if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
             raise ValueError('n_persons must be int32 [%d]' % B)
@@ -1325,7 +1337,7 @@ class Tracker:
             self._issued = torch.zeros((1,), dtype=torch.int32, device=dev)
         out['issued'] = self._issued
         a = L.mpe_track_args()
-        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, self.pcap, eng.J, int(tri), int(tri)
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, self.pcap, eng.J, int(tri), int(per_joint)
         a.used_joint_mask = sum(1 << j for j in eng.params.used_joints)
         a.gate = self.gate
         a.d_poses, a.d_flags, a.d_n_persons = poses.data_ptr(), flags.data_ptr(), n_persons.data_ptr()
@@ -1421,6 +1433,97 @@ class Smoother:
     def close(self):
         if getattr(self, 'state', None) and self.eng.ctx:
             self.eng.lib.mpe_smooth_destroy(self.eng.ctx, self.state)
+        self.state = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TrackScore:
+    """Engine.track_scorer's object: the device state of one recording (the totals, the per-identity carry, the
+    identity x track table).  update() takes the frames in order, in chunks of any size; nothing depends on the chunking.
+    Everything stays on the device and on the current stream: update() neither synchronises nor reads anything back;
+    result() does both."""
+
+    def __init__(self, eng, mode, threshold_mm, gid_cap, tid_cap, max_frames, gcap, pcap):
+        if mode not in ('mlp', 'tri'):
+            raise ValueError('mode must be mlp or tri')
+        if not threshold_mm > 0:
+            raise ValueError('threshold_mm must be > 0')
+        self.eng, self.mode, self.threshold_mm = eng, mode, float(threshold_mm)
+        self.gid_cap, self.tid_cap, self.max_frames, self.gcap, self.pcap = int(gid_cap), int(tid_cap), int(max_frames), int(gcap), int(pcap)
+        self.state = C.c_void_p()
+        self._status = torch.zeros((1,), dtype=torch.int32, device=eng.device)
+        eng._chk(eng.lib.mpe_track_score_create(eng.ctx, self.pcap, self.gcap, self.gid_cap, self.tid_cap, self.max_frames, C.byref(self.state)))
+
+    def update(self, ev, flags, n_persons, track_ids, gt_ids, gt_valid, skip=None):
+        """ev: Engine.evaluate's dict for the next B >= 0 frames ('assign', 'err', 'invalid', 'n_res', 'n_gt' are read);
+        flags / n_persons: what Engine.evaluate took; track_ids [B,Pcap] i32: Tracker.update's 'ids' for the same rows;
+        gt_ids [B,Gcap] i32 and gt_valid [B,Gcap] u8: identity (< 0: none) and validity of every GT row; skip [B] u8:
+        frames to leave out.  -> {'frame_counts' [B,4] i32 (tp, fp, fn, idsw), 'match_tid' [B,Gcap] i32 (the matched
+        track, -1 miss, -2 not counted), 'status' [1] i32 (sticky MPE_TRACK_SCORE_OVER_IDS)}, device tensors."""
+        eng, tri = self.eng, self.mode == 'tri'
+        if not self.state:
+            raise RuntimeError('the track scorer is closed')
+        B = int(track_ids.shape[0]) if track_ids.dim() == 2 else -1
+        P, G = self.pcap, self.gcap
+        want = {'flags': (flags, torch.uint8, (B, P, eng.J) if tri else (B, P)), 'n_persons': (n_persons, torch.int32, (B,)),
+                'track_ids': (track_ids, torch.int32, (B, P)), 'gt_ids': (gt_ids, torch.int32, (B, G)),
+                'gt_valid': (gt_valid, torch.uint8, (B, G)), 'assign': (ev['assign'], torch.int32, (B, P)),
+                'err': (ev['err'], torch.float64, (B, P)), 'invalid': (ev['invalid'], torch.uint8, (B, P)),
+                'n_res': (ev['n_res'], torch.int32, (B,)), 'n_gt': (ev['n_gt'], torch.int32, (B,))}
+        if skip is not None:
+            want['skip'] = (skip, torch.uint8, (B,))
+        for k, (t, dt, shape) in want.items():
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != eng.device:
+                raise ValueError('%s must be %s %s, contiguous, on %s' % (k, dt, list(shape), eng.device))
+        dev = eng.device
+        out = {'frame_counts': torch.empty((B, 4), dtype=torch.int32, device=dev),
+               'match_tid': torch.empty((B, G), dtype=torch.int32, device=dev), 'status': self._status}
+        a = L.mpe_track_score_args()
+        a.n_frames, a.pcap, a.gcap, a.joint_flags, a.threshold_mm = B, P, G, int(tri), self.threshold_mm
+        a.d_flags, a.d_n_persons, a.d_track_id = flags.data_ptr(), n_persons.data_ptr(), track_ids.data_ptr()
+        a.d_assign, a.d_err, a.d_invalid = ev['assign'].data_ptr(), ev['err'].data_ptr(), ev['invalid'].data_ptr()
+        a.d_n_res, a.d_n_gt, a.d_gt_id, a.d_gt_valid = ev['n_res'].data_ptr(), ev['n_gt'].data_ptr(), gt_ids.data_ptr(), gt_valid.data_ptr()
+        a.d_skip = skip.data_ptr() if skip is not None else None
+        a.d_frame_counts, a.d_match_tid, a.d_status = out['frame_counts'].data_ptr(), out['match_tid'].data_ptr(), self._status.data_ptr()
+        eng._chk(eng.lib.mpe_track_score_batch(eng.ctx, eng._stream(), self.state, C.byref(a)))
+        return out
+
+    def result(self):
+        """The totals and ratios of the recording so far (synchronises; the IDTP pairing runs on the host) -> dict:
+        frames, n_gt, n_pred, tp, fp, fn, idsw, frag, ignored, over_ids, idtp, n_ids, n_tracks, mt, pt, ml, status
+        (int); err_sum, mota, motp_mm, idp, idr, idf1 (float, NaN for a zero denominator)."""
+        r = L.mpe_track_score_totals()
+        self.eng._chk(self.eng.lib.mpe_track_score_result(self.eng.ctx, self.eng._stream(), self.state, C.byref(r)))
+        return {k: getattr(r, k) for k, _ in r._fields_ if k != 'reserved'}
+
+    def read_state(self):
+        """The per-identity and per-track state (synchronises) -> numpy {'last', 'present', 'matched', 'bits' [gid_cap],
+        'pred_count' [tid_cap], 'table' [gid_cap, tid_cap]} i32."""
+        ident = np.empty((4, self.gid_cap), np.int32)
+        pred, table = np.empty(self.tid_cap, np.int32), np.empty((self.gid_cap, self.tid_cap), np.int32)
+        self.eng._chk(self.eng.lib.mpe_track_score_read(self.eng.ctx, self.eng._stream(), self.state, ident.ctypes.data, pred.ctypes.data,
+                                                        table.ctypes.data))
+        return {'last': ident[0], 'present': ident[1], 'matched': ident[2], 'bits': ident[3], 'pred_count': pred, 'table': table}
+
+    def launches(self):
+        """Kernels this scorer has enqueued so far."""
+        n = C.c_int64()
+        self.eng._chk(self.eng.lib.mpe_track_score_launches(self.eng.ctx, self.state, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Start a new recording (ordered on the current stream)."""
+        self.eng._chk(self.eng.lib.mpe_track_score_reset(self.eng.ctx, self.eng._stream(), self.state))
+        self._status.zero_()
+
+    def close(self):
+        if getattr(self, 'state', None) and self.eng.ctx:
+            self.eng.lib.mpe_track_score_destroy(self.eng.ctx, self.state)
         self.state = None
 
     def __del__(self):

@@ -829,6 +829,90 @@ int mpe_smooth_destroy(mpe_ctx *ctx, mpe_smooth_state *state);
 int mpe_smooth_batch(mpe_ctx *ctx, void *stream, mpe_smooth_state *state, const mpe_smooth_args *a);
 int mpe_smooth_launches(mpe_ctx *ctx, const mpe_smooth_state *state, int64_t *n);
 
+/* Track scoring: how well the track ids follow the ground-truth identities over a recording -- CLEAR-MOT (MOTA, MOTP, ID
+ * switches, fragmentations, MT / PT / ML; Bernardin & Stiefelhagen 2008) and the identity measures IDF1 / IDP / IDR
+ * (Ristani et al. 2016).  The inputs are what mpe_eval_batch and mpe_track_batch left on the device plus one identity
+ * per GT row; every output is an exact integer or one f64 left fold, so there is nothing to tolerate.  The rule
+ * (harness/track_score.py states it in numpy, and the two agree exactly):
+ *   Frames arrive in sequence order, in any chunking.  A frame with d_skip[f] != 0 (d_skip may be NULL) changes neither
+ *   the state nor the frame count; its d_frame_counts are 0 and its d_match_tid are -2.
+ *   Prediction side of frame f: detections and their order are mpe_eval_batch's.  joint_flags == 0: detection r is the
+ *   r-th row p < d_n_persons[f] with d_flags[f][p] != 0; joint_flags == 1: r = p < d_n_persons[f].  Those with
+ *   r < d_n_res[f] exist.  Detection r carries g = d_assign[f][r], e = d_err[f][r] (metres), d_invalid[f][r] (NULL
+ *   pointer: 0) and the track id h = d_track_id[f][p(r)] (row order, as mpe_track_batch writes it).
+ *   GT side: row g < d_n_gt[f] carries o = d_gt_id[f][g] and d_gt_valid[f][g]; it is COUNTED when valid and o >= 0,
+ *   every other row is an IGNORE row.
+ *   Classes: a detection with 0 <= g < d_n_gt[f] whose row is an ignore row is IGNORED and counts nowhere.  A detection
+ *   is a CANDIDATE when g names a counted row, e * 1000. < threshold_mm (f64, strict), it is not invalid and h >= 0; the
+ *   candidate of lowest r of a row is its MATCH (mpe_eval_batch's assignment is one-to-one, so there is one at most).
+ *   Every other detection that is not ignored is a FALSE POSITIVE; a counted row without a match is a MISS.
+ *   Per frame: d_frame_counts[f] = {tp, fp, fn, idsw}; d_match_tid[f][g] = h of the match, -1 for a miss, -2 for a row
+ *   that is not counted (g >= d_n_gt[f] included).
+ *   Identity pass: the RECORD of a counted row is (o, h) or (o, miss).  For every identity o, over the frames with a
+ *   record of o in sequence order: present[o] += 1; with a match: matched[o] += 1, table[o][h] += 1, an ID switch when
+ *   last[o] >= 0 and last[o] != h (it counts in the frame's idsw), then last[o] = h, and a fragmentation when o was
+ *   matched in an earlier frame and its previous record was a miss; last[o] survives misses and absences.
+ *   pred_count[h] += 1 for every detection with h >= 0 that is not ignored.
+ *   Left out, each adding 1 to over_ids and setting the sticky MPE_TRACK_SCORE_OVER_IDS: a record with o >= gid_cap,
+ *   with a matched h >= tid_cap, or whose o a lower counted row of the frame already carries (the identity pass sees
+ *   nothing of it); a pred_count increment with h >= tid_cap.  tp / fp / fn count them all the same.
+ *   Totals (int64, in the state): frames, n_gt (counted rows), n_pred (detections not ignored), tp, fp, fn, idsw, frag,
+ *   ignored, over_ids.  err_sum: the f64 left fold of e over the matches in (frame, detection) order, every addition
+ *   rounded on its own, continued from call to call.
+ * mpe_track_score_create allocates all device memory the calls need: the state, table[gid_cap][tid_cap] and a scratch of
+ * max_frames frames (MPE_ERR_CAPACITY for pcap or gcap > MPE_TRACK_MAX_PERSONS or gid_cap * tid_cap > 2^22).
+ * mpe_track_score_reset starts a new recording, ordered on `stream`.  mpe_track_score_batch is ordered on `stream` and
+ * neither synchronises nor allocates: three kernels whatever n_frames is (mpe_track_score_launches counts them as
+ * mpe_track_launches does); n_frames == 0 does nothing.  MPE_ERR_INVALID: pcap / gcap other than the state's,
+ * joint_flags outside {0, 1}, threshold_mm <= 0; MPE_ERR_CAPACITY: n_frames > max_frames.  *d_status receives the sticky
+ * bits.  Calls on one state belong on one stream, in sequence order.
+ * mpe_track_score_result is the only call that synchronises (`stream`): it reads the state back and finishes on the
+ * host.  MOTA = 1 - (fn + fp + idsw) / n_gt; MOTP_mm = err_sum * 1000 / tp; IDTP = the largest sum of table over
+ * one-to-one pairings of identities and tracks (an exact integer; once per recording, on the host: csrc/assign_int.h);
+ * IDP = IDTP / n_pred, IDR = IDTP / n_gt, IDF1 = 2 IDTP / (n_gt + n_pred); an identity with present > 0 is mostly
+ * tracked when 5 * matched >= 4 * present, mostly lost when 5 * matched < present, partially tracked otherwise;
+ * n_ids = identities with present > 0, n_tracks = tracks with pred_count > 0.  A ratio with a zero denominator is NaN. */
+#define MPE_TRACK_SCORE_OVER_IDS 1
+#define MPE_TRACK_SCORE_MAX_TABLE (1 << 22)
+typedef struct mpe_track_score_state mpe_track_score_state;
+typedef struct {
+    int32_t n_frames, pcap, gcap;
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8 (f32 poses' person flags); 1: not read, r = p */
+    double threshold_mm;           /* > 0 */
+    const uint8_t *d_flags;        /* joint_flags == 0 only */
+    const int32_t *d_n_persons;    /* [n_frames] */
+    const int32_t *d_track_id;     /* [n_frames][pcap], mpe_track_batch's */
+    const int32_t *d_assign;       /* [n_frames][pcap], mpe_eval_batch's (detection order), as d_err and d_invalid */
+    const double *d_err;           /* [n_frames][pcap] */
+    const uint8_t *d_invalid;      /* [n_frames][pcap] or NULL */
+    const int32_t *d_n_res;        /* [n_frames] */
+    const int32_t *d_n_gt;         /* [n_frames] */
+    const int32_t *d_gt_id;        /* [n_frames][gcap] */
+    const uint8_t *d_gt_valid;     /* [n_frames][gcap] */
+    const uint8_t *d_skip;         /* [n_frames] or NULL */
+    int32_t *d_frame_counts;       /* [n_frames][4] */
+    int32_t *d_match_tid;          /* [n_frames][gcap] */
+    int32_t *d_status;             /* [1] */
+} mpe_track_score_args;
+typedef struct {
+    int64_t frames, n_gt, n_pred, tp, fp, fn, idsw, frag, ignored, over_ids;
+    int64_t idtp, n_ids, n_tracks, mt, pt, ml;
+    double err_sum, mota, motp_mm, idp, idr, idf1;
+    int32_t status, reserved;
+} mpe_track_score_totals;
+int mpe_track_score_create(mpe_ctx *ctx, int32_t pcap, int32_t gcap, int32_t gid_cap, int32_t tid_cap, int32_t max_frames,
+                           mpe_track_score_state **out);
+int mpe_track_score_reset(mpe_ctx *ctx, void *stream, mpe_track_score_state *state);
+int mpe_track_score_destroy(mpe_ctx *ctx, mpe_track_score_state *state);
+int mpe_track_score_batch(mpe_ctx *ctx, void *stream, mpe_track_score_state *state, const mpe_track_score_args *a);
+int mpe_track_score_launches(mpe_ctx *ctx, const mpe_track_score_state *state, int64_t *n);
+int mpe_track_score_result(mpe_ctx *ctx, void *stream, mpe_track_score_state *state, mpe_track_score_totals *out);
+/* The per-identity and per-track state as it stands, to host arrays (any may be NULL); synchronises `stream`.
+ * h_ident [4][gid_cap]: last, present, matched, bits (1: matched in some frame, 2: the previous record was a miss);
+ * h_pred_count [tid_cap]; h_table [gid_cap][tid_cap]. */
+int mpe_track_score_read(mpe_ctx *ctx, void *stream, mpe_track_score_state *state, int32_t *h_ident, int32_t *h_pred_count,
+                         int32_t *h_table);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

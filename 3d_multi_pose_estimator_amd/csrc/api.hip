@@ -1263,7 +1263,8 @@ int mpe_mlp3d_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const int32_
     const int n_out = ctx->mlp[ctx->mlp_layers - 1].out_dim;
     if (n_out != ctx->cfg.n_joints * 3)
         return fail(ctx, MPE_ERR_INVALID, "MLP output width %d != 3*J", n_out);
-    // small batches: the persons' prefix inside the row kernel, the decode inside the last layer's launch (two launches fewer)
+    // the decode rides in the last layer's launch wherever that launch has the epilogue (the K-split kernel: 54 features are four
+    // column tiles at any batch size); small batches: the persons' prefix inside the row kernel as well
     const bool small = latency_path_on() && b->n_frames <= LAT_MAX_FRAMES;
     if (small) {
         // the batch whose pairs mpe_match_batch left solved (same input arrays, same sizes)?  then the row kernel fetches them
@@ -1276,14 +1277,16 @@ int mpe_mlp3d_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const int32_
                                     ctx->cfg.max_heads_per_frame));
     } else {
         HIPCHK(ctx, launch_person_scan(s, b->n_frames, pcap, d_n_persons, ctx->person_off, ctx->mlp_count));
+        // (the row kernel zeroes the pose slots nobody fills, as on the small-batch route: the last layer's launch decodes the rest)
         HIPCHK(ctx, launch_mlp_rows(s, ctx->d_cfg, ctx->cfg.n_cameras, ctx->cfg.n_joints, *b, d_persons, d_n_persons,
-                                    ctx->person_off, pcap, ctx->mlp_rows, ctx->mlp_ld_in, d_valid ? d_valid : ctx->valid_tmp));
+                                    ctx->person_off, pcap, ctx->mlp_rows, ctx->mlp_ld_in, d_valid ? d_valid : ctx->valid_tmp, nullptr, nullptr,
+                                    d_poses, n_out));
     }
     float *y;
     int ldy;
     const DecodeEpi dec{ctx->person_off, b->n_frames, pcap, n_out, 10.f, d_poses};
     bool decoded = false;
-    if ((rc = mlp_chain(ctx, s, ctx->mlp_rows, ctx->mlp_ld_in, b->n_frames * pcap, ctx->mlp_count, &y, &ldy, small ? &dec : nullptr, &decoded))) return rc;
+    if ((rc = mlp_chain(ctx, s, ctx->mlp_rows, ctx->mlp_ld_in, b->n_frames * pcap, ctx->mlp_count, &y, &ldy, &dec, &decoded))) return rc;
     if (!decoded) HIPCHK(ctx, launch_decode(s, b->n_frames, pcap, n_out, 10.f, d_n_persons, ctx->person_off, y, ldy, d_poses));
     return MPE_OK;
 }

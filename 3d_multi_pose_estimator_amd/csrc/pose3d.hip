@@ -8,10 +8,10 @@
 // and the two OpenCV calls they make, restated from OpenCV's published algorithms in f64:
 //   cv2.undistortPoints  : normalise with K, 5 fixed-point iterations of the k1,k2,p1,p2,k3 model
 //   cv2.triangulatePoints: 4x4 DLT system, right singular vector of the smallest singular
-//                          value (here: one-sided Jacobi SVD in registers).
+//                          value (dlt_solve.h: one-sided Jacobi on the rows, in registers).
 // One workgroup per (frame, person); pair solves are spread over the lanes, sums run in the
 // reference's pair order.  f64 arithmetic is kept un-contracted (no fma fusion) to stay as
-// close as possible to the CPU evaluation order, except inside the Jacobi SVD (an iteration to
+// close as possible to the CPU evaluation order, except inside the Jacobi solve (an iteration to
 // convergence whose result does not depend on the rounding of single steps beyond a few ulp).
 #include "mpe_internal.h"
 #include "dlt_common.h"

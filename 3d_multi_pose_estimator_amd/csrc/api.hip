@@ -806,6 +806,8 @@ int mpe_create(const mpe_config *cfg, mpe_ctx **out) {
         if ((rc = dev_alloc(ctx, &ctx->cl_scratch, ctx->cl_scratch_per_frame * cfg->max_frames, false))) break;
         if ((rc = dev_alloc(ctx, &ctx->mlp_count, 1))) break;
         if ((rc = dev_alloc(ctx, &ctx->scores_tmp, (size_t)cfg->max_edge_nodes))) break;
+        if (geom_needs_table(cfg->max_heads_per_frame, cfg->n_joints) &&
+            (rc = dev_alloc(ctx, &ctx->geom_rays, geom_table_doubles(cfg->max_heads, cfg->n_joints), false))) break;
         if ((rc = dev_alloc(ctx, &ctx->person_off, (size_t)cfg->max_frames + 1))) break;
         if ((rc = dev_alloc(ctx, &ctx->valid_tmp, (size_t)cfg->max_frames * cfg->max_persons_per_frame))) break;
     } while (0);
@@ -1667,6 +1669,48 @@ int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_r
         !a->d_iters || !a->d_n_views)
         return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: NULL argument");
     HIPCHK(ctx, launch_refine(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
+    return MPE_OK;
+}
+
+static int geom_checks(mpe_ctx *ctx, const mpe_geom_args *a, const char *who) {
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "%s: NULL argument", who);
+    if (!(a->sigma_m > 0.0) || !(a->clip_m >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "%s: sigma_m %g must be positive and clip_m %g must not be negative", who, a->sigma_m, a->clip_m);
+    if (a->min_joints < 1 || a->min_joints > ctx->cfg.n_joints)
+        return fail(ctx, MPE_ERR_INVALID, "%s: min_joints %d outside 1..%d", who, a->min_joints, ctx->cfg.n_joints);
+    if (!(a->min_conf >= 0.0f)) return fail(ctx, MPE_ERR_INVALID, "%s: min_conf %g must not be negative", who, (double)a->min_conf);
+    return MPE_OK;
+}
+
+int mpe_geom_scores_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_geom_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    DeviceGuard dg(ctx);
+    if ((rc = geom_checks(ctx, a, "mpe_geom_scores_batch"))) return rc;
+    if (b->n_frames == 0) return MPE_OK;
+    if (!a->d_scores) return fail(ctx, MPE_ERR_INVALID, "mpe_geom_scores_batch: NULL output");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((rc = gat_topology(ctx, s, b))) return rc;
+    HIPCHK(ctx, launch_geom(s, ctx->d_cfg, ctx->cfg.n_cameras, ctx->cfg.n_joints, *b, ctx->en_pair, ctx->cfg.max_heads_per_frame, ctx->x_m_cap,
+                            *a, a->d_scores, ctx->geom_rays));
+    return MPE_OK;
+}
+
+int mpe_geom_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_geom_args *a, int32_t *d_persons,
+                         int32_t *d_n_persons) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    DeviceGuard dg(ctx);
+    if ((rc = geom_checks(ctx, a, "mpe_geom_match_batch"))) return rc;
+    if (b->n_frames == 0) return MPE_OK;
+    if (!d_persons || !d_n_persons) return fail(ctx, MPE_ERR_INVALID, "mpe_geom_match_batch: NULL output");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *scores = a->d_scores ? a->d_scores : ctx->scores_tmp;
+    if ((rc = gat_topology(ctx, s, b))) return rc;
+    HIPCHK(ctx, launch_geom(s, ctx->d_cfg, ctx->cfg.n_cameras, ctx->cfg.n_joints, *b, ctx->en_pair, ctx->cfg.max_heads_per_frame, ctx->x_m_cap,
+                            *a, scores, ctx->geom_rays));
+    HIPCHK(ctx, launch_cluster(s, ctx->d_cfg, *b, ctx->en_pair, scores, ctx->cfg.max_persons_per_frame, ctx->cfg.max_heads_per_frame,
+                               ctx->cl_keys, ctx->cl_keys_per_frame, ctx->cl_scratch, ctx->cl_scratch_per_frame, d_persons, d_n_persons));
     return MPE_OK;
 }
 

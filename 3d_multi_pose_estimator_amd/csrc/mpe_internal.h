@@ -161,6 +161,7 @@ struct mpe_ctx {
     float *mlp_act[2] = {nullptr, nullptr};
     int32_t *mlp_count = nullptr;
     float *scores_tmp = nullptr;    // [max_edge_nodes]
+    double *geom_rays = nullptr;    // mpe_geom_scores_batch: [max_heads][3 J + 1] head records, only where a frame's records do not fit LDS (geom.hip)
     int32_t *person_off = nullptr;  // [max_frames+1]
     uint8_t *valid_tmp = nullptr;   // [max_frames*Pcap]
     std::vector<void *> owned;     // everything to hipFree at destroy
@@ -375,6 +376,12 @@ hipError_t launch_track_score(hipStream_t s, mpe_track_score_state *st, const mp
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);
 // refine.hip
 hipError_t launch_refine(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_refine_args &a);
+// geom.hip: en_pair = the context's pair table (launch_topology); ray_table only when geom_needs_table()
+constexpr size_t GEOM_LDS_BYTES = 48 * 1024;     // head records of a frame staged in LDS up to this (three 256-thread workgroups per CU's 160 KiB)
+bool geom_needs_table(int max_heads_per_frame, int J);
+size_t geom_table_doubles(int max_heads, int J);
+hipError_t launch_geom(hipStream_t s, const DevCfg *cfg, int V, int J, const mpe_batch &b, const int32_t *en_pair, int max_heads_per_frame,
+                       int x_m_cap, const mpe_geom_args &a, float *scores, double *ray_table);
 // partition.hip
 hipError_t launch_partition_labels(hipStream_t s, int V, const mpe_batch &b, const mpe_partition_labels_args &a);
 hipError_t launch_group_bodies(hipStream_t s, const mpe_group_bodies_args &a);

@@ -45,6 +45,14 @@ def build_parser(description):
     p.add_argument('--random-weights', action='store_true', help='deterministic hash-initialised weights (no checkpoint offline)')
     p.add_argument('--teacher-scores', action='store_true',
                    help='synthetic frames only: replace the GAT scores by the ground-truth pairing (isolates the 3D stage)')
+    p.add_argument('--matcher', choices=['gat', 'geometric'], default='gat',
+                   help='geometric: the matching scores come from the calibration alone (mpe_geom_match_batch: distance between the back-projected '
+                        'rays of two skeletons); no skeleton-matching model is loaded and one further line reports the matcher.  '
+                        '--teacher-scores keeps precedence')
+    p.add_argument('--geom-sigma', type=float, default=0.10, metavar='M', help='--matcher geometric: mean ray distance that scores 0.5, metres')
+    p.add_argument('--geom-clip', type=float, default=0.5, metavar='M', help='--matcher geometric: largest distance a joint contributes, metres (0: no clip)')
+    p.add_argument('--geom-min-joints', type=int, default=1, metavar='N', help='--matcher geometric: common joints a pair needs to score at all')
+    p.add_argument('--geom-min-conf', type=float, default=0.0, metavar='C', help='--matcher geometric: detection confidence a joint needs in both views')
     p.add_argument('--noise-px', type=float, default=0.0)
     p.add_argument('--persons', type=int, default=4)
     p.add_argument('--gat-acc64', action='store_true',
@@ -87,12 +95,45 @@ def build_parser(description):
     return p
 
 
+def geom_options(args):
+    """The options of Engine.geom_match under --matcher geometric, else None."""
+    if getattr(args, 'matcher', 'gat') != 'geometric':
+        return None
+    return dict(sigma=args.geom_sigma, clip=args.geom_clip, min_joints=args.geom_min_joints, min_conf=args.geom_min_conf)
+
+
+def match_stage(eng, args, db):
+    """The matching stage of the scripts -> (persons, n_persons): the GAT, or the ray distances under --matcher geometric."""
+    opts = geom_options(args)
+    if opts is not None:
+        return eng.geom_match(db, want_scores=False, **opts)[1:]
+    return eng.match(db, want_scores=False)[1:]
+
+
+def report_matcher(args):
+    """The further report line of --matcher geometric."""
+    opts = geom_options(args)
+    if opts is not None:
+        from .geometric import report_line
+        print(report_line(opts))
+    return opts
+
+
 def load_models(eng, args, need_mlp):
     """skeleton_matching.prms/.tch and pose_estimator.pytorch (metrics_from_model.py:89-100),
-    or deterministic weights when none are available."""
+    or deterministic weights when none are available.  --matcher geometric loads no skeleton-matching model."""
     V, J = eng.V, eng.J
     nf = 2 + V * J * 10
     mdir = args.modelsdir if args.modelsdir.endswith('/') else args.modelsdir + '/'
+    if geom_options(args) is not None:
+        if need_mlp:
+            if args.random_weights or not os.path.exists(mdir + 'pose_estimator.pytorch'):
+                if not args.random_weights:
+                    print('no pose_estimator.pytorch under %s: using deterministic random weights' % mdir)
+                eng.load_mlp(synthetic.mlp_state_dict(11, V * J * parameters.numbers_per_joint))
+            else:
+                eng.load_mlp(torch.load(mdir + 'pose_estimator.pytorch', map_location='cpu')['model_state_dict'])
+        return
     if args.random_weights or not os.path.exists(mdir + 'skeleton_matching.tch'):
         if not args.random_weights:
             print('no model files under %s: using deterministic random weights' % mdir)
@@ -526,7 +567,7 @@ def run(args, mode):
         if args.teacher_scores and owners[0] is not None:
             persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
         else:
-            _, persons, n_persons = eng.match(db, want_scores=False)
+            persons, n_persons = match_stage(eng, args, db)
         torch.cuda.synchronize()
         t1 = time.time()
         if mode == 'mlp':
@@ -562,7 +603,7 @@ def run(args, mode):
         if args.teacher_scores and owners[0] is not None:
             persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
         else:
-            _, persons, n_persons = eng.match(db, want_scores=False)
+            persons, n_persons = match_stage(eng, args, db)
         torch.cuda.synchronize()
         t1 = time.time()
         if mode == 'mlp':
@@ -644,6 +685,8 @@ def run(args, mode):
     else:
         metrics, n_data, n_results = evaluate(work, infer, mode, T_i1, args.batch)
     out = metrics.report()
+    if report_matcher(args) is not None:
+        out['matcher'] = dict(geom_options(args), name='geometric')
     if n_data > 0:
         print('Mean time for graph matching', t['match'] / n_data)
         print('Mean time for graph matching (per person)', t['match'] / max(1, n_results))

@@ -37,7 +37,7 @@ from ..calibration import Calibration
 from ..parameters import parameters
 from ..pipeline import Engine
 from . import reprojection as R
-from .common import build_parser, dataset_transform, load_models, pack_ground_truth, teacher_scores
+from .common import build_parser, dataset_transform, load_models, match_stage, pack_ground_truth, report_matcher, teacher_scores
 
 
 def project(calib, cam_idx, p3d):
@@ -258,7 +258,7 @@ def run(args):
         if args.teacher_scores and owners[0] is not None:
             persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
         else:
-            _, persons, n_persons = eng.match(db, want_scores=False)
+            persons, n_persons = match_stage(eng, args, db)
         poses, valid = eng.mlp3d(db, persons, n_persons)
         # the script's own gather keeps joints whose id is > 0 (reprojection_error.py:296-300)
         tri, jv = eng.triangulate(db, persons, n_persons, all_joints=True, positive_ids_only=True)
@@ -281,7 +281,7 @@ def run(args):
         if args.teacher_scores and owners[0] is not None:
             persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
         else:
-            _, persons, n_persons = eng.match(db, want_scores=False)
+            persons, n_persons = match_stage(eng, args, db)
         poses, valid = eng.mlp3d(db, persons, n_persons)
         tri, jv = eng.triangulate(db, persons, n_persons, all_joints=True, positive_ids_only=True)
         return db, persons, n_persons, poses, valid, tri, jv
@@ -299,6 +299,9 @@ def run(args):
         out = evaluate_arrays(work, infer_arrays, calib, True, args.batch)
     else:
         out = evaluate(work, infer, calib, args.batch)
+    opts = report_matcher(args)
+    if opts is not None:
+        out['matcher'] = dict(opts, name='geometric')
     eng.close()
     return out
 

@@ -28,7 +28,7 @@ from ..calibration import Calibration
 from ..parameters import parameters
 from ..pipeline import Engine
 from . import partition as P
-from .common import build_parser, load_models, teacher_scores
+from .common import build_parser, load_models, match_stage, report_matcher, teacher_scores
 
 
 def gt_labels(frame):
@@ -207,7 +207,7 @@ def run(args):
         if args.teacher_scores and owners[0] is not None:
             persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
         else:
-            _, persons, n_persons = eng.match(db, want_scores=False)
+            persons, n_persons = match_stage(eng, args, db)
         eng.sync_status()
         persons, n_persons = persons.cpu().numpy(), n_persons.cpu().numpy()
         out = []
@@ -224,7 +224,7 @@ def run(args):
         if args.teacher_scores and owners[0] is not None:
             persons, n_persons = eng.cluster(db, teacher_scores(db, owners))
         else:
-            _, persons, n_persons = eng.match(db, want_scores=False)
+            persons, n_persons = match_stage(eng, args, db)
         B = len(frames)
         H = np.diff(np.asarray(db.host.frame_head_off[:B + 1]))
         M = np.diff(np.asarray(db.host.frame_en_off[:B + 1]))
@@ -246,6 +246,9 @@ def run(args):
             dgt.close()
     else:
         out = evaluate(work, infer, args.batch)
+    opts = report_matcher(args)
+    if opts is not None:
+        out['matcher'] = dict(opts, name='geometric')
     eng.close()
     return out
 

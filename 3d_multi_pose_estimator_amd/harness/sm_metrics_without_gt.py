@@ -26,7 +26,7 @@ from ..calibration import Calibration
 from ..graph_generator import MergedMultipleHumansDataset, batch
 from ..parameters import parameters
 from ..pipeline import Engine, explicit_m_cap
-from .common import build_parser, load_models
+from .common import build_parser, load_models, match_stage, report_matcher
 
 CLASSIFICATION_THRESHOLD = 0.5
 
@@ -44,7 +44,7 @@ def labels_of(persons_row, n_persons, H):
     return out
 
 
-def evaluate_on_device(dataset, eng, batch_graphs=64):
+def evaluate_on_device(dataset, eng, batch_graphs=64, match=None):
     """evaluate() with --device-metrics: both proposal sets become labels in Engine.partition_labels and are scored by
     Engine.partition_scores (harness/partition.py states the arithmetic); one [B,4] array per batch comes back for the
     totals, which are added here in graph order, and the proposals themselves for `per_graph`."""
@@ -57,7 +57,7 @@ def evaluate_on_device(dataset, eng, batch_graphs=64):
         items = [dataset[i] for i in range(start, min(len(dataset), start + batch_graphs))]
         g = batch([it[0] for it in items])
         db = g.device_batch(eng)
-        _, persons, n_persons = eng.match(db, want_scores=False)
+        persons, n_persons = match(db) if match else eng.match(db, want_scores=False)[1:]
         lab = torch.cat([it[1].reshape(-1) for it in items]).to(torch.float32)
         gt_persons, gt_n = eng.cluster(db, lab)
         hcap = max([1] + [int(H) for H in g.batch_num_heads])
@@ -83,7 +83,7 @@ def evaluate_on_device(dataset, eng, batch_graphs=64):
     return out
 
 
-def evaluate(dataset, eng, batch_graphs=64):
+def evaluate(dataset, eng, batch_graphs=64, match=None):
     from sklearn.metrics import adjusted_rand_score, homogeneity_completeness_v_measure
     tot = {'rand score': 0.0, 'homogeneity': 0.0, 'completeness': 0.0, 'v_measure': 0.0}
     n_data = 0
@@ -92,7 +92,7 @@ def evaluate(dataset, eng, batch_graphs=64):
         items = [dataset[i] for i in range(start, min(len(dataset), start + batch_graphs))]
         g = batch([it[0] for it in items])
         db = g.device_batch(eng)
-        _, persons, n_persons = eng.match(db, want_scores=False)
+        persons, n_persons = match(db) if match else eng.match(db, want_scores=False)[1:]
         # the true grouping: the same proposal function on the labels used as scores (:143-147)
         lab = torch.cat([it[1].reshape(-1) for it in items]).to(torch.float32)
         gt_persons, gt_n = eng.cluster(db, lab)
@@ -139,7 +139,10 @@ def run(args):
     eng = Engine(parameters, Calibration(parameters), max_frames=B, max_heads_per_frame=hpf, max_edge_nodes_per_frame=mmax,
                  threshold=CLASSIFICATION_THRESHOLD)
     load_models(eng, args, need_mlp=False)
-    out = (evaluate_on_device if getattr(args, 'device_metrics', False) else evaluate)(dataset, eng, B)
+    out = (evaluate_on_device if getattr(args, 'device_metrics', False) else evaluate)(dataset, eng, B, lambda db: match_stage(eng, args, db))
+    opts = report_matcher(args)
+    if opts is not None:
+        out['matcher'] = dict(opts, name='geometric')
     eng.close()
     return out
 

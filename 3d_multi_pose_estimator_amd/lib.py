@@ -127,6 +127,11 @@ class mpe_refine_args(C.Structure):
                 ('d_iters', C.c_void_p), ('d_n_views', C.c_void_p)]
 
 
+class mpe_geom_args(C.Structure):
+    _fields_ = [('sigma_m', C.c_double), ('clip_m', C.c_double), ('min_joints', C.c_int32), ('joint_mask', C.c_uint32),
+                ('min_conf', C.c_float), ('d_scores', C.c_void_p), ('d_n_votes', C.c_void_p), ('d_mean', C.c_void_p)]
+
+
 class mpe_residual_stats_args(C.Structure):
     _fields_ = [('n_buffers', C.c_int32), ('n_joints', C.c_int32), ('d_res', C.POINTER(C.c_void_p)), ('n_groups', C.POINTER(C.c_int64)),
                 ('d_count', C.c_void_p), ('d_nonfinite', C.c_void_p), ('d_sum', C.c_void_p), ('d_mid', C.c_void_p)]
@@ -248,6 +253,8 @@ SYMBOLS = {
     'mpe_track_score_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_args)]),
+    'mpe_geom_scores_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args)]),
+    'mpe_geom_match_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args), C.c_void_p, C.c_void_p]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),
     'mpe_partition_labels': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_partition_labels_args)]),
     'mpe_group_bodies': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_group_bodies_args)]),

@@ -202,7 +202,8 @@ class Engine:
         """Native (C++) packer: JSON text of a list of frames -> PackedBatch."""
         return pack_json(text, self.params, frame_start, frame_step, max_frames, n_threads)
 
-    def stream_json(self, text, chunk_frames=None, mode='mlp', frame_step=1, n_threads=0, parser='device', contexts=1):
+    def stream_json(self, text, chunk_frames=None, mode='mlp', frame_step=1, n_threads=0, parser='device', contexts=1, matcher='gat',
+                    geom=None):
         """Frame JSON (bytes, the reference's wire format) -> 3D poses, chunk by chunk, with the
         host side off the critical path: the native packer parses chunk i+1 straight into a
         page-locked arena (worker thread; the C call releases the GIL) while chunk i is copied to
@@ -223,8 +224,10 @@ class Engine:
         offsets, test with isinstance if you need the host arrays).  A chunk holding a shape
         the device parser leaves to the host (literals, nested values, numbers beyond the exact fast path)
         is packed by the host packer instead -- same arrays either way.  parser = 'host': the round-2 path.
-        contexts = 2 (device parser only): windows take turns on two contexts (sibling()), two windows in flight."""
+        contexts = 2 (device parser only): windows take turns on two contexts (sibling()), two windows in flight.
+        matcher = 'geometric': geom_match (options in the dict `geom`) in the place of match; no GAT weights are needed."""
         from concurrent.futures import ThreadPoolExecutor
+        match_stage = self._match_stage(matcher, geom)
         if isinstance(text, str):
             text = text.encode()
         B = int(chunk_frames or self.max_frames)
@@ -240,7 +243,7 @@ class Engine:
                                    'first, or use a second Engine / Engine.sibling()')
             self._json_busy = True
             try:
-                yield from self._stream_json_device(text, B, mode, frame_step, n_threads, contexts)
+                yield from self._stream_json_device(text, B, mode, frame_step, n_threads, contexts, match_stage)
             finally:
                 self._json_busy = False
             return
@@ -275,7 +278,7 @@ class Engine:
                 db = dbs[k].rebind(pb)
                 dev[k].buf.copy_(host[k].buf, non_blocking=True)
                 uploaded[k].record()
-                _, persons, n_persons = self.match(db, want_scores=False)
+                _, persons, n_persons = match_stage(self, db)
                 poses = (self.mlp3d(db, persons, n_persons) if mode == 'mlp' else self.triangulate(db, persons, n_persons))[0]
                 out[k][0][:pb.n_frames].copy_(poses, non_blocking=True)
                 out[k][1][:pb.n_frames].copy_(n_persons, non_blocking=True)
@@ -300,11 +303,12 @@ class Engine:
             pool.shutdown(wait=True)
             index.close()
 
-    def _stream_json_device(self, text, B, mode, frame_step, n_threads, contexts=1):
+    def _stream_json_device(self, text, B, mode, frame_step, n_threads, contexts=1, match_stage=None):
         from concurrent.futures import ThreadPoolExecutor
         import os
         import time
         t_call = time.perf_counter()
+        match_stage = match_stage or self._match_stage('gat', None)
         H = B * self.hpf
         # page-locked staging, the device arenas, the page-locked result buffers and the streams are kept with the engine:
         # allocating and pinning ~150 MB per call cost more than parsing a few windows
@@ -473,7 +477,7 @@ class Engine:
                 if db.host is not None:
                     l_m.wait_stream(cur)                     # host-packed window: its upload went over the caller's stream
                 with torch.cuda.stream(l_m):
-                    _, persons, n_persons = eng.match(db, want_scores=False)
+                    _, persons, n_persons = match_stage(eng, db)
                     ev_m = torch.cuda.Event()
                     ev_m.record()
                 with torch.cuda.stream(l_d):
@@ -700,7 +704,7 @@ class Engine:
         out['_keep'] = (Td_d, fof_d, ec, en)
         return out
 
-    def run_pipelined(self, batches, mode='mlp', contexts=1):
+    def run_pipelined(self, batches, mode='mlp', contexts=1, matcher='gat', geom=None):
         """Batches (DeviceBatch or PackedBatch) -> (poses, n_persons, persons) per batch, in order.
 
         contexts == 1: the two stages on their own streams: the matching stage of batch i+1 (GAT workspace) runs while
@@ -709,7 +713,9 @@ class Engine:
         batches).  contexts == K > 1: K contexts (sibling()) take turns on the batches, each on its own stream, so K whole
         batches are in flight (195.6 k against 186-189 k frames/s at K = 2; K = 3: 194.7 k).  Either way the results are
         the same bits as match() + mlp3d() / triangulate() called one after the other.  Each result is yielded once its
-        3D stage has finished (with K contexts: when K - 1 later batches have been queued)."""
+        3D stage has finished (with K contexts: when K - 1 later batches have been queued).
+        matcher = 'geometric': geom_match (options in the dict `geom`) in the place of match; no GAT weights are needed."""
+        match_stage = self._match_stage(matcher, geom)
         K = max(1, int(contexts))
         engs = self.contexts(K)
         two = K == 1
@@ -725,7 +731,7 @@ class Engine:
                 # before its matching stage -- per batch, not once in front of the loop
                 sm.wait_stream(cur)
                 with torch.cuda.stream(sm):
-                    _, persons, n_persons = e.match(db, want_scores=False)
+                    _, persons, n_persons = match_stage(e, db)
                     ev = torch.cuda.Event()
                     ev.record(sm)
                 with torch.cuda.stream(sd):
@@ -808,6 +814,51 @@ class Engine:
         self._chk(self.lib.mpe_match_batch(self.ctx, self._stream(), C.byref(db.struct),
                                            _ptr(scores), _ptr(persons), _ptr(n_persons)))
         return (scores[:db.n_edge_nodes] if want_scores else None), persons, n_persons
+
+    def _geom_args(self, sigma, clip, min_joints, joint_mask, min_conf):
+        a = L.mpe_geom_args()
+        a.sigma_m, a.clip_m, a.min_joints = float(sigma), float(clip), int(min_joints)
+        a.joint_mask, a.min_conf = int(joint_mask or 0), float(min_conf)
+        return a
+
+    def geom_scores(self, db, sigma=0.10, clip=0.5, min_joints=1, joint_mask=None, min_conf=0.0, details=False):
+        """Matching scores from the calibration alone (mpe_geom_scores_batch; no weights needed): per edge-node the mean
+        distance between the back-projected rays of its two skeletons over the joints both have (joint_mask: the joints
+        that may vote, None = all; min_conf: the detection confidence a vote needs in both views), clipped per joint at
+        `clip` metres (0: no clip), as score = sigma / (sigma + mean); 0 with fewer than min_joints votes.  include/mpe.h
+        has the rule, harness/geometric.py states it in numpy and the two agree bit for bit.  The scores feed cluster()
+        like the GAT's.  -> scores [n_edge_nodes] f32, or with details (scores, n_votes u8, mean f64: -1 without a vote)."""
+        M = db.n_edge_nodes
+        sc = torch.empty(max(M, 1), dtype=torch.float32, device=self.device)
+        a = self._geom_args(sigma, clip, min_joints, joint_mask, min_conf)
+        a.d_scores = sc.data_ptr()
+        if details:
+            nv = torch.empty(max(M, 1), dtype=torch.uint8, device=self.device)
+            mean = torch.empty(max(M, 1), dtype=torch.float64, device=self.device)
+            a.d_n_votes, a.d_mean = nv.data_ptr(), mean.data_ptr()
+        self._chk(self.lib.mpe_geom_scores_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return (sc[:M], nv[:M], mean[:M]) if details else sc[:M]
+
+    def geom_match(self, db, want_scores=True, sigma=0.10, clip=0.5, min_joints=1, joint_mask=None, min_conf=0.0):
+        """match() with the geometric scores of geom_scores in the GAT's place (mpe_geom_match_batch: scores + clustering).
+        -> (scores[n_edge_nodes] f32 or None, persons[B,Pcap,V] i32, n_persons[B] i32)."""
+        B = db.n_frames
+        scores = torch.empty(max(db.n_edge_nodes, 1), dtype=torch.float32, device=self.device) if want_scores else None
+        persons = torch.empty((B, self.pcap, self.V), dtype=torch.int32, device=self.device)
+        n_persons = torch.empty((B,), dtype=torch.int32, device=self.device)
+        a = self._geom_args(sigma, clip, min_joints, joint_mask, min_conf)
+        a.d_scores = scores.data_ptr() if want_scores else None
+        self._chk(self.lib.mpe_geom_match_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a), _ptr(persons), _ptr(n_persons)))
+        return (scores[:db.n_edge_nodes] if want_scores else None), persons, n_persons
+
+    def _match_stage(self, matcher, geom):
+        """matcher 'gat' | 'geometric' (geom: the options of geom_match) -> the matching call of the pipelines, f(engine, db)."""
+        if matcher == 'gat':
+            return lambda e, db: e.match(db, want_scores=False)
+        if matcher != 'geometric':
+            raise ValueError("matcher must be 'gat' or 'geometric'")
+        opts = dict(geom or {})
+        return lambda e, db: e.geom_match(db, want_scores=False, **opts)
 
     def gat_scores(self, db, heads=False, feats=None):
         """GAT2.forward; `feats` (optional) = dense [n_nodes, F] rows supplied by the caller."""

@@ -392,6 +392,58 @@ typedef struct {
 } mpe_refine_args;
 int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_refine_args *a);
 
+/* Geometric cross-view matching: a score per edge-node (h1,h2) that needs the calibration only -- how closely the
+ * back-projected rays of the two 2D skeletons meet in space (the standard multi-view baseline; no GAT, no MLP weights).
+ * All binary64, every operation named below rounded on its own (nothing fused), quotients and roots correctly rounded;
+ * only the score is rounded to float.  harness/geometric.py states the same in numpy, and the two agree bit for bit.
+ * The edge-nodes are the batch's: the implicit list or mpe_batch::d_en_pair (checked and copied as for every other stage).
+ * Rays.  Head h of camera c, joint j, pixel (u, v) = d_xy[h][j]; (x, y) = the five-iteration undistortion of
+ *   mpe_triangulate_batch (csrc/dlt_common.h: undistort_point, with fx, fy, cx, cy = (double) cfg.K[c] and k1, k2, p1, p2,
+ *   k3 = cfg.dist[c]), which leaves up to 1.5e-2 px at the image border, followed by two Newton steps on the same lens
+ *   model (a ray then passes within 1e-6 px of its pixel).  With xt = (u - cx) * (1 / fx), yt = (v - cy) * (1 / fy), twice:
+ *   r = x*x + y*y ; f = 1 + ((k3*r + k2)*r + k1)*r ; fd = ((3*k3)*r + 2*k2)*r + k1 ; tx = 2*x ; ty = 2*y
+ *   ex = ((x*f + p1*(tx*y)) + p2*(r + tx*x)) - xt ; ey = ((y*f + p1*(r + ty*y)) + p2*(tx*y)) - yt
+ *   a = ((f + (tx*x)*fd) + p1*ty) + (3*p2)*tx ; b = ((tx*y)*fd + p1*tx) + p2*ty ; d = ((f + (ty*y)*fd) + (3*p1)*ty) + p2*tx
+ *   det = a*d - b*b ; x, y = x - (d*ex - b*ey) / det, y - (a*ey - b*ex) / det          (both from the old x, y)
+ *   With T = cfg.P[c] as stored (root -> camera; R = T[:, 0:3], t = T[:, 3]):
+ *   q_k = (T[0][k]*x + T[1][k]*y) + T[2][k]                                 k = 0..2
+ *   n   = sqrt((q_0*q_0 + q_1*q_1) + q_2*q_2) ; r_k = q_k / n              (unit direction, world frame)
+ *   o_k = -((T[0][k]*T[0][3] + T[1][k]*T[1][3]) + T[2][k]*T[2][3])         (camera centre, world frame)
+ * Votes.  Joint j of edge-node (h1,h2) votes when the two heads are in different cameras, bit j is set in both
+ *   d_joint_mask words and in joint_mask (0 = every joint), and d_vp[h][j][0] >= min_conf for both heads.
+ * Distance of a voting joint, (o1, r1) the ray of h1 and (o2, r2) that of h2:
+ *   w_k = o1_k - o2_k ; b = (r1_0*r2_0 + r1_1*r2_1) + r1_2*r2_2 ; d and e likewise from (r1, w) and (r2, w)
+ *   den = 1 - b*b ; den < 1e-12 (parallel rays): t1 = 0, t2 = e ; otherwise t1 = (b*e - d) / den, t2 = (e - b*d) / den
+ *   a t1 or t2 that is < 0 is replaced by 0 (rays that meet behind a camera are penalised, not rewarded)
+ *   g_k = (o1_k + t1*r1_k) - (o2_k + t2*r2_k) ; dist = sqrt((g_0*g_0 + g_1*g_1) + g_2*g_2)
+ *   with clip_m > 0, a dist > clip_m is replaced by clip_m.
+ * Score.  n = the number of voting joints, mean = (the left-fold sum of dist over the voting joints in increasing j,
+ *   from 0.0) / n, score = (float)(sigma_m / (sigma_m + mean)); 0.0f when n < min_joints (and so whenever the heads share
+ *   a camera).  With the clustering threshold 0.5, two skeletons link when their rays pass within sigma_m on average.
+ * Outputs per edge-node: d_scores; optionally d_n_votes = n and d_mean = mean (-1 where n == 0).  A frame beyond
+ *   max_heads_per_frame (or, with d_en_pair, beyond the per-frame edge-node limit) gets zeros (d_mean -1) and the sticky
+ *   status bit mpe_sync_status reports, as everywhere.
+ * mpe_geom_scores_batch: the topology launch mpe_cluster_batch also makes, then one launch (one workgroup per frame: the
+ *   unit rays of every head once, in LDS, or in a table of the context when max_heads_per_frame * (3 n_joints + 1) doubles
+ *   exceed 48 KiB -- same bits either way).  mpe_geom_match_batch: the same, then the clustering of mpe_cluster_batch on the
+ *   scores (d_scores may be NULL: the scores then stay in context scratch).  Both are ordered on `stream`, neither
+ *   synchronises nor allocates, n_frames == 0 does nothing, both work on a context without weights, and neither reads or
+ *   writes anything mpe_match_batch leaves behind for mpe_mlp3d_batch.  MPE_ERR_INVALID for sigma_m <= 0, clip_m < 0
+ *   (or NaN), min_joints outside 1..n_joints, a negative or NaN min_conf, or a NULL output. */
+typedef struct {
+    double sigma_m;                /* metres, > 0                                                    */
+    double clip_m;                 /* metres, >= 0; 0: no clip                                       */
+    int32_t min_joints;            /* 1 .. n_joints                                                  */
+    uint32_t joint_mask;           /* bit j: joint j may vote; 0: every joint                        */
+    float min_conf;                /* votes need values[3] >= this in both heads; 0: all             */
+    float *d_scores;               /* [n_edge_nodes]                                                 */
+    uint8_t *d_n_votes;            /* [n_edge_nodes] or NULL                                         */
+    double *d_mean;                /* [n_edge_nodes] or NULL: mean distance, -1 where n_votes == 0   */
+} mpe_geom_args;
+int mpe_geom_scores_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_geom_args *a);
+int mpe_geom_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_geom_args *a,
+                         int32_t *d_persons, int32_t *d_n_persons);
+
 /* Clustering quality of the matching stage (test/sm_metrics.py:125-229, test/sm_metrics_without_gt.py:131-170): labels
  * from proposals, the ground-truth grouping of a frame's bodies_3D, and the four scores of two labelings.
  * harness/partition.py states all three on the host; host and device agree bit for bit.  Per-frame status words: */

@@ -149,3 +149,18 @@ class Calibration:
 
     def index(self, cam_name):
         return self.names.index(cam_name)
+
+    def with_extrinsics(self, E):
+        """A new Calibration with root -> camera i given by E[i] (3 x 4, or 4 x 4 whose last row is 0 0 0 1), E in the
+        order of ``names``: T_d, T_i, T_i32, centre32 and P are rebuilt from E the way __init__ builds them from the
+        transform manager (T_i = numpy.linalg.inv of the stored matrix); intrinsics and distortion are kept.  This
+        object is not modified."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape not in ((self.n_cameras, 3, 4), (self.n_cameras, 4, 4)) or not np.isfinite(E).all():
+            raise ValueError('E must be finite and [%d,3,4] or [%d,4,4]' % (self.n_cameras, self.n_cameras))
+        tm = TransformManager()
+        for i, cam in enumerate(self.names):
+            T = np.eye(4)
+            T[:3, :] = E[i][:3, :]
+            tm.add_transform('root', cam, T)
+        return Calibration(self.params, tm)

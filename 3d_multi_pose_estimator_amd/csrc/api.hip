@@ -1864,3 +1864,196 @@ int mpe_profile_read_bf16(mpe_ctx *ctx, double *ms, double *flop, int64_t *launc
 }
 
 }  // extern "C"
+
+// ---- calibration (calib.hip sums on the device; the step below is host work, once per pass) ----
+#include "calib_solve.h"
+
+struct mpe_calib_host {
+    calib_cam cam[MPE_MAX_CAMERAS];
+    double E[MPE_MAX_CAMERAS * 12];                  // staging of the trial set for the copy to the device
+    double sums[MPE_MAX_CAMERAS * MPE_CALIB_SUMS];
+    int64_t n_obs[MPE_MAX_CAMERAS], n_skipped[MPE_MAX_CAMERAS];
+};
+
+namespace {
+
+// accepted = trial = E for every camera, the sums zeroed, the trial set on the device
+int calib_start(mpe_ctx *ctx, hipStream_t s, mpe_calib_state *st, const double *E) {
+    for (int c = 0; c < st->V; ++c) {
+        calib_cam_start(&st->host->cam[c], E + 12 * c);
+        std::memcpy(st->host->E + 12 * c, E + 12 * c, 12 * sizeof(double));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(st->E, st->host->E, (size_t)st->V * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_calib_clear(s, st, st->V));
+    HIPCHK(ctx, hipStreamSynchronize(s));            // the staging buffer is the state's own: the next call may rewrite it
+    return MPE_OK;
+}
+
+int calib_fetch(mpe_ctx *ctx, hipStream_t s, mpe_calib_state *st) {
+    mpe_calib_host *h = st->host;
+    HIPCHK(ctx, hipMemcpyAsync(h->sums, st->acc, (size_t)st->V * MPE_CALIB_SUMS * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h->n_obs, st->n_obs, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h->n_skipped, st->n_skipped, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return MPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpe_calib_destroy(mpe_ctx *ctx, mpe_calib_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    dev_free(ctx, st->E);
+    dev_free(ctx, st->acc);
+    dev_free(ctx, st->n_obs);
+    dev_free(ctx, st->n_skipped);
+    dev_free(ctx, st->S);
+    delete st->host;
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_calib_create(mpe_ctx *ctx, mpe_calib_state **out) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_create: NULL argument");
+    *out = nullptr;
+    DeviceGuard dg(ctx);
+    mpe_calib_state *st = new (std::nothrow) mpe_calib_state();
+    if (st) st->host = new (std::nothrow) mpe_calib_host();
+    if (!st || !st->host) {
+        delete st;
+        return fail(ctx, MPE_ERR_NOMEM, "mpe_calib_create: out of memory");
+    }
+    st->V = ctx->cfg.n_cameras;
+    st->max_frames = ctx->cfg.max_frames;
+    int rc = dev_alloc(ctx, &st->E, (size_t)st->V * 12);
+    if (!rc) rc = dev_alloc(ctx, &st->acc, (size_t)st->V * MPE_CALIB_SUMS);
+    if (!rc) rc = dev_alloc(ctx, &st->n_obs, st->V);
+    if (!rc) rc = dev_alloc(ctx, &st->n_skipped, st->V);
+    if (!rc) rc = dev_alloc(ctx, &st->S, calib_workspace_doubles(st->max_frames, st->V), false);
+    if (!rc) rc = calib_start(ctx, nullptr, st, &ctx->hcfg.P[0][0]);
+    if (rc) {
+        const std::string why = ctx->err;
+        mpe_calib_destroy(ctx, st);
+        ctx->err = why;
+        return rc;
+    }
+    *out = st;
+    return MPE_OK;
+}
+
+int mpe_calib_reset(mpe_ctx *ctx, void *stream, mpe_calib_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_reset: NULL state");
+    DeviceGuard dg(ctx);
+    return calib_start(ctx, static_cast<hipStream_t>(stream), st, &ctx->hcfg.P[0][0]);
+}
+
+int mpe_calib_set_extrinsics(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const double *E) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !E) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_set_extrinsics: NULL argument");
+    for (int i = 0; i < st->V * 12; ++i)
+        if (!calib_finite(E[i])) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_set_extrinsics: entry %d of camera %d is not finite", i % 12, i / 12);
+    DeviceGuard dg(ctx);
+    return calib_start(ctx, static_cast<hipStream_t>(stream), st, E);
+}
+
+int mpe_calib_get_extrinsics(mpe_ctx *ctx, const mpe_calib_state *st, double *accepted, double *trial) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_get_extrinsics: NULL state");
+    for (int c = 0; c < st->V; ++c) {
+        if (accepted) std::memcpy(accepted + 12 * c, st->host->cam[c].Ea, 12 * sizeof(double));
+        if (trial) std::memcpy(trial + 12 * c, st->host->cam[c].Et, 12 * sizeof(double));
+    }
+    return MPE_OK;
+}
+
+int mpe_calib_launches(mpe_ctx *ctx, const mpe_calib_state *st, int64_t *n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_launches: NULL argument");
+    *n = st->launches;
+    return MPE_OK;
+}
+
+int mpe_calib_batch(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_batch *b, const mpe_calib_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames != b->n_frames || a->pcap < 1 || a->n_joints != ctx->cfg.n_joints || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: bad sizes or modes (%d frames, the batch has %d; %d joints, the context has %d)",
+                    a->n_frames, b->n_frames, a->n_joints, ctx->cfg.n_joints);
+    if (!(a->huber_px >= 0.0)) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: huber_px %g must not be negative", a->huber_px);
+    if (st->V != ctx->cfg.n_cameras || b->n_frames > st->max_frames)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: the state belongs to another context");
+    if (b->n_frames == 0) return MPE_OK;
+    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: NULL argument");
+    HIPCHK(ctx, launch_calib(static_cast<hipStream_t>(stream), ctx->d_cfg, st->V, st, *b, *a));
+    return MPE_OK;
+}
+
+int mpe_calib_read(mpe_ctx *ctx, void *stream, mpe_calib_state *st, double *sums, int64_t *n_obs, int64_t *n_skipped) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_read: NULL state");
+    DeviceGuard dg(ctx);
+    int rc = calib_fetch(ctx, static_cast<hipStream_t>(stream), st);
+    if (rc) return rc;
+    if (sums) std::memcpy(sums, st->host->sums, (size_t)st->V * MPE_CALIB_SUMS * sizeof(double));
+    if (n_obs) std::memcpy(n_obs, st->host->n_obs, (size_t)st->V * sizeof(int64_t));
+    if (n_skipped) std::memcpy(n_skipped, st->host->n_skipped, (size_t)st->V * sizeof(int64_t));
+    return MPE_OK;
+}
+
+int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_calib_step_args *a, mpe_calib_report *report) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_step: NULL argument");
+    if (a->min_obs < 6) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_step: min_obs %lld is below 6, the unknowns of a camera", (long long)a->min_obs);
+    if (!(a->rot_tol >= 0.0) || !(a->trans_tol >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_calib_step: rot_tol %g and trans_tol %g must not be negative", a->rot_tol, a->trans_tol);
+    DeviceGuard dg(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    mpe_calib_host *h = st->host;
+    int rc = calib_fetch(ctx, s, st);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_calib_clear(s, st, st->V));
+    for (int c = 0; c < st->V; ++c)
+        if (h->cam[c].passes > 0 && h->n_obs[c] != h->cam[c].n_obs) {
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            return fail(ctx, MPE_ERR_INVALID, "mpe_calib_step: the passes did not see the same data (camera %d: %lld observations, %lld in the first pass)",
+                        c, (long long)h->n_obs[c], (long long)h->cam[c].n_obs);
+        }
+    int all_done = 1;
+    for (int c = 0; c < st->V; ++c) {
+        calib_cam *cam = &h->cam[c];
+        calib_cam_step(cam, h->sums + (size_t)c * MPE_CALIB_SUMS, h->n_obs[c], (a->hold_mask >> c) & 1u, a->min_obs, a->rot_tol, a->trans_tol);
+        std::memcpy(h->E + 12 * c, cam->Et, 12 * sizeof(double));
+        all_done &= calib_cam_done(cam);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(st->E, h->E, (size_t)st->V * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (report) {
+        std::memset(report, 0, sizeof *report);
+        report->n_cameras = st->V;
+        report->all_done = all_done;
+        for (int c = 0; c < st->V; ++c) {
+            const calib_cam &cam = h->cam[c];
+            mpe_calib_cam_report &r = report->cam[c];
+            r.status = cam.status;
+            r.passes = cam.passes;
+            r.n_obs = h->n_obs[c];
+            r.n_skipped = h->n_skipped[c];
+            r.cost_start = cam.cost_start;
+            r.cost = cam.Aa[27];
+            r.lambda = cam.lambda;
+            r.last_rot = cam.last_rot;
+            r.last_trans = cam.last_trans;
+            std::memcpy(r.delta, cam.delta, sizeof r.delta);
+        }
+    }
+    return MPE_OK;
+}
+
+}  // extern "C"

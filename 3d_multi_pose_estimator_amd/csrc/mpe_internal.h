@@ -218,6 +218,19 @@ struct mpe_track_score_state {
 };
 #define MPE_TS_TOTALS 12
 
+// calib.hip: what mpe_calib_batch accumulates and mpe_calib_step reads.  The Levenberg-Marquardt state of the cameras lives
+// on the host (api.hip, csrc/calib_solve.h).
+struct mpe_calib_host;
+struct mpe_calib_state {
+    int V = 0, max_frames = 0;
+    int64_t launches = 0;           // kernels enqueued since mpe_calib_create
+    double *E = nullptr;            // [V][12] trial extrinsics
+    double *acc = nullptr;          // [V][MPE_CALIB_SUMS] sums of the pass so far
+    unsigned long long *n_obs = nullptr, *n_skipped = nullptr;   // [V]
+    double *S = nullptr;            // scratch [max_frames][V][MPE_CALIB_SUMS]: the per-frame partials of a call
+    mpe_calib_host *host = nullptr;
+};
+
 namespace mpe {
 
 // gemm.hip
@@ -376,6 +389,10 @@ hipError_t launch_track_score(hipStream_t s, mpe_track_score_state *st, const mp
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);
 // refine.hip
 hipError_t launch_refine(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_refine_args &a);
+// calib.hip
+size_t calib_workspace_doubles(int max_frames, int V);
+hipError_t launch_calib(hipStream_t s, const DevCfg *cfg, int V, mpe_calib_state *st, const mpe_batch &b, const mpe_calib_args &a);
+hipError_t launch_calib_clear(hipStream_t s, mpe_calib_state *st, int V);
 // geom.hip: en_pair = the context's pair table (launch_topology); ray_table only when geom_needs_table()
 constexpr size_t GEOM_LDS_BYTES = 48 * 1024;     // head records of a frame staged in LDS up to this (three 256-thread workgroups per CU's 160 KiB)
 bool geom_needs_table(int max_heads_per_frame, int J);

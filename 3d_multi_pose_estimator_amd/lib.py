@@ -127,6 +127,28 @@ class mpe_refine_args(C.Structure):
                 ('d_iters', C.c_void_p), ('d_n_views', C.c_void_p)]
 
 
+class mpe_calib_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float), ('reserved', C.c_int32),
+                ('huber_px', C.c_double),
+                ('d_persons', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_poses', C.c_void_p), ('d_flags', C.c_void_p)]
+
+
+class mpe_calib_step_args(C.Structure):
+    _fields_ = [('rot_tol', C.c_double), ('trans_tol', C.c_double), ('min_obs', C.c_int64), ('hold_mask', C.c_uint32),
+                ('reserved', C.c_int32)]
+
+
+class mpe_calib_cam_report(C.Structure):
+    _fields_ = [('status', C.c_int32), ('passes', C.c_int32), ('n_obs', C.c_int64), ('n_skipped', C.c_int64),
+                ('cost_start', C.c_double), ('cost', C.c_double), ('lambda_', C.c_double), ('last_rot', C.c_double),
+                ('last_trans', C.c_double), ('delta', C.c_double * 6)]
+
+
+class mpe_calib_report(C.Structure):
+    _fields_ = [('n_cameras', C.c_int32), ('all_done', C.c_int32), ('cam', mpe_calib_cam_report * MPE_MAX_CAMERAS)]
+
+
 class mpe_geom_args(C.Structure):
     _fields_ = [('sigma_m', C.c_double), ('clip_m', C.c_double), ('min_joints', C.c_int32), ('joint_mask', C.c_uint32),
                 ('min_conf', C.c_float), ('d_scores', C.c_void_p), ('d_n_votes', C.c_void_p), ('d_mean', C.c_void_p)]
@@ -187,6 +209,10 @@ MPE_TRACK_SCORE_OVER_IDS, MPE_TRACK_SCORE_MAX_TABLE = 1, 1 << 22
 # per-joint status bits and the iteration cap of mpe_refine_batch
 MPE_REFINE_SOLVED, MPE_REFINE_MOVED, MPE_REFINE_CONVERGED, MPE_REFINE_FEW_VIEWS, MPE_REFINE_BAD_START = 1, 2, 4, 8, 16
 MPE_REFINE_MAX_ITERS = 64
+
+# per-camera status bits of mpe_calib_step and the sums a camera accumulates
+MPE_CALIB_HELD, MPE_CALIB_FEW_OBS, MPE_CALIB_CONVERGED, MPE_CALIB_STALLED, MPE_CALIB_ACCEPTED, MPE_CALIB_REJECTED = 1, 2, 4, 8, 16, 32
+MPE_CALIB_SUMS = 28
 
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
@@ -253,6 +279,15 @@ SYMBOLS = {
     'mpe_track_score_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_args)]),
+    'mpe_calib_create': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    'mpe_calib_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_calib_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_calib_set_extrinsics': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    'mpe_calib_get_extrinsics': (C.c_int, [C.c_void_p, C.c_void_p, c_f64p, c_f64p]),
+    'mpe_calib_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_calib_args)]),
+    'mpe_calib_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'mpe_calib_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_calib_step_args), C.POINTER(mpe_calib_report)]),
+    'mpe_calib_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'mpe_geom_scores_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args)]),
     'mpe_geom_match_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args), C.c_void_p, C.c_void_p]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),

@@ -1157,6 +1157,14 @@ class Engine:
         self._chk(self.lib.mpe_refine_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
         return res
 
+    def calibrator(self, kind, huber_px=0.0, min_obs=50, hold=()):
+        """A Calibrator for poses of `kind` ('est' or 'triang', as refine takes them): the camera extrinsics refined from
+        a recording's own poses, the joints held fixed (mpe_calib_*; include/mpe.h has the rule, harness/calibrate.py
+        states it in numpy).  huber_px > 0 bounds the pull of an outlying detection; a camera with fewer than min_obs
+        (>= 6) observations is held, as are the cameras in `hold` (names or engine indices).  This engine's own
+        calibration is never modified: Calibrator.calibration() gives the one to build the next engine from."""
+        return Calibrator(self, kind, huber_px, min_obs, hold)
+
     def residual_stats(self, res_list):
         """Per-camera statistics of one or more residual tensors [..., V, J] f64 on the device (mpe_residual_stats): the
         exact middle elements by radix select, a sum reduced in a fixed order.  -> dict of numpy arrays over the cameras:
@@ -1410,6 +1418,120 @@ class Tracker:
     def close(self):
         if getattr(self, 'state', None) and self.eng.ctx:
             self.eng.lib.mpe_track_destroy(self.eng.ctx, self.state)
+        self.state = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Calibrator:
+    """Engine.calibrator's object: trial extrinsics and the 28 sums per camera on the device, the Levenberg-Marquardt
+    state of the cameras in the library.  A pass is accumulate() over every batch of the recording, in any chunking (the
+    sums are the same bits), then step(); passes repeat on the same batches and poses until the report says all_done.
+    accumulate() stays on the current stream and neither synchronises nor reads back; step() synchronises."""
+
+    def __init__(self, eng, kind, huber_px, min_obs, hold):
+        if kind not in ('est', 'triang'):
+            raise ValueError('kind must be est or triang')
+        if not huber_px >= 0.0:
+            raise ValueError('huber_px must be >= 0')
+        names = list(eng.params.used_cameras_skeleton_matching)
+        idx = [names.index(h) if isinstance(h, str) else int(h) for h in hold]
+        if any(not 0 <= i < eng.V for i in idx):
+            raise ValueError('hold names cameras of the engine')
+        self.eng, self.kind, self.huber_px, self.min_obs = eng, kind, float(huber_px), int(min_obs)
+        self.hold_mask = sum(1 << i for i in set(idx))
+        self.state = C.c_void_p()
+        eng._chk(eng.lib.mpe_calib_create(eng.ctx, C.byref(self.state)))
+
+    def _open(self):
+        if not self.state:
+            raise RuntimeError('the calibrator is closed')
+
+    def accumulate(self, db, persons, n_persons, poses, flags, joint_mask=None, threshold=0.5):
+        """The observations of one batch added to the pass (arguments as Engine.refine takes them)."""
+        self._open()
+        eng = self.eng
+        B, tri, joint_mask = eng._pose_args(db, persons, n_persons, poses, flags, self.kind, joint_mask, ('est', 'triang'))
+        a = L.mpe_calib_args()
+        a.n_frames, a.pcap, a.n_joints = B, eng.pcap, eng.J
+        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
+        a.huber_px = self.huber_px
+        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
+        eng._chk(eng.lib.mpe_calib_batch(eng.ctx, eng._stream(), self.state, C.byref(db.struct), C.byref(a)))
+
+    def read(self):
+        """The sums of the pass so far (synchronises) -> {'acc' [V,28] f64, 'n_obs' [V] i64, 'n_skipped' [V] i64}."""
+        self._open()
+        eng = self.eng
+        acc, n, k = np.zeros((eng.V, L.MPE_CALIB_SUMS)), np.zeros(eng.V, np.int64), np.zeros(eng.V, np.int64)
+        i64p = C.POINTER(C.c_int64)
+        eng._chk(eng.lib.mpe_calib_read(eng.ctx, eng._stream(), self.state, acc.ctypes.data_as(L.c_f64p), n.ctypes.data_as(i64p),
+                                        k.ctypes.data_as(i64p)))
+        return {'acc': acc, 'n_obs': n, 'n_skipped': k}
+
+    def step(self, rot_tol=1e-7, trans_tol=1e-6):
+        """The end of a pass: per camera the pass is accepted or rejected and the next trial extrinsics are set
+        (mpe_calib_step).  -> {'status' (MPE_CALIB_* bits), 'passes', 'n_obs', 'n_skipped', 'cost_start', 'cost',
+        'lambda', 'last_rot', 'last_trans'} as arrays over the cameras, 'delta' [V,6] (the perturbation of the last trial
+        built) and 'all_done'."""
+        self._open()
+        eng = self.eng
+        a, rep = L.mpe_calib_step_args(), L.mpe_calib_report()
+        a.rot_tol, a.trans_tol, a.min_obs, a.hold_mask = float(rot_tol), float(trans_tol), self.min_obs, self.hold_mask
+        eng._chk(eng.lib.mpe_calib_step(eng.ctx, eng._stream(), self.state, C.byref(a), C.byref(rep)))
+        cams = [rep.cam[c] for c in range(rep.n_cameras)]
+        out = {k: np.array([getattr(c, k) for c in cams], np.int32) for k in ('status', 'passes')}
+        out.update({k: np.array([getattr(c, k) for c in cams], np.int64) for k in ('n_obs', 'n_skipped')})
+        out.update({k: np.array([getattr(c, k) for c in cams], np.float64) for k in ('cost_start', 'cost', 'last_rot', 'last_trans')})
+        out['lambda'] = np.array([c.lambda_ for c in cams], np.float64)
+        out['delta'] = np.array([list(c.delta) for c in cams], np.float64).reshape(-1, 6)
+        out['all_done'] = bool(rep.all_done)
+        return out
+
+    def extrinsics(self):
+        """-> (accepted [V,3,4], trial [V,3,4]) f64, in the engine's camera order."""
+        self._open()
+        eng = self.eng
+        acc, tri = np.zeros((eng.V, 3, 4)), np.zeros((eng.V, 3, 4))
+        eng._chk(eng.lib.mpe_calib_get_extrinsics(eng.ctx, self.state, acc.ctypes.data_as(L.c_f64p), tri.ctypes.data_as(L.c_f64p)))
+        return acc, tri
+
+    def calibration(self):
+        """A new Calibration: the engine's, with the accepted extrinsics (Calibration.with_extrinsics)."""
+        calib = self.eng.calib
+        E = np.array(calib.P, np.float64)
+        for i, cam in enumerate(self.eng.params.used_cameras_skeleton_matching):
+            E[calib.index(cam)] = self.extrinsics()[0][i]
+        return calib.with_extrinsics(E)
+
+    def set_extrinsics(self, E):
+        """Start afresh from E [V,3,4] (engine camera order): accepted = trial = E, the sums zeroed."""
+        self._open()
+        eng = self.eng
+        E = np.ascontiguousarray(E, np.float64)
+        if E.shape != (eng.V, 3, 4):
+            raise ValueError('E must be [%d,3,4]' % eng.V)
+        eng._chk(eng.lib.mpe_calib_set_extrinsics(eng.ctx, eng._stream(), self.state, E.ctypes.data_as(L.c_f64p)))
+
+    def launches(self):
+        """Kernels this calibrator has enqueued so far."""
+        self._open()
+        n = C.c_int64()
+        self.eng._chk(self.eng.lib.mpe_calib_launches(self.eng.ctx, self.state, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Start afresh from the engine's own extrinsics."""
+        self._open()
+        self.eng._chk(self.eng.lib.mpe_calib_reset(self.eng.ctx, self.eng._stream(), self.state))
+
+    def close(self):
+        if getattr(self, 'state', None) and self.eng.ctx:
+            self.eng.lib.mpe_calib_destroy(self.eng.ctx, self.state)
         self.state = None
 
     def __del__(self):

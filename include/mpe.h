@@ -392,6 +392,108 @@ typedef struct {
 } mpe_refine_args;
 int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_refine_args *a);
 
+/* Calibration: the camera extrinsics refined from a recording's own poses -- the other half of bundle adjustment: the 3D
+ * joints are held fixed and every camera is moved to the minimum of the reprojection cost of the joints it observed.  A
+ * pass (mpe_calib_batch over every batch of the recording) reduces all observations into one 6 x 6 system per camera on the
+ * device; mpe_calib_step solves the systems on the host (Levenberg-Marquardt per camera; the cameras are independent
+ * because the points are fixed) and sets the extrinsics the next pass is taken at.  Alternated with mpe_triangulate_batch /
+ * mpe_refine_batch under the new extrinsics this is a bundle adjustment of the rig; the global similarity gauge stays free
+ * (hold one camera to keep the rig where it was).  The context's own calibration is never modified.
+ * All binary64, every operation named below rounded on its own (nothing fused), quotients and roots correctly rounded;
+ * harness/calibrate.py states the same in numpy: the sums agree bit for bit, and so does the step's delta.
+ * State.  A trial extrinsic E[c] (3 x 4) per camera, cfg.P[c] at create; the 28 sums per camera of the pass so far.
+ * One pass, per observation.  Camera c observes joint j of person p of frame f exactly when mpe_reproject_batch, given the
+ *   same d_persons / d_n_persons / d_poses / d_flags / pose_f64 / joint_flags / joint_mask / threshold, would count
+ *   d_res[f][p][c][j]; X = that joint widened to f64, x, y = that detection.  With T = E[c], kd and K as for
+ *   mpe_refine_batch, the projection lines of mpe_refine_batch give pc_0..2, h0, h1, r, f, u_2, px, py, rx, ry, e.  Then
+ *   a = (1/pc_2, 0, (-h0)/pc_2) ; b = (0, 1/pc_2, (-h1)/pc_2)                 the derivative by pc_k, k = 0..2
+ *   fd, q_k, m_k, n_k, v_ik as for mpe_refine_batch from these a_k, b_k
+ *   cx_k = (v_0k - px*v_2k) / u_2 ; cy_k = (v_1k - py*v_2k) / u_2
+ *   the camera perturbed as pc + w x pc + tau, xi = (w_0, w_1, w_2, tau_0, tau_1, tau_2):
+ *   Jx_0 = cx_2*pc_1 - cx_1*pc_2 ; Jx_1 = cx_0*pc_2 - cx_2*pc_0 ; Jx_2 = cx_1*pc_0 - cx_0*pc_1 ; Jx_{3+k} = cx_k
+ *   Jy likewise from cy; the weight w and rho(e) as for mpe_refine_batch (Huber; huber_px = 0: plain least squares).
+ *   An observation whose joint is not finite, for which pc_2 > 0 does not hold, or whose px or py is not finite is not
+ *   summed and is counted in n_skipped[c].  Every other one adds 28 numbers to camera c (q = 0..27):
+ *     A_kl += w*(Jx_k*Jx_l + Jy_k*Jy_l)   k <= l, row by row: (0,0) (0,1) .. (0,5) (1,1) .. (5,5)       q = 0..20
+ *     g_k  += w*(Jx_k*rx + Jy_k*ry)                                                                  q = 21..26
+ *     C    += rho(e)                                                                                 q = 27
+ *   and 1 to n_obs[c].
+ * Order.  Per frame, S_f[c][q] is the left fold from 0.0 of these terms over p increasing, then j increasing.  A call takes
+ *   acc[c][q] = acc[c][q] + S_f[c][q] for its frames in increasing f -- every frame, whether its partial is zero or not --
+ *   and calls count in the order made: the sums do not depend on how a recording is cut into batches, bit for bit.
+ * mpe_calib_batch: two launches whatever the frame count, ordered on `stream`; neither synchronises nor allocates; n_frames
+ *   == 0 does nothing.  MPE_ERR_INVALID as for mpe_refine_batch: n_frames other than the batch's, n_joints other than the
+ *   context's, a negative (or NaN) huber_px.
+ * mpe_calib_step synchronises `stream`, reads the sums, runs the rule below per camera (csrc/calib_solve.h: the order of
+ *   every sum is written out there), stores the new trial extrinsics on the device and zeroes the sums.  Per camera the
+ *   state keeps the accepted extrinsics E_a with their cost C_a and sums A_a, g_a, lambda (1e-3 at the start) and n_obs of
+ *   the first pass.
+ *   Held: bit c of hold_mask (MPE_CALIB_HELD), or n_obs < min_obs (MPE_CALIB_HELD | MPE_CALIB_FEW_OBS; min_obs >= 6, else
+ *     MPE_ERR_INVALID).  A held camera has its sums and cost reported; its trial stays its accepted state.
+ *   n_obs other than the first pass's, in any camera: MPE_ERR_INVALID ("the passes did not see the same data"); the sums are
+ *     zeroed, nothing else changes.
+ *   First pass: accepted.  Later passes: accepted iff C < C_a (strict; NaN rejects).  Accepted: E_a = the trial, C_a, A_a,
+ *     g_a = the pass's, lambda = max(lambda / 10, 1e-12) (not after the first pass); if the step that led here had
+ *     |w| < rot_tol and max |tau_k| < trans_tol the camera is MPE_CALIB_CONVERGED and stops.  Rejected: lambda = lambda * 10.
+ *   Trial (after either): M = A_a + lambda*diag(A_a), M delta = -g_a by unpivoted LDL^T; a pivot that is not > 0 or a delta
+ *     that is not finite multiplies lambda by 10 and retries, at most 8 times, then the camera is MPE_CALIB_STALLED and
+ *     stops.  E_t = [exp(w) R_a | exp(w) t_a + tau], exp by Rodrigues' formula (series below |w| = 1e-8).
+ *   A camera that stopped keeps trial = accepted; later passes leave it alone.  all_done: every camera is held or stopped.
+ * mpe_calib_set_extrinsics: host E [V][12]; accepted = trial = E, the Levenberg-Marquardt state and the sums start afresh.
+ * mpe_calib_reset: the same with cfg.P.  mpe_calib_get_extrinsics: host copies [V][12] of the accepted and the trial set
+ * (either may be NULL).  mpe_calib_read: synchronises and returns the sums of the pass so far, [V][28], and the counts [V]
+ * (any may be NULL).  One state serves one thread and one stream of work at a time. */
+typedef struct mpe_calib_state mpe_calib_state;
+enum {
+    MPE_CALIB_HELD = 1,
+    MPE_CALIB_FEW_OBS = 2,
+    MPE_CALIB_CONVERGED = 4,
+    MPE_CALIB_STALLED = 8,
+    MPE_CALIB_ACCEPTED = 16,       /* the last step accepted the pass */
+    MPE_CALIB_REJECTED = 32        /* the last step rejected it       */
+};
+#define MPE_CALIB_SUMS 28
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t joint_mask;           /* bit j: joint j is observed                                     */
+    float threshold;               /* 0.5, as for mpe_reproject_batch                                */
+    int32_t reserved;
+    double huber_px;               /* pixels, >= 0; 0: plain least squares                           */
+    const int32_t *d_persons;      /* [n_frames][pcap][V]                                            */
+    const int32_t *d_n_persons;    /* [n_frames]                                                     */
+    const void *d_poses;
+    const uint8_t *d_flags;
+} mpe_calib_args;
+typedef struct {
+    double rot_tol, trans_tol;     /* radians, metres                                                */
+    int64_t min_obs;               /* >= 6                                                           */
+    uint32_t hold_mask;            /* bit c: camera c is held                                        */
+    int32_t reserved;
+} mpe_calib_step_args;
+typedef struct {
+    int32_t status, passes;        /* MPE_CALIB_* bits; passes this camera's state has seen          */
+    int64_t n_obs, n_skipped;      /* of the pass just read                                          */
+    double cost_start, cost;       /* C_a after the first pass and now                               */
+    double lambda;
+    double last_rot, last_trans;   /* |w| and |tau| of the last trial built                          */
+    double delta[6];               /* that trial's perturbation (w, tau)                             */
+} mpe_calib_cam_report;
+typedef struct {
+    int32_t n_cameras, all_done;
+    mpe_calib_cam_report cam[MPE_MAX_CAMERAS];
+} mpe_calib_report;
+int mpe_calib_create(mpe_ctx *ctx, mpe_calib_state **out);
+int mpe_calib_destroy(mpe_ctx *ctx, mpe_calib_state *st);
+int mpe_calib_reset(mpe_ctx *ctx, void *stream, mpe_calib_state *st);
+int mpe_calib_set_extrinsics(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const double *E);
+int mpe_calib_get_extrinsics(mpe_ctx *ctx, const mpe_calib_state *st, double *accepted, double *trial);
+int mpe_calib_batch(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_batch *b, const mpe_calib_args *a);
+int mpe_calib_read(mpe_ctx *ctx, void *stream, mpe_calib_state *st, double *sums, int64_t *n_obs, int64_t *n_skipped);
+int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_calib_step_args *a, mpe_calib_report *report);
+int mpe_calib_launches(mpe_ctx *ctx, const mpe_calib_state *st, int64_t *n);
+
 /* Geometric cross-view matching: a score per edge-node (h1,h2) that needs the calibration only -- how closely the
  * back-projected rays of the two 2D skeletons meet in space (the standard multi-view baseline; no GAT, no MLP weights).
  * All binary64, every operation named below rounded on its own (nothing fused), quotients and roots correctly rounded;

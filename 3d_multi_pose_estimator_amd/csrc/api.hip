@@ -1490,6 +1490,171 @@ int mpe_smooth_batch(mpe_ctx *ctx, void *stream, mpe_smooth_state *st, const mpe
     return MPE_OK;
 }
 
+int mpe_skel_destroy(mpe_ctx *ctx, mpe_skel_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    dev_free(ctx, st->bones);
+    dev_free(ctx, st->hist);
+    dev_free(ctx, st->len);
+    dev_free(ctx, st->count);
+    dev_free(ctx, st->ctr);
+    dev_free(ctx, st->sched);
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_skel_create(mpe_ctx *ctx, const mpe_skel_config *cfg, mpe_skel_state **out) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: NULL argument");
+    *out = nullptr;
+    if (!cfg || !cfg->bones) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: NULL argument");
+    const int32_t pcap = cfg->pcap, n_joints = cfg->n_joints, pose_f64 = cfg->pose_f64, tid_cap = cfg->tid_cap, n_bones = cfg->n_bones;
+    const int32_t *bones = cfg->bones;
+    const double bin_width = cfg->bin_width;
+    if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || (pose_f64 & ~1) || tid_cap < 1 || n_bones < 1 || n_bones > MPE_SKEL_MAX_BONES)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: pcap %d / joints %d / pose_f64 %d / tid_cap %d / n_bones %d; joints 1 .. %d, bones 1 .. %d",
+                    pcap, n_joints, pose_f64, tid_cap, n_bones, MPE_MAX_JOINTS, MPE_SKEL_MAX_BONES);
+    if (!(bin_width > 0.0) || !std::isfinite(bin_width))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: bin_width %g; it is finite and > 0", bin_width);
+    for (int b = 0; b < n_bones; ++b) {
+        const int32_t jp = bones[2 * b], jc = bones[2 * b + 1];
+        if (jp < 0 || jp >= n_joints || jc < 0 || jc >= n_joints || jp == jc)
+            return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: bone %d is (%d, %d); two different joints within 0 .. %d", b, jp, jc, n_joints - 1);
+    }
+    if (pcap > MPE_TRACK_MAX_PERSONS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_skel_create: pcap %d over %d", pcap, MPE_TRACK_MAX_PERSONS);
+    const uint64_t hist_bytes = (uint64_t)tid_cap * n_bones * MPE_SKEL_BINS * sizeof(uint32_t);
+    if (hist_bytes > MPE_SKEL_MAX_HIST_BYTES)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_skel_create: tid_cap %d x %d bones need %llu bytes of histogram, over %u", tid_cap, n_bones,
+                    (unsigned long long)hist_bytes, (unsigned)MPE_SKEL_MAX_HIST_BYTES);
+    DeviceGuard dg(ctx);
+    mpe_skel_state *st = new (std::nothrow) mpe_skel_state();
+    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_skel_create: out of memory");
+    st->pcap = pcap;
+    st->J = n_joints;
+    st->pose_f64 = pose_f64;
+    st->tid_cap = tid_cap;
+    st->n_bones = n_bones;
+    st->bin_width = bin_width;
+    const size_t pairs = (size_t)tid_cap * n_bones;
+    int rc = dev_alloc(ctx, &st->bones, (size_t)n_bones * 2);
+    if (!rc) rc = dev_alloc(ctx, &st->hist, pairs * MPE_SKEL_BINS);
+    if (!rc) rc = dev_alloc(ctx, &st->len, pairs);
+    if (!rc) rc = dev_alloc(ctx, &st->count, pairs);
+    if (!rc) rc = dev_alloc(ctx, &st->ctr, 3);
+    std::vector<uint32_t> sched;
+    skel_schedule(bones, n_bones, &sched, st->steps_upto);
+    if (!rc) rc = dev_alloc(ctx, &st->sched, sched.size(), false);
+    if (!rc && (hipMemcpy(st->bones, bones, (size_t)n_bones * 2 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(st->sched, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
+        rc = fail(ctx, MPE_ERR_HIP, "mpe_skel_create: hipMemcpy failed");
+    if (rc) {
+        const std::string why = ctx->err;
+        mpe_skel_destroy(ctx, st);
+        ctx->err = why;
+        return rc;
+    }
+    *out = st;
+    return MPE_OK;
+}
+
+int mpe_skel_reset(mpe_ctx *ctx, void *stream, mpe_skel_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_reset: NULL state");
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, launch_skel_reset(static_cast<hipStream_t>(stream), st));
+    return MPE_OK;
+}
+
+int mpe_skel_launches(mpe_ctx *ctx, const mpe_skel_state *st, int64_t *n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_launches: NULL argument");
+    *n = st->launches;
+    return MPE_OK;
+}
+
+namespace {
+
+// what observe and fit check alike -> MPE_OK with *run = false for a call without frames
+int skel_check(mpe_ctx *ctx, const char *who, const mpe_skel_state *st, const mpe_skel_args *a, bool *run) {
+    *run = false;
+    if (a->pcap != st->pcap || a->n_joints != st->J || a->pose_f64 != st->pose_f64)
+        return fail(ctx, MPE_ERR_INVALID, "%s: pcap %d / joints %d / pose_f64 %d, the state was made for %d / %d / %d", who, a->pcap, a->n_joints,
+                    a->pose_f64, st->pcap, st->J, st->pose_f64);
+    if (a->n_frames < 0 || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "%s: n_frames %d / joint_flags %d", who, a->n_frames, a->joint_flags);
+    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "%s: %d frames over 2^23 per call", who, a->n_frames);
+    *run = a->n_frames > 0;
+    return MPE_OK;
+}
+
+}  // namespace
+
+int mpe_skel_observe_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const mpe_skel_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_observe_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    bool run;
+    const int rc = skel_check(ctx, "mpe_skel_observe_batch", st, a, &run);
+    if (rc || !run) return rc;
+    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_observe_batch: NULL argument");
+    HIPCHK(ctx, launch_skel_observe(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
+int mpe_skel_update(mpe_ctx *ctx, void *stream, mpe_skel_state *st, int32_t min_samples) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_update: NULL state");
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, launch_skel_update(static_cast<hipStream_t>(stream), st, min_samples));
+    return MPE_OK;
+}
+
+int mpe_skel_set_lengths(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const double *d_len) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !d_len) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_set_lengths: NULL argument");
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, hipMemcpyAsync(st->len, d_len, (size_t)st->tid_cap * st->n_bones * sizeof(double), hipMemcpyDeviceToDevice,
+                               static_cast<hipStream_t>(stream)));
+    return MPE_OK;
+}
+
+int mpe_skel_get_lengths(mpe_ctx *ctx, void *stream, mpe_skel_state *st, double *h_len, int32_t *h_count, int64_t *h_counters, int32_t *h_status) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_get_lengths: NULL state");
+    DeviceGuard dg(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t pairs = (size_t)st->tid_cap * st->n_bones;
+    unsigned long long ctr[3] = {0, 0, 0};
+    if (h_len) HIPCHK(ctx, hipMemcpyAsync(h_len, st->len, pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (h_count) HIPCHK(ctx, hipMemcpyAsync(h_count, st->count, pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctr, st->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (h_counters) {
+        h_counters[0] = (int64_t)ctr[0];
+        h_counters[1] = (int64_t)ctr[1];
+    }
+    if (h_status) *h_status = (int32_t)ctr[2];
+    return MPE_OK;
+}
+
+int mpe_skel_fit_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const mpe_skel_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    bool run;
+    const int rc = skel_check(ctx, "mpe_skel_fit_batch", st, a, &run);
+    if (rc) return rc;
+    if (a->iters < 1 || a->iters > MPE_SKEL_MAX_ITERS)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: iters %d; 1 .. %d", a->iters, MPE_SKEL_MAX_ITERS);
+    if (!run) return MPE_OK;
+    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_poses_out || !a->d_err || !a->d_n_bones)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: NULL argument");
+    if (a->d_poses_out == a->d_poses) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: d_poses_out is d_poses (rows are copied through from the input)");
+    HIPCHK(ctx, launch_skel_fit(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
 int mpe_track_score_destroy(mpe_ctx *ctx, mpe_track_score_state *st) {
     if (!ctx) return MPE_ERR_INVALID;
     if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_destroy: NULL state");

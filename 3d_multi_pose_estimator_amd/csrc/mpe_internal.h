@@ -218,6 +218,22 @@ struct mpe_track_score_state {
 };
 #define MPE_TS_TOTALS 12
 
+// skel.hip: the bone-length state of mpe_skel_*: a histogram per (track id, bone), the length table read from it (or
+// uploaded), and the counters.  Nothing is double-buffered: observe adds integers, update and fit only read what
+// earlier calls on the stream wrote.
+struct mpe_skel_state {
+    int pcap = 0, J = 0, pose_f64 = 0, tid_cap = 0, n_bones = 0;
+    double bin_width = 0.0;
+    int64_t launches = 0;           // kernels enqueued since mpe_skel_create
+    int32_t *bones = nullptr;       // [n_bones][2] (parent, child)
+    uint32_t *hist = nullptr;       // [tid_cap][n_bones][MPE_SKEL_BINS]
+    double *len = nullptr;          // [tid_cap][n_bones], an entry > 0 and finite is a length
+    int32_t *count = nullptr;       // [tid_cap][n_bones]
+    unsigned long long *ctr = nullptr;   // out_of_range, over_ids, status
+    uint32_t *sched = nullptr;      // the steps of the fit (skel_schedule)
+    int steps_upto[MPE_SKEL_MAX_ITERS + 1] = {};   // [iters]: the steps that hold the first `iters` sweeps
+};
+
 // calib.hip: what mpe_calib_batch accumulates and mpe_calib_step reads.  The Levenberg-Marquardt state of the cameras lives
 // on the host (api.hip, csrc/calib_solve.h).
 struct mpe_calib_host;
@@ -380,6 +396,13 @@ hipError_t launch_track(hipStream_t s, mpe_track_state *st, const mpe_track_args
 // smooth.hip
 hipError_t launch_smooth_reset(hipStream_t s, mpe_smooth_state *st);
 hipError_t launch_smooth(hipStream_t s, mpe_smooth_state *st, const mpe_smooth_args &a);
+
+// skel.hip
+void skel_schedule(const int32_t *bones, int n_bones, std::vector<uint32_t> *table, int *steps_upto);
+hipError_t launch_skel_reset(hipStream_t s, mpe_skel_state *st);
+hipError_t launch_skel_observe(hipStream_t s, mpe_skel_state *st, const mpe_skel_args &a);
+hipError_t launch_skel_update(hipStream_t s, mpe_skel_state *st, int min_samples);
+hipError_t launch_skel_fit(hipStream_t s, mpe_skel_state *st, const mpe_skel_args &a);
 
 // track_score.hip
 hipError_t launch_track_score_reset(hipStream_t s, mpe_track_score_state *st);

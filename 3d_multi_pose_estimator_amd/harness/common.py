@@ -87,6 +87,15 @@ def build_parser(description):
     p.add_argument('--smooth-decay', type=float, default=0.8, metavar='L', help='--smooth: weight ratio of consecutive frames, within [0.25, 1]')
     p.add_argument('--smooth-fill', action='store_true',
                    help='--smooth: a triangulated joint that is missing now but was seen twice or more in the window gets the value of the line')
+    p.add_argument('--bones', type=int, default=0, metavar='ITERS',
+                   help='implies --track; the bone lengths of every track are learned from its own poses and the poses are moved towards them '
+                        'with ITERS sweeps, 1..64 (mpe_skel_*: after refine, track and smooth, before scoring; per evaluated --batch chunk '
+                        'observe, update, fit, so a chunk is fitted with the lengths of the recording up to and including that chunk), the '
+                        'fitted poses are scored, and one further line reports the tracks with a length, the rows and bones fitted, the '
+                        'bone-length error before and after and the mean displacement.  Like --track and --smooth it acts in metrics_from_model '
+                        'and metrics_from_triangulation; the other harnesses accept and ignore it')
+    p.add_argument('--bones-min', type=int, default=10, metavar='N', help='--bones: lengths a track needs of a bone before the bone is held to one')
+    p.add_argument('--bones-bin', type=float, default=2.0, metavar='MM', help='--bones: bin width of the length histograms, millimetres')
     p.add_argument('--refine', type=int, default=0, metavar='ITERS',
                    help='implies --device-metrics; every joint is moved to the minimum of its reprojection error over the cameras that saw it '
                         '(mpe_refine_batch: at most ITERS Levenberg-Marquardt iterations per joint, 1..64) and the refined poses are scored; '
@@ -531,7 +540,10 @@ def run(args, mode):
     refine = int(getattr(args, 'refine', 0) or 0)
     smooth = int(getattr(args, 'smooth', 0) or 0)
     track_score = bool(getattr(args, 'track_score', False))
-    if smooth or track_score:
+    bones = int(getattr(args, 'bones', 0) or 0)
+    if bones and not (1 <= bones <= 64 and args.bones_bin > 0 and np.isfinite(args.bones_bin)):
+        raise ValueError('--bones takes 1 .. 64 sweeps and --bones-bin a width > 0 (got %d, %g)' % (bones, args.bones_bin))
+    if smooth or track_score or bones:
         args.track = True
     if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
         args.device_metrics = True
@@ -546,7 +558,7 @@ def run(args, mode):
     T_i1 = torch.from_numpy(calib.T_i32[1])
     J = eng.J
     t = {'match': 0.0, '3d': 0.0}
-    tracker = summary = smoother = smoothed = gt_tracker = scorer = None
+    tracker = summary = smoother = smoothed = gt_tracker = scorer = skeleton = boned = None
     last = {}                                                # what the track score of a batch needs from infer_device
     refined = []
     if getattr(args, 'track', False):
@@ -555,6 +567,9 @@ def run(args, mode):
     if smooth:
         from .smoothing import SmoothSummary
         smoother, smoothed = eng.smoother(mode, window=smooth, decay=args.smooth_decay, fill=args.smooth_fill), SmoothSummary(mode)
+    if bones:
+        from .skeleton import SkeletonSummary
+        skeleton, boned = eng.skeleton(mode, bin_mm=args.bones_bin), SkeletonSummary()
     if track_score:
         # GT identities: the GT bodies of the evaluated frames through a tracker of their own, same gate and gap
         gt_tracker = eng.tracker('gt', max_gap=args.track_gap, gate=args.track_gate, pcap=TRACK_SCORE_GCAP)
@@ -619,12 +634,22 @@ def run(args, mode):
         if tracker is not None:
             # the frames that are evaluated (a cross-camera pair, as Engine.evaluate's skip rule has it), in order
             keep = torch.from_numpy(np.flatnonzero(np.diff(np.asarray(db.host.frame_en_off[:db.n_frames + 1])) != 0)).to(poses.device)
-        if smoother is not None:
-            # track, then smooth, then scoring: the fitted poses of the tracked frames take the place of the raw ones
+        if smoother is not None or skeleton is not None:
+            # track, then smooth, then bones, then scoring: the fitted poses of the tracked frames take the place of the raw ones
             p_in, f_in, n_in = poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep)
             tr = tracker.update(p_in, f_in, n_in)
-            sm = smoother.update(p_in, f_in, n_in, tr['ids'])
-            poses, flags = poses.index_copy(0, keep, sm['poses']), flags.index_copy(0, keep, sm['flags'])
+            p_cur, f_cur = p_in, f_in
+            if smoother is not None:
+                sm = smoother.update(p_in, f_in, n_in, tr['ids'])
+                p_cur, f_cur = sm['poses'], sm['flags']
+            if skeleton is not None:
+                # the lengths a chunk is fitted with are those of the recording up to and including the chunk
+                p_sk = p_cur
+                skeleton.observe(p_sk, f_cur, n_in, tr['ids'])
+                skeleton.update(args.bones_min)
+                sk = skeleton.fit(p_sk, f_cur, n_in, tr['ids'], iters=bones)
+                p_cur = sk['poses']
+            poses, flags = poses.index_copy(0, keep, p_cur), flags.index_copy(0, keep, f_cur)
             torch.cuda.synchronize()
         t3 = time.time()
         ev = eng.evaluate(db, poses, flags, n_persons, gt, mode)
@@ -633,9 +658,12 @@ def run(args, mode):
         t['3d'] += t2 - t1
         t['eval'] += time.time() - t3
         eng.sync_status()
-        if smoother is not None:
+        if smoother is not None or skeleton is not None:
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
-            smoothed.add(p_in.cpu().numpy(), f_in.cpu().numpy(), {k: sm[k].cpu().numpy() for k in ('poses', 'flags', 'n_samples')})
+            if smoother is not None:
+                smoothed.add(p_in.cpu().numpy(), f_in.cpu().numpy(), {k: sm[k].cpu().numpy() for k in ('poses', 'flags', 'n_samples')})
+            if skeleton is not None:
+                boned.add(p_sk.cpu().numpy(), {k: sk[k].cpu().numpy() for k in ('poses', 'err', 'n_bones')})
         elif tracker is not None:
             tr = tracker.update(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
@@ -710,6 +738,11 @@ def run(args, mode):
         print('Smoothed (window %d, decay %g%s): %d joints fitted, %d filled, mean displacement %.3f mm'
               % (smooth, args.smooth_decay, ', fill' if args.smooth_fill else '', r['fitted'], r['filled'], r['mean_move_mm']))
         smoother.close()
+    if skeleton is not None:
+        from .skeleton import report_line as bones_line
+        out['bones'] = r = boned.result(skeleton.lengths())
+        print(bones_line(bones, args.bones_bin, args.bones_min, r))
+        skeleton.close()
     if scorer is not None:
         from .track_score import report_line
         out['track_score'] = scorer.result()

@@ -97,6 +97,18 @@ class mpe_smooth_args(C.Structure):
                 ('d_poses_out', C.c_void_p), ('d_flags_out', C.c_void_p), ('d_vel', C.c_void_p), ('d_n_samples', C.c_void_p)]
 
 
+class mpe_skel_config(C.Structure):
+    _fields_ = [('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32), ('tid_cap', C.c_int32), ('n_bones', C.c_int32),
+                ('reserved', C.c_int32), ('bin_width', C.c_double), ('bones', c_i32p)]
+
+
+class mpe_skel_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('iters', C.c_int32), ('joint_mask', C.c_uint32), ('reserved', C.c_int32),
+                ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p),
+                ('d_poses_out', C.c_void_p), ('d_err', C.c_void_p), ('d_n_bones', C.c_void_p)]
+
+
 class mpe_track_score_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('gcap', C.c_int32), ('joint_flags', C.c_int32), ('threshold_mm', C.c_double),
                 ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p), ('d_assign', C.c_void_p),
@@ -203,6 +215,9 @@ MPE_TRACK_MAX_PERSONS, MPE_TRACK_MAX_GAP = 128, 15
 # the window cap of mpe_smooth_create and the output flag of a joint that mpe_smooth_batch filled in
 MPE_SMOOTH_MAX_WINDOW, MPE_SMOOTH_FILLED = 15, 2
 
+# the caps of mpe_skel_create / mpe_skel_fit_batch and the sticky status bit of mpe_skel_observe_batch
+MPE_SKEL_BINS, MPE_SKEL_MAX_BONES, MPE_SKEL_MAX_ITERS, MPE_SKEL_OVER_IDS, MPE_SKEL_MAX_HIST_BYTES = 512, 32, 64, 1, 256 << 20
+
 # the sticky status bit of mpe_track_score_batch and the cap on gid_cap * tid_cap of mpe_track_score_create
 MPE_TRACK_SCORE_OVER_IDS, MPE_TRACK_SCORE_MAX_TABLE = 1, 1 << 22
 
@@ -270,6 +285,15 @@ SYMBOLS = {
     'mpe_smooth_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
     'mpe_smooth_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_smooth_args)]),
     'mpe_smooth_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_skel_create': (C.c_int, [C.c_void_p, C.POINTER(mpe_skel_config), C.POINTER(C.c_void_p)]),
+    'mpe_skel_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_skel_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_skel_observe_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_skel_args)]),
+    'mpe_skel_update': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    'mpe_skel_set_lengths': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_skel_get_lengths': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_skel_fit_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_skel_args)]),
+    'mpe_skel_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'mpe_track_score_create': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     'mpe_track_score_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_track_score_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1087,6 +1087,15 @@ class Engine:
         pcap: rows per frame when the poses are not this engine's (default: the engine's Pcap)."""
         return Smoother(self, mode, window, decay, fill, self.pcap if pcap is None else int(pcap))
 
+    def skeleton(self, mode, bones=None, bin_mm=2.0, tid_cap=256, pcap=None):
+        """A Skeleton for one tracked sequence of poses in `mode` ('mlp' or 'tri', as Engine.tracker takes it): the
+        bone lengths of every track are learned from its own frames (a histogram per track and bone with bins of bin_mm,
+        its lower median) and the poses are moved towards them frame by frame (mpe_skel_*).  bones: (parent, child) joint
+        pairs, at most 32, swept in list order (default: harness.skeleton.BONES_18, for 18 joints only); tid_cap: track
+        ids the tables hold (tid_cap * bones <= 2^17); pcap: rows per frame when the poses are not this engine's
+        (default: the engine's Pcap)."""
+        return Skeleton(self, mode, bones, bin_mm, tid_cap, self.pcap if pcap is None else int(pcap))
+
     def _pose_args(self, db, persons, n_persons, poses, flags, kind, joint_mask, kinds):
         """The argument checks reproject and refine share -> (B, tri, joint_mask)."""
         B = db.n_frames
@@ -1606,6 +1615,129 @@ class Smoother:
     def close(self):
         if getattr(self, 'state', None) and self.eng.ctx:
             self.eng.lib.mpe_smooth_destroy(self.eng.ctx, self.state)
+        self.state = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Skeleton:
+    """Engine.skeleton's object: the device state of one sequence (a histogram of lengths per track id and bone, the
+    length table, the counters).  observe() adds frames in any order and chunking, update() reads the lengths off the
+    histograms, fit() moves poses towards the lengths of their tracks.  Everything stays on the device and on the
+    current stream: only lengths() synchronises and reads back."""
+
+    def __init__(self, eng, mode, bones, bin_mm, tid_cap, pcap):
+        from .harness import skeleton as S
+        if mode not in ('mlp', 'tri'):
+            raise ValueError('mode must be mlp or tri')
+        if bones is None:
+            if eng.J != 18:
+                raise ValueError('bones must be given for %d joints (the default list is for 18)' % eng.J)
+            bones = S.BONES_18
+        self.bones = S.check_bones(bones, eng.J)
+        if not (bin_mm > 0 and np.isfinite(bin_mm)):
+            raise ValueError('bin_mm must be finite and > 0')
+        if int(tid_cap) < 1 or int(tid_cap) * len(self.bones) * L.MPE_SKEL_BINS * 4 > L.MPE_SKEL_MAX_HIST_BYTES:
+            raise ValueError('tid_cap must be within 1 .. %d for %d bones' % (L.MPE_SKEL_MAX_HIST_BYTES // (4 * L.MPE_SKEL_BINS * len(self.bones)),
+                                                                            len(self.bones)))
+        self.eng, self.mode, self.bin_width, self.tid_cap, self.pcap = eng, mode, float(bin_mm) / 1000.0, int(tid_cap), int(pcap)
+        self.state = C.c_void_p()
+        flat = np.ascontiguousarray(self.bones, np.int32)
+        cfg = L.mpe_skel_config()
+        cfg.pcap, cfg.n_joints, cfg.pose_f64, cfg.tid_cap, cfg.n_bones = self.pcap, eng.J, int(mode == 'tri'), self.tid_cap, len(self.bones)
+        cfg.bin_width, cfg.bones = self.bin_width, flat.ctypes.data_as(L.c_i32p)
+        eng._chk(eng.lib.mpe_skel_create(eng.ctx, C.byref(cfg), C.byref(self.state)))
+
+    def _args(self, poses, flags, n_persons, ids, joint_mask):
+        eng, tri = self.eng, self.mode == 'tri'
+        if not self.state:
+            raise RuntimeError('the skeleton is closed')
+        B = int(poses.shape[0]) if poses.dim() == 4 else -1
+        want = torch.float64 if tri else torch.float32
+        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, eng.J, 3):
+            raise ValueError('poses must be %s [B,%d,%d,3]' % (want, self.pcap, eng.J))
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if tri else (B, self.pcap)):
+            raise ValueError('flags do not match mode %s' % self.mode)
+        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
+            raise ValueError('n_persons must be int32 [%d]' % B)
+        if ids.dtype != torch.int32 or tuple(ids.shape) != (B, self.pcap):
+            raise ValueError('ids must be int32 [%d,%d]' % (B, self.pcap))
+        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous() and ids.is_contiguous()):
+            raise ValueError('poses, flags, n_persons and ids must be contiguous')
+        if any(t.device != eng.device for t in (poses, flags, n_persons, ids)):
+            raise ValueError('poses, flags, n_persons and ids must be on %s' % eng.device)
+        a = L.mpe_skel_args()
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, self.pcap, eng.J, int(tri), int(tri)
+        a.joint_mask = (1 << eng.J) - 1 if joint_mask is None else int(joint_mask)
+        a.d_poses, a.d_flags, a.d_n_persons, a.d_track_id = poses.data_ptr(), flags.data_ptr(), n_persons.data_ptr(), ids.data_ptr()
+        return a, B
+
+    def observe(self, poses, flags, n_persons, ids, joint_mask=None):
+        """poses / flags / n_persons of B >= 0 frames as Tracker.update took them, and the 'ids' it returned: the length
+        of every bone whose two joints are there (and inside joint_mask, default: all) goes into its track's histogram."""
+        a, _ = self._args(poses, flags, n_persons, ids, joint_mask)
+        self.eng._chk(self.eng.lib.mpe_skel_observe_batch(self.eng.ctx, self.eng._stream(), self.state, C.byref(a)))
+
+    def update(self, min_samples=10):
+        """The length table from the histograms as they stand: the lower median of every (track, bone) that has
+        min_samples lengths or more, none for the others."""
+        self.eng._chk(self.eng.lib.mpe_skel_update(self.eng.ctx, self.eng._stream(), self.state, int(min_samples)))
+
+    def fit(self, poses, flags, n_persons, ids, iters=16, joint_mask=None):
+        """`iters` (1 .. 64) sweeps over the bones of every row whose track has lengths.  -> {'poses' (the type and
+        shape of the input, a new tensor), 'err' [B,Pcap,2] f64 (the row's worst bone-length error in metres before and
+        after, -1 for a row that is not fitted), 'n_bones' [B,Pcap] u8 (bones held to a length)}, device tensors."""
+        if not 1 <= int(iters) <= L.MPE_SKEL_MAX_ITERS:
+            raise ValueError('iters must be within 1 .. %d' % L.MPE_SKEL_MAX_ITERS)
+        a, B = self._args(poses, flags, n_persons, ids, joint_mask)
+        dev = self.eng.device
+        out = {'poses': torch.empty_like(poses), 'err': torch.empty((B, self.pcap, 2), dtype=torch.float64, device=dev),
+               'n_bones': torch.empty((B, self.pcap), dtype=torch.uint8, device=dev)}
+        a.iters = int(iters)
+        a.d_poses_out, a.d_err, a.d_n_bones = (out[k].data_ptr() for k in ('poses', 'err', 'n_bones'))
+        self.eng._chk(self.eng.lib.mpe_skel_fit_batch(self.eng.ctx, self.eng._stream(), self.state, C.byref(a)))
+        return out
+
+    def lengths(self):
+        """The table as it stands (synchronises) -> {'len' [tid_cap, n_bones] f64 metres (an entry > 0 and finite is a
+        length), 'count' i32 of the same shape (numpy), 'out_of_range', 'over_ids', 'status' (int)}."""
+        n = (self.tid_cap, len(self.bones))
+        table, count = np.empty(n, np.float64), np.empty(n, np.int32)
+        ctr, status = (C.c_int64 * 2)(), C.c_int32()
+        self.eng._chk(self.eng.lib.mpe_skel_get_lengths(self.eng.ctx, self.eng._stream(), self.state, table.ctypes.data, count.ctypes.data,
+                                                        C.addressof(ctr), C.addressof(status)))
+        return {'len': table, 'count': count, 'out_of_range': int(ctr[0]), 'over_ids': int(ctr[1]), 'status': int(status.value)}
+
+    def set_lengths(self, table):
+        """A caller's table [tid_cap, n_bones] (metres; an entry <= 0 or not finite: no length) in the place of the
+        learned one, ordered on the current stream.  A host array is uploaded first."""
+        if not self.state:
+            raise RuntimeError('the skeleton is closed')
+        if not isinstance(table, torch.Tensor):
+            table = torch.from_numpy(np.ascontiguousarray(table, np.float64))
+        if table.dtype != torch.float64 or tuple(table.shape) != (self.tid_cap, len(self.bones)):
+            raise ValueError('the table must be float64 [%d,%d]' % (self.tid_cap, len(self.bones)))
+        table = table.to(self.eng.device).contiguous()
+        self.eng._chk(self.eng.lib.mpe_skel_set_lengths(self.eng.ctx, self.eng._stream(), self.state, table.data_ptr()))
+        table.record_stream(torch.cuda.current_stream(self.eng.device))
+
+    def launches(self):
+        """Kernels this skeleton has enqueued so far."""
+        n = C.c_int64()
+        self.eng._chk(self.eng.lib.mpe_skel_launches(self.eng.ctx, self.state, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Empty histograms, no lengths, counters at zero (ordered on the current stream)."""
+        self.eng._chk(self.eng.lib.mpe_skel_reset(self.eng.ctx, self.eng._stream(), self.state))
+
+    def close(self):
+        if getattr(self, 'state', None) and self.eng.ctx:
+            self.eng.lib.mpe_skel_destroy(self.eng.ctx, self.state)
         self.state = None
 
     def __del__(self):

@@ -1067,6 +1067,91 @@ int mpe_track_score_result(mpe_ctx *ctx, void *stream, mpe_track_score_state *st
 int mpe_track_score_read(mpe_ctx *ctx, void *stream, mpe_track_score_state *state, int32_t *h_ident, int32_t *h_pred_count,
                          int32_t *h_table);
 
+/* Skeleton: bone lengths held constant along a track.  The tracker says which rows are one body over time; the lengths of
+ * that body's bones are learned from its own frames (a histogram per (track, bone), its lower median) and every pose of
+ * the track is then moved, within its own frame, towards those lengths.  The rule (harness/skeleton.py states it in
+ * numpy, and the two agree bit for bit):
+ *   State, fixed at create time (mpe_skel_config): pcap, n_joints, pose_f64, tid_cap, the bone list int32 [n_bones][2] = (parent, child)
+ *   with 0 <= parent != child < n_joints, 1 <= n_bones <= MPE_SKEL_MAX_BONES, and bin_width (f64 metres, finite, > 0).
+ *   It holds hist u32 [tid_cap][n_bones][MPE_SKEL_BINS], len f64 and count i32 [tid_cap][n_bones], the int64 counters
+ *   out_of_range and over_ids, and the sticky status word.
+ *   Detections and joint presence as in mpe_smooth_batch.  Row p of frame f is a detection when p < d_n_persons[f],
+ *   d_track_id[f][p] >= 0 and, with joint_flags == 0, d_flags[f][p] != 0; joint_flags == 0: all joints of a detection
+ *   are present; joint_flags == 1: joint j is present when d_flags[f][p][j] != 0.  A joint is ACTIVE when it is present,
+ *   inside joint_mask and its three stored coordinates are finite; a bone is LIVE in a row when both its joints are
+ *   active.  Coordinates are widened to f64; nothing is contracted; sqrt and / are IEEE.
+ *   Length of a bone from coordinates x: d = x_child - x_parent; s = (dx*dx + dy*dy) + dz*dz; l = sqrt(s).
+ *   mpe_skel_observe_batch: for every detection with id t < tid_cap and every live bone b, l from the stored
+ *   coordinates and q = l / bin_width; when l > 0 and q < MPE_SKEL_BINS, hist[t][b][(int)q] += 1, otherwise
+ *   out_of_range += 1.  A detection with t >= tid_cap adds 1 to over_ids (once per row, whatever its bones) and sets
+ *   MPE_SKEL_OVER_IDS; it reaches neither hist nor out_of_range.  Only integer additions reach memory: the state after
+ *   a sequence is the same bits for any chunking and any frame order.
+ *   mpe_skel_update(min_samples): for every (t, b), n = the sum of hist[t][b][..] and count = n (INT32_MAX at most).
+ *   n < max(min_samples, 1): len = 0.0, no length.  Otherwise k* = the smallest k with 2 * (hist[..0] + .. + hist[..k])
+ *   >= n (the lower median) and len = ((double)k* + 0.5) * bin_width.
+ *   mpe_skel_set_lengths copies a table [tid_cap][n_bones] f64 in DEVICE memory over len, ordered on `stream`, as it is;
+ *   an entry has a length when it is > 0 and finite.  count keeps what the last update left.
+ *   mpe_skel_fit_batch(iters): every (frame, row) on its own.  A bone is CONSTRAINED in a row when it is live and
+ *   len[t][b] has a length; a row is PROCESSED when it is a detection with t < tid_cap and a constrained bone.  The
+ *   working copy x holds the active joints in f64.  For sweep = 1 .. iters, for each constrained bone in LIST ORDER with
+ *   L = len[t][b]: l from x; unless l > 0 the bone is skipped; e = (l - L) / l; h = 0.5 * e; per axis a, with d taken
+ *   before any update of this bone: m = h * d_a; x_parent[a] = x_parent[a] + m; x_child[a] = x_child[a] - m.
+ *   d_poses_out: a joint that is an end of a constrained bone of a processed row gets its working value rounded once to
+ *   the pose type; every other joint and every other row is copied through bit for bit (absent joints and NaNs as well).
+ *   d_err[f][p] = {e0, e1}: the left fold from 0.0 over the constrained bones in list order of `if (v > m) m = v` with
+ *   v = |l - L|, l from the stored input coordinates (e0) and from the final working values before rounding (e1); both
+ *   -1.0 for a row that is not processed.  d_n_bones[f][p] = the constrained bones, 0 for a row that is not processed.
+ *   The fit changes nothing in the state and counts nothing.
+ * mpe_skel_create allocates all device memory the calls need (MPE_ERR_CAPACITY when tid_cap * n_bones * MPE_SKEL_BINS * 4
+ * bytes exceed MPE_SKEL_MAX_HIST_BYTES or pcap > MPE_TRACK_MAX_PERSONS; MPE_ERR_INVALID, with the values in
+ * mpe_last_error, for anything else that is wrong); no later call allocates.  mpe_skel_reset zeroes hist, len, count,
+ * the counters and the status, ordered on `stream`.  observe, update and fit are one kernel each whatever n_frames is
+ * (mpe_skel_launches counts them as mpe_track_launches does), ordered on `stream`, and neither synchronise nor allocate;
+ * n_frames == 0 does nothing.  MPE_ERR_INVALID, with the values in mpe_last_error: sizes or a pose type other than the
+ * state's, joint_flags outside {0, 1}, iters outside 1 .. MPE_SKEL_MAX_ITERS, d_poses_out == d_poses; n_frames > 2^23:
+ * MPE_ERR_CAPACITY.  mpe_skel_get_lengths is the only call that synchronises (`stream`): len, count, {out_of_range,
+ * over_ids} and the status to host arrays (any may be NULL).  Calls on one state belong on one stream. */
+#define MPE_SKEL_BINS 512
+#define MPE_SKEL_MAX_BONES 32
+#define MPE_SKEL_MAX_ITERS 64
+#define MPE_SKEL_OVER_IDS 1
+#define MPE_SKEL_MAX_HIST_BYTES (256u << 20)
+typedef struct mpe_skel_state mpe_skel_state;
+typedef struct {
+    int32_t pcap, n_joints;
+    int32_t pose_f64;              /* 0: f32 poses; 1: f64 */
+    int32_t tid_cap;               /* track ids 0 .. tid_cap - 1 have a row in the tables */
+    int32_t n_bones, reserved;
+    double bin_width;              /* metres, finite, > 0 */
+    const int32_t *bones;          /* host, [n_bones][2] (parent, child); copied */
+} mpe_skel_config;
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    int32_t iters;                 /* mpe_skel_fit_batch: sweeps, 1 .. MPE_SKEL_MAX_ITERS; observe does not read it */
+    uint32_t joint_mask;
+    int32_t reserved;
+    const void *d_poses;
+    const uint8_t *d_flags;
+    const int32_t *d_n_persons;    /* [n_frames] */
+    const int32_t *d_track_id;     /* [n_frames][pcap], mpe_track_batch's */
+    void *d_poses_out;             /* fit: the type and shape of d_poses, another buffer */
+    double *d_err;                 /* fit: [n_frames][pcap][2] */
+    uint8_t *d_n_bones;            /* fit: [n_frames][pcap] */
+} mpe_skel_args;
+int mpe_skel_create(mpe_ctx *ctx, const mpe_skel_config *cfg, mpe_skel_state **out);
+int mpe_skel_reset(mpe_ctx *ctx, void *stream, mpe_skel_state *state);
+int mpe_skel_destroy(mpe_ctx *ctx, mpe_skel_state *state);
+int mpe_skel_observe_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *state, const mpe_skel_args *a);
+int mpe_skel_update(mpe_ctx *ctx, void *stream, mpe_skel_state *state, int32_t min_samples);
+/* d_len: DEVICE memory, [tid_cap][n_bones] f64; a host pointer is not detected and faults.  Copied on `stream`, no synchronisation. */
+int mpe_skel_set_lengths(mpe_ctx *ctx, void *stream, mpe_skel_state *state, const double *d_len);
+int mpe_skel_get_lengths(mpe_ctx *ctx, void *stream, mpe_skel_state *state, double *h_len, int32_t *h_count, int64_t *h_counters,
+                         int32_t *h_status);
+int mpe_skel_fit_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *state, const mpe_skel_args *a);
+int mpe_skel_launches(mpe_ctx *ctx, const mpe_skel_state *state, int64_t *n);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

@@ -732,7 +732,7 @@ int copy_rows_in(mpe_ctx *ctx, hipStream_t s, float *dst, int ld_dst, const floa
 
 extern "C" {
 
-const char *mpe_version(void) { return "mpe-hip 0.1 (gfx950)"; }
+const char *mpe_version(void) { return "mpe-hip 0.2 (gfx950)"; }
 
 const char *mpe_last_error(const mpe_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 

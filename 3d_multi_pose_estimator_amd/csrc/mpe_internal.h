@@ -42,7 +42,8 @@ struct GatLayer {
 struct DevCfg {                // calibration + scalars, lives in device memory
     int32_t V, J, W, H, npj, min_views, median_axis;
     uint32_t used_joint_mask;
-    float threshold, median_window;
+    float threshold;
+    double median_window;      // f64: the reference's `dist_to_median < 0.05` is a comparison of doubles
     float Kinv[MPE_MAX_CAMERAS][9];
     float K[MPE_MAX_CAMERAS][9];
     float T_i[MPE_MAX_CAMERAS][16];

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(128) void k_triangulate(const DevCfg *__restrict__ 
     PersonCtx pc{f, p, V, J, npairs, h0};
     person_front(cfg, pc, s_head, s_mask, xy, s_und, s_pts);
     const int axis = cfg->median_axis;
-    const double win = (double)cfg->median_window;
+    const double win = cfg->median_window;
     for (int j = threadIdx.x; j < J; j += blockDim.x) {
         // pairs in combination order of the cameras that see joint j
         int n = 0;

@@ -42,7 +42,7 @@ class mpe_config(C.Structure):
         ('n_cameras', C.c_int32), ('n_joints', C.c_int32), ('image_width', C.c_int32),
         ('image_height', C.c_int32), ('numbers_per_joint', C.c_int32), ('min_views', C.c_int32),
         ('median_axis', C.c_int32), ('used_joint_mask', C.c_uint32), ('threshold', C.c_float),
-        ('median_window', C.c_float), ('max_frames', C.c_int32), ('max_heads', C.c_int32),
+        ('median_window', C.c_double), ('max_frames', C.c_int32), ('max_heads', C.c_int32),
         ('max_edge_nodes', C.c_int32), ('max_heads_per_frame', C.c_int32),
         ('max_persons_per_frame', C.c_int32),
         ('Kinv', c_f32p), ('K', c_f32p), ('T_i', c_f32p), ('P', c_f64p), ('dist', c_f64p),

@@ -63,7 +63,9 @@ typedef struct {
     int32_t median_axis;        /* parameters.axes_3D['Y'][0]                          */
     uint32_t used_joint_mask;   /* bit j set for j in parameters.used_joints           */
     float threshold;            /* CLASSIFICATION_THRESHOLD (0.5)                      */
-    float median_window;        /* 0.05 m (pose_estimator_utils.py:73)                 */
+    double median_window;       /* 0.05 m, compared in f64 as the reference does (pose_estimator_utils.py:73); a double
+                                 * (a float until mpe-hip 0.1): float(0.05) = 0.05000000074505806 keeps pairs the
+                                 * reference drops; the struct grew by 8 bytes with it, see mpe_version            */
     /* capacities of one batch (workspace is sized from these at mpe_create) */
     int32_t max_frames;
     int32_t max_heads;          /* total 2D skeletons in a batch                       */
@@ -142,7 +144,7 @@ typedef struct {
 int mpe_create(const mpe_config *cfg, mpe_ctx **out);
 void mpe_destroy(mpe_ctx *ctx);
 const char *mpe_last_error(const mpe_ctx *ctx);
-const char *mpe_version(void);
+const char *mpe_version(void);           /* "mpe-hip 0.2 ...": 0.2 = mpe_config.median_window is a double (the layout of 0.1 had a float) */
 
 /* ---- weights (host pointers, copied once; ctx owns padded device copies) ---------------
  * GAT2 state-dict tensors of layer l (gat2.py:18-48): fc1.weight [in][in], fc1.bias [in],

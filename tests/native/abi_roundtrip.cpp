@@ -139,7 +139,7 @@ int main(int argc, char **argv) {
     cfg.median_axis = (int32_t)c[6];
     cfg.used_joint_mask = (uint32_t)c[7];
     cfg.threshold = (float)c[8];
-    cfg.median_window = (float)c[9];
+    cfg.median_window = c[9];
     cfg.max_frames = (int32_t)c[10];
     cfg.max_heads = (int32_t)c[11];
     cfg.max_edge_nodes = (int32_t)c[12];

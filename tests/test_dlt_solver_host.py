@@ -2,6 +2,7 @@
 (tests/native/dlt_solve_host.cpp, run as a child process) against numpy.linalg.svd of the same systems (dlt_cases.py has the
 systems and the bounds).  Two builds: the host's own 1 / sqrt and 1 / x as the rsq / rcp estimates, and the estimates rounded to
 24 bits (coarser than the hardware's), which is what the Newton steps of the rotation are there for."""
+import json
 import os
 import re
 import shutil
@@ -96,3 +97,50 @@ def test_rotation_is_orthonormal_to_a_few_ulp(build_dir, build):
     print('%s: max |c^2 + s^2 - 1| %.3g (%.1f x 2^-53), max rotated inner product / (al + be) %.3g' % (build, orth, orth * 2.0 ** 53, left))
     assert orth <= 16 * 2.0 ** -53
     assert left <= 1e-12
+
+
+def test_window_edge_f64_and_float_windows_disagree():
+    """Why mpe_config.median_window is a double.  The frame of window_edge_case.py through the oracle's triangulation (numpy's SVD):
+    a bisection on the displacement t finds the point at which one moved pair sits less than 5e-10 m OUTSIDE the 5 cm window.  The
+    reference's comparison (`dist_to_median < 0.05`, doubles) drops that pair; the same comparison against float(0.05) =
+    0.05000000074505806, which is what a float field hands the kernel, keeps it, and the joint moves by
+    more than 7 mm."""
+    import window_edge_case as we
+    from conftest import env, oracle, pkg
+    onp, syn, calib = oracle(), pkg('synthetic'), env('panoptic').calib
+    params = calib.params
+    axis = params.axes_3D['Y'][0]
+    cams = list(params.camera_names)
+    assert we.JOINT in params.used_joints and len(cams) == 5
+
+    def skeletons(t):
+        fr, _ = we.frame(calib, syn, t)
+        return {c: json.loads(fr[c][0])[0] for c in cams}
+
+    def pair_points(t):
+        """The oracle's pair loop for the one joint (oracle_np.triangulate_person)."""
+        sk = skeletons(t)
+        und = [onp.undistort_points(np.array(sk[c][str(we.JOINT)][1:3]), calib.K32[calib.index(c)], calib.dist[calib.index(c)])[0] for c in cams]
+        return np.array([onp.dlt_pair(calib.P[calib.index(cams[a])], calib.P[calib.index(cams[b])], und[a], und[b])
+                         for a in range(5) for b in range(a + 1, 5)])
+
+    t_out, t_in, k, steps = we.bisect(lambda t: we.window_distances(pair_points(t), axis))
+    d_out, d_in = we.window_distances(pair_points(t_out), axis)[k], we.window_distances(pair_points(t_in), axis)[k]
+    print('t outside %.12f px (distance - 0.05 = %.3g m), t inside %.12f px (%.3g m), pair %d, %d steps' % (t_out, d_out - 0.05, t_in, d_in - 0.05, k, steps))
+    assert we.WINDOW <= d_out < we.WINDOW + we.BAND and we.WINDOW - we.BAND < d_in < we.WINDOW
+    pts = pair_points(t_out)
+    want, kept = we.filtered_mean(pts, axis, we.WINDOW)
+    # the oracle itself (the reference's rule restated) is the f64 window: same bits as numpy's mean over the kept pairs up to its summation order
+    ref = onp.triangulate_person(skeletons(t_out), calib, all_joints=True)[we.JOINT]
+    assert np.abs(ref - want).max() < 1e-15
+    as_float, kept_float = we.filtered_mean(pts, axis, we.WINDOW_AS_FLOAT)
+    assert kept_float == kept + 1, (kept, kept_float)
+    moved = np.linalg.norm(as_float - want)
+    print('f64 window keeps %d of 10 pairs, the float window %d; the joint moves by %.1f mm' % (kept, kept_float, 1e3 * moved))
+    # the kept pairs are the six that never moved (all at the median), the seventh is 5 cm from it along Y: 0.05 / 7 m along Y alone
+    assert kept == 6 and moved > 0.05 / 7 * 0.99
+    # inside the window the two agree
+    pts = pair_points(t_in)
+    a, ka = we.filtered_mean(pts, axis, we.WINDOW)
+    b, kb = we.filtered_mean(pts, axis, we.WINDOW_AS_FLOAT)
+    assert ka == kb == kept + 1 and np.array_equal(a, b)

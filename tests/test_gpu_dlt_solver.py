@@ -99,7 +99,7 @@ def test_every_call_site_gives_the_bits_of_dlt_pairs(engine, calib, n_frames):
     # triangulate: pairs on the joint mask, upper median of the Y axis, mean of the pairs within the window of it
     key, pts, cams = person_pairs(db.host, pn, nn, V, J, db.host.joint_mask)
     X = grouped(key, engine.dlt_pairs(pts, cams).cpu().numpy())
-    axis, win = engine.params.axes_3D['Y'][0], float(np.float32(0.05))
+    axis, win = engine.params.axes_3D['Y'][0], 0.05
     tri_np, jv_np = tri.cpu().numpy(), jv.cpu().numpy()
     for f in range(n_frames):
         for p in range(int(nn[f])):
@@ -114,3 +114,44 @@ def test_every_call_site_gives_the_bits_of_dlt_pairs(engine, calib, n_frames):
                     if abs(x[axis] - med) < win:
                         acc, kept = acc + x, kept + 1
                 assert np.array_equal(tri_np[f, p, j], acc / kept), (f, p, j)
+
+
+def test_triangulate_window_edge(engine, calib):
+    """The 5 cm median window is the reference's `dist_to_median < 0.05` in doubles (pose_estimator_utils.py:73), to the last bit: the
+    frame of window_edge_case.py, persons from the clustering kernel on the ground-truth pairing, and a bisection on the displacement
+    t of one pixel that runs on the GPU's own pair points (mpe_dlt_pairs; numpy's differ by up to ~1e-10 m, the band is 5e-10).  At
+    the t where one moved pair sits within 5e-10 m OUTSIDE the window the joint is the mean of the pairs strictly inside 0.05 -- the
+    pair is dropped -- and at the t where it sits within 5e-10 m inside it is kept.  A window carried as a float (0.05 + 7.45e-10)
+    keeps the pair at both."""
+    import window_edge_case as we
+    syn, common = pkg('synthetic'), pkg('harness.common')
+    V, J = engine.V, engine.J
+    axis = engine.params.axes_3D['Y'][0]
+    assert V == 5 and we.JOINT in engine.params.used_joints
+
+    def solve(t):
+        fr, owner = we.frame(calib, syn, t)
+        db = engine.to_device(engine.pack([oracle().processed_input(fr)], keep_json=True))
+        persons, n_persons = engine.cluster(db, common.teacher_scores(db, [owner]))
+        pn, nn = persons.cpu().numpy(), n_persons.cpu().numpy()
+        assert nn[0] == 1 and (pn[0, 0] >= 0).all()                # one person, seen by all five cameras
+        key, pts, cams = person_pairs(db.host, pn, nn, V, J, db.host.joint_mask)
+        X = grouped(key, engine.dlt_pairs(pts, cams).cpu().numpy())[(0, 0, we.JOINT)]
+        assert len(X) == 10
+        return db, persons, n_persons, np.array(X)
+
+    t_out, t_in, k, steps = we.bisect(lambda t: we.window_distances(solve(t)[3], axis))
+    kept = {}
+    for name, t in (('inside', t_in), ('outside', t_out)):
+        db, persons, n_persons, X = solve(t)                        # the frame packed again at this t
+        d = we.window_distances(X, axis)[k]
+        want, kept[name] = we.filtered_mean(X, axis, we.WINDOW)
+        tri, jv = engine.triangulate(db, persons, n_persons, all_joints=True)
+        engine.sync_status()
+        got = tri[0, 0, we.JOINT].cpu().numpy()
+        print('%s: t = %.12f px, distance - 0.05 = %.3g m, %d of 10 pairs inside 0.05, |kernel - expected| = %.3g m (%d steps)'
+              % (name, t, d - we.WINDOW, kept[name], np.abs(got - want).max(), steps))
+        assert (we.WINDOW <= d < we.WINDOW + we.BAND) if name == 'outside' else (we.WINDOW - we.BAND < d < we.WINDOW)
+        assert bool(jv[0, 0, we.JOINT])
+        assert np.array_equal(got, want), (name, t, got, want)
+    assert kept['outside'] == kept['inside'] - 1, kept

@@ -60,7 +60,7 @@ def _write_case(path, eng, gat_weights, mlp_weights, text):
     with open(path, 'wb') as fh:
         # the scalar fields of mpe_config in declaration order, as the Engine gave them to mpe_create (pipeline.py: Engine.__init__)
         _put(fh, 'cfg', np.array([eng.V, eng.J, p.image_width, p.image_height, p.numbers_per_joint, p.min_number_of_views, p.axes_3D['Y'][0],
-                                  sum(1 << j for j in p.used_joints), eng._made_with['threshold'], np.float32(0.05), eng.max_frames,
+                                  sum(1 << j for j in p.used_joints), eng._made_with['threshold'], 0.05, eng.max_frames,
                                   eng.max_frames * eng.hpf, eng.max_frames * eng.m_frame, eng.hpf, eng.pcap], np.float64))
         for k in ('Kinv', 'K', 'T_i', 'P', 'dist'):
             _put(fh, k, eng._keep[k])

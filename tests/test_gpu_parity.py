@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_checks as gc
 from conftest import ALL_CASES, ALL_CASES_FZ, CASES, GOLDEN, ROOT, env, load_case, oracle, pkg
 
 pytestmark = pytest.mark.gpu
@@ -105,17 +106,7 @@ def test_head_features_vs_golden(variant, name):
         p = 'f%d_' % n
         pb = engine.pack([_pi(frame)])
         feat = engine.head_features(engine.to_device(pb)).cpu().numpy()      # [H][J][10]
-        H = pb.n_heads
-        dense = np.zeros((H, env(variant).meta['num_feats']), np.float32)
-        rc = arr[p + 'feat_rc']
-        sel = rc[:, 0] < H
-        dense[rc[sel, 0], rc[sel, 1]] = arr[p + 'feat_v'][sel]
-        for h in range(H):
-            c = pb.head_cam[h]
-            want = dense[h, 2 + c * 180: 2 + (c + 1) * 180].reshape(18, 10)
-            # rays are 3-term f32 dot products: allow 2 ulp of the largest term
-            np.testing.assert_allclose(feat[h], want, rtol=0, atol=5e-7)
-            assert dense[h, 0] == 1.0
+        gc.head_features(feat, pb.head_cam[:pb.n_heads], arr, p, env(variant).meta['num_feats'])
 
 
 @pytest.mark.parametrize('variant,name', ALL_CASES_FZ)
@@ -133,14 +124,7 @@ def test_dense_rows_vs_golden(variant, name):
         db = engine.to_device(engine.pack([_pi(frame)]))
         if db.n_heads + db.n_edge_nodes == 0:
             continue
-        got = engine.dense_rows(db).cpu().numpy()
-        N = int(arr[p + 'N'])
-        assert got.shape == (N, F)
-        want = np.zeros((N, F), np.float32)
-        rc = arr[p + 'feat_rc']
-        want[rc[:, 0], rc[:, 1]] = arr[p + 'feat_v']
-        np.testing.assert_allclose(got, want, rtol=0, atol=5e-7)
-        assert np.array_equal(got == 0, want == 0) or np.abs(got[(got == 0) != (want == 0)]).max() < 5e-7
+        gc.dense_rows(engine.dense_rows(db).cpu().numpy(), arr, p, F)
 
 
 @pytest.mark.parametrize('variant,name', ALL_CASES_FZ)
@@ -151,10 +135,7 @@ def test_gat_scores_vs_golden(variant, name):
         p = 'f%d_' % n
         db = engine.to_device(engine.pack([_pi(frame)]))
         sc, sh = engine.gat_scores(db, heads=True)
-        want = arr[p + 'scores']
-        H = db.n_heads
-        np.testing.assert_allclose(sc.cpu().numpy(), want[H:], rtol=0, atol=2e-5)
-        np.testing.assert_allclose(sh.cpu().numpy(), want[:H], rtol=0, atol=2e-5)
+        gc.gat_scores(sc.cpu().numpy(), sh.cpu().numpy(), arr, p)
 
 
 @pytest.mark.parametrize('variant', ['wave', 'lds', 'big', 'block', 'ring23', 'ring23_wave', 'ring23_big'])
@@ -317,52 +298,15 @@ def test_match_and_3d_vs_golden(variant, name):
         p = 'f%d_' % n
         db = engine.to_device(engine.pack([_pi(frame)]))
         scores, persons, n_persons = engine.match(db)
-        want = arr[p + 'persons']
-        H = db.n_heads
-        gs = np.sort(arr[p + 'scores'][H:])
-        assert int(n_persons[0]) == len(want)
-        assert np.array_equal(persons[0, :len(want)].cpu().numpy(), want)
+        want = gc.persons(persons[0].cpu().numpy(), n_persons[0], arr, p)
         if len(want) == 0:
             continue
         rows, valid = engine.mlp_input_rows(db, persons, n_persons)
-        np.testing.assert_allclose(rows[0, :len(want)].cpu().numpy(), arr[p + 'mlp_in'], rtol=0, atol=3e-7)
-        assert valid[0, :len(want)].all()
-        # MLP on IDENTICAL rows (the reference's): |gpu - ref| is bounded by the two sides' distances
-        # to the exactly evaluated network, and the HIP side is the closer one.  No additive slack.
-        onp = oracle()
-        mlp_sd = env(variant).mlp
-        x_ref = torch.from_numpy(arr[p + 'mlp_in'])
-        y = engine.mlp_forward(x_ref.cuda()).cpu().numpy()
-        exact = onp.mlp_exact(mlp_sd, x_ref).numpy()
-        e_cpu = np.abs(arr[p + 'mlp_out'] - exact).max()
-        e_gpu = np.abs(y - exact).max()
-        assert e_gpu <= e_cpu, (e_gpu, e_cpu)
-        assert np.abs(y - arr[p + 'mlp_out']).max() <= e_cpu + e_gpu
-        # end to end the HIP path feeds its OWN rows (<= 3e-7 from the reference's, above).  Same
-        # rule on those rows with torch-CPU (= the reference's MLP arithmetic) as the other side;
-        # the batched path must give the bits of the stage call and the x10 decode must be exact fp32.
-        x_gpu = rows[0, :len(want)]
-        y_gpu_own = engine.mlp_forward(x_gpu.contiguous()).cpu().numpy()
-        y_cpu_own = onp.mlp_forward(mlp_sd, x_gpu.cpu()).numpy()
-        ex_own = onp.mlp_exact(mlp_sd, x_gpu.cpu()).numpy()
-        e_gpu_own, e_cpu_own = np.abs(y_gpu_own - ex_own).max(), np.abs(y_cpu_own - ex_own).max()
-        assert e_gpu_own <= e_cpu_own, (e_gpu_own, e_cpu_own)
+        gc.mlp_rows(rows[0].cpu().numpy(), valid[0].cpu().numpy(), arr, p, len(want))
         poses, pv = engine.mlp3d(db, persons, n_persons)
-        got_pose = poses[0, :len(want)].cpu().numpy()
-        assert np.array_equal(got_pose.reshape(len(want), -1), y_gpu_own * np.float32(10.0))
-        # distance to the reference's poses = MLP budget + what the reference network itself makes of
-        # the row difference (torch-CPU on both sets of rows) + one fp32 quantum of the decode
-        drift = 10 * np.abs(y_cpu_own - arr[p + 'mlp_out']).max()
-        q = float(np.spacing(np.float32(np.abs(arr[p + 'poses']).max())))
-        d = np.abs(got_pose - arr[p + 'poses']).max()
-        assert d <= 10 * (e_gpu_own + e_cpu_own) + drift + q, (d, e_gpu_own, e_cpu_own, drift)
+        gc.poses(engine, variant, arr, p, rows[0], poses[0].cpu().numpy(), len(want))
         tri, jv = engine.triangulate(db, persons, n_persons)
-        tv = arr[p + 'tri_valid'].astype(bool)
-        has_id = any('ID' in sk for cam in frame for sk in json.loads(frame[cam][0]))
-        if not has_id:
-            assert np.array_equal(jv[0, :len(want)].cpu().numpy().astype(bool), tv)
-            got = tri[0, :len(want)].cpu().numpy()
-            np.testing.assert_allclose(got[tv], arr[p + 'tri'][tv], rtol=1e-9, atol=1e-9)
+        gc.triangulation(frame, arr, p, tri[0].cpu().numpy(), jv[0].cpu().numpy(), len(want))
 
 
 def _first_divergence(s_gpu, s_ref, thr=0.5):

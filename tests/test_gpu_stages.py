@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_checks as gc
 from conftest import ALL_CASES, ALL_CASES_FZ, ROOT, env, load_case, oracle, pkg
 
 pytestmark = pytest.mark.gpu
@@ -74,10 +75,7 @@ def test_gat_layers_vs_reference_activations(variant, name):
             # (i) chained: the layer consumes the HIP path's own previous output
             x = eng.gat_layer(db, l, x, activation=0)
             got = x.cpu().numpy()
-            nh = min(4, H)                         # the fixture holds rows [0:4] and [H:H+4] of the N x HD matrix
-            assert _close(got[:nh], arr[p + 'act%d_head' % l][:nh], 2e-5), (l, 'head rows vs reference')
-            want_en = arr[p + 'act%d_en' % l]
-            assert _close(got[H:H + len(want_en)], want_en, 2e-5), (l, 'edge-node rows vs reference')
+            gc.layer_activations(got, H, arr, p, l)    # the fixture holds rows [0:4] and [H:H+4] of the N x HD matrix
             assert _close(got, inter[l].numpy(), 2e-5), (l, 'all rows vs oracle')
             # (ii) isolated: the layer alone on the oracle's input rows
             if l > 0:
@@ -87,7 +85,7 @@ def test_gat_layers_vs_reference_activations(variant, name):
         # (3e-5 here, 2e-5 on the production path: through this entry point layer 0 runs DENSE, one fp32
         #  chain over all F columns, and the fixture weights multiply the last logits by 25)
         sc = eng.gat_layer(db, prm['gnn_layers'] - 1, x, activation=1).cpu().numpy().reshape(-1)
-        np.testing.assert_allclose(sc, arr[p + 'scores'], rtol=0, atol=3e-5)
+        np.testing.assert_allclose(sc, arr[p + 'scores'], rtol=0, atol=gc.LAYER_SCORES_ATOL)
         logits = eng.gat_layer(db, prm['gnn_layers'] - 1, x, activation=2).cpu().numpy().reshape(-1)
         np.testing.assert_allclose(1.0 / (1.0 + np.exp(-logits.astype(np.float64))), arr[p + 'scores'], rtol=0, atol=3e-5)
 

@@ -76,6 +76,62 @@ int dev_alloc(mpe_ctx *ctx, T **p, size_t count, bool zero = true) {
     return MPE_OK;
 }
 
+// ---- the state objects of the sequence stages (mpe_track_*, mpe_smooth_*, mpe_skel_*, mpe_track_score_*, mpe_calib_*) ----
+
+// What every *_create does around its own part.  fill(st) gets the zeroed host struct: it checks the sizes first (a
+// refusal there comes before anything is allocated on the device), sets the fields and allocates.  When it fails,
+// destroy frees what it got as far as it came and the message of the failure stays the last error.
+template <typename S, typename Fill>
+int create_state(mpe_ctx *ctx, const char *who, S **out, int (*destroy)(mpe_ctx *, S *), Fill fill) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!out) return fail(ctx, MPE_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    DeviceGuard dg(ctx);
+    S *st = new (std::nothrow) S();
+    if (!st) return fail(ctx, MPE_ERR_NOMEM, "%s: out of memory", who);
+    const int rc = fill(st);
+    if (rc) {
+        const std::string why = ctx->err;
+        destroy(ctx, st);
+        ctx->err = why;
+        return rc;
+    }
+    *out = st;
+    return MPE_OK;
+}
+
+template <typename S>
+int reset_state(mpe_ctx *ctx, const char *who, void *stream, S *st, hipError_t (*launch_reset)(hipStream_t, S *)) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "%s: NULL state", who);
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, launch_reset(static_cast<hipStream_t>(stream), st));
+    return MPE_OK;
+}
+
+template <typename S>
+int state_launches(mpe_ctx *ctx, const char *who, const S *st, int64_t *n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "%s: NULL argument", who);
+    *n = st->launches;
+    return MPE_OK;
+}
+
+// What the batch calls on pose rows (track, smooth, skel observe and fit) check alike: the sizes and the pose type the
+// state was made for, the frame count and the flag mode -> MPE_OK with *run = false for a call without frames.
+template <typename S, typename A>
+int check_pose_rows(mpe_ctx *ctx, const char *who, const S *st, const A *a, bool *run) {
+    *run = false;
+    if (a->pcap != st->pcap || a->n_joints != st->J || a->pose_f64 != st->pose_f64)
+        return fail(ctx, MPE_ERR_INVALID, "%s: pcap %d / joints %d / pose_f64 %d, the state was made for %d / %d / %d", who, a->pcap, a->n_joints,
+                    a->pose_f64, st->pcap, st->J, st->pose_f64);
+    if (a->n_frames < 0 || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "%s: n_frames %d / joint_flags %d", who, a->n_frames, a->joint_flags);
+    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "%s: %d frames over 2^23 per call", who, a->n_frames);
+    *run = a->n_frames > 0;
+    return MPE_OK;
+}
+
 void free_linear(mpe_ctx *ctx, Linear *L) {
     dev_free(ctx, L->w);
     dev_free(ctx, L->b);
@@ -1341,68 +1397,45 @@ int mpe_track_destroy(mpe_ctx *ctx, mpe_track_state *st) {
 }
 
 int mpe_track_create(mpe_ctx *ctx, int32_t pcap, int32_t n_joints, int32_t max_gap, int32_t pose_f64, mpe_track_state **out) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_track_create: NULL argument");
-    *out = nullptr;
-    if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || max_gap < 0 || (pose_f64 & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_track_create: bad sizes or pose type");
-    if (pcap > MPE_TRACK_MAX_PERSONS || max_gap > MPE_TRACK_MAX_GAP)
-        return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_create: pcap %d / max_gap %d over %d / %d", pcap, max_gap, MPE_TRACK_MAX_PERSONS,
-                    MPE_TRACK_MAX_GAP);
-    DeviceGuard dg(ctx);
-    mpe_track_state *st = new (std::nothrow) mpe_track_state();
-    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_track_create: out of memory");
-    st->pcap = pcap;
-    st->J = n_joints;
-    st->H = max_gap + 1;
-    st->pose_f64 = pose_f64;
-    const size_t rows = (size_t)st->H * pcap;
-    int rc = MPE_OK;
-    for (int i = 0; i < 2 && !rc; ++i) {
-        rc = dev_alloc(ctx, &st->pose[i], rows * n_joints * 3);
-        if (!rc) rc = dev_alloc(ctx, &st->mask[i], rows);
-        if (!rc) rc = dev_alloc(ctx, &st->id[i], rows);
-        if (!rc) rc = dev_alloc(ctx, &st->child[i], rows);
-    }
-    if (!rc) rc = dev_alloc(ctx, &st->count, 2);
-    if (!rc) rc = dev_alloc(ctx, &st->ws, 1024);
-    if (!rc && track_prepare(pcap) != hipSuccess) rc = fail(ctx, MPE_ERR_HIP, "mpe_track_create: the stage kernel cannot have %d KB of LDS", pcap * pcap / 128);
-    if (rc) {
-        const std::string why = ctx->err;
-        mpe_track_destroy(ctx, st);
-        ctx->err = why;
+    return create_state(ctx, "mpe_track_create", out, mpe_track_destroy, [&](mpe_track_state *st) {
+        if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || max_gap < 0 || (pose_f64 & ~1))
+            return fail(ctx, MPE_ERR_INVALID, "mpe_track_create: bad sizes or pose type");
+        if (pcap > MPE_TRACK_MAX_PERSONS || max_gap > MPE_TRACK_MAX_GAP)
+            return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_create: pcap %d / max_gap %d over %d / %d", pcap, max_gap, MPE_TRACK_MAX_PERSONS,
+                        MPE_TRACK_MAX_GAP);
+        st->pcap = pcap;
+        st->J = n_joints;
+        st->H = max_gap + 1;
+        st->pose_f64 = pose_f64;
+        const size_t rows = (size_t)st->H * pcap;
+        int rc = MPE_OK;
+        for (int i = 0; i < 2 && !rc; ++i) {
+            rc = dev_alloc(ctx, &st->pose[i], rows * n_joints * 3);
+            if (!rc) rc = dev_alloc(ctx, &st->mask[i], rows);
+            if (!rc) rc = dev_alloc(ctx, &st->id[i], rows);
+            if (!rc) rc = dev_alloc(ctx, &st->child[i], rows);
+        }
+        if (!rc) rc = dev_alloc(ctx, &st->count, 2);
+        if (!rc) rc = dev_alloc(ctx, &st->ws, 1024);
+        if (!rc && track_prepare(pcap) != hipSuccess)
+            rc = fail(ctx, MPE_ERR_HIP, "mpe_track_create: the stage kernel cannot have %d KB of LDS", pcap * pcap / 128);
         return rc;
-    }
-    *out = st;
-    return MPE_OK;
+    });
 }
 
-int mpe_track_reset(mpe_ctx *ctx, void *stream, mpe_track_state *st) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_reset: NULL state");
-    DeviceGuard dg(ctx);
-    HIPCHK(ctx, launch_track_reset(static_cast<hipStream_t>(stream), st));
-    return MPE_OK;
-}
+int mpe_track_reset(mpe_ctx *ctx, void *stream, mpe_track_state *st) { return reset_state(ctx, "mpe_track_reset", stream, st, launch_track_reset); }
 
-int mpe_track_launches(mpe_ctx *ctx, const mpe_track_state *st, int64_t *n) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_track_launches: NULL argument");
-    *n = st->launches;
-    return MPE_OK;
-}
+int mpe_track_launches(mpe_ctx *ctx, const mpe_track_state *st, int64_t *n) { return state_launches(ctx, "mpe_track_launches", st, n); }
 
 int mpe_track_batch(mpe_ctx *ctx, void *stream, mpe_track_state *st, const mpe_track_args *a) {
     if (!ctx) return MPE_ERR_INVALID;
     if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: NULL argument");
     DeviceGuard dg(ctx);
-    if (a->pcap != st->pcap || a->n_joints != st->J || a->pose_f64 != st->pose_f64)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: pcap %d / joints %d / pose_f64 %d, the state was made for %d / %d / %d", a->pcap,
-                    a->n_joints, a->pose_f64, st->pcap, st->J, st->pose_f64);
-    if (a->n_frames < 0 || (a->joint_flags & ~1) || !(a->gate > 0.0))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: bad frame count, flag mode or gate");
-    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_batch: %d frames over 2^23 per call", a->n_frames);
-    if (a->n_frames == 0) return MPE_OK;
+    // in front of the shared check, not behind it: a bad gate is MPE_ERR_INVALID whatever the frame count
+    if (!(a->gate > 0.0)) return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: gate %g; it is > 0", a->gate);
+    bool run;
+    const int rc = check_pose_rows(ctx, "mpe_track_batch", st, a, &run);
+    if (rc || !run) return rc;
     if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_link_cost || !a->d_link_gap || !a->d_issued)
         return fail(ctx, MPE_ERR_INVALID, "mpe_track_batch: NULL argument");
     HIPCHK(ctx, launch_track(static_cast<hipStream_t>(stream), st, *a));
@@ -1423,66 +1456,41 @@ int mpe_smooth_destroy(mpe_ctx *ctx, mpe_smooth_state *st) {
 }
 
 int mpe_smooth_create(mpe_ctx *ctx, int32_t pcap, int32_t n_joints, int32_t window, int32_t pose_f64, mpe_smooth_state **out) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_create: NULL argument");
-    *out = nullptr;
-    if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || window < 0 || window > MPE_SMOOTH_MAX_WINDOW || (pose_f64 & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_create: pcap %d / joints %d / window %d / pose_f64 %d; joints 1 .. %d, window 0 .. %d", pcap,
-                    n_joints, window, pose_f64, MPE_MAX_JOINTS, MPE_SMOOTH_MAX_WINDOW);
-    if (pcap > MPE_TRACK_MAX_PERSONS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_smooth_create: pcap %d over %d", pcap, MPE_TRACK_MAX_PERSONS);
-    DeviceGuard dg(ctx);
-    mpe_smooth_state *st = new (std::nothrow) mpe_smooth_state();
-    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_smooth_create: out of memory");
-    st->pcap = pcap;
-    st->J = n_joints;
-    st->W = window;
-    st->pose_f64 = pose_f64;
-    const size_t rows = (size_t)window * pcap;
-    int rc = MPE_OK;
-    for (int i = 0; i < 2 && !rc; ++i) {
-        rc = dev_alloc(ctx, &st->pose[i], rows * n_joints * 3);
-        if (!rc) rc = dev_alloc(ctx, &st->mask[i], rows);
-        if (!rc) rc = dev_alloc(ctx, &st->id[i], rows);
-        if (!rc && rows && hipMemset(st->id[i], 0xFF, rows * sizeof(int32_t)) != hipSuccess)          // -1: nobody is seen yet
-            rc = fail(ctx, MPE_ERR_HIP, "mpe_smooth_create: hipMemset failed");
-    }
-    if (rc) {
-        const std::string why = ctx->err;
-        mpe_smooth_destroy(ctx, st);
-        ctx->err = why;
+    return create_state(ctx, "mpe_smooth_create", out, mpe_smooth_destroy, [&](mpe_smooth_state *st) {
+        if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || window < 0 || window > MPE_SMOOTH_MAX_WINDOW || (pose_f64 & ~1))
+            return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_create: pcap %d / joints %d / window %d / pose_f64 %d; joints 1 .. %d, window 0 .. %d",
+                        pcap, n_joints, window, pose_f64, MPE_MAX_JOINTS, MPE_SMOOTH_MAX_WINDOW);
+        if (pcap > MPE_TRACK_MAX_PERSONS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_smooth_create: pcap %d over %d", pcap, MPE_TRACK_MAX_PERSONS);
+        st->pcap = pcap;
+        st->J = n_joints;
+        st->W = window;
+        st->pose_f64 = pose_f64;
+        const size_t rows = (size_t)window * pcap;
+        int rc = MPE_OK;
+        for (int i = 0; i < 2 && !rc; ++i) {
+            rc = dev_alloc(ctx, &st->pose[i], rows * n_joints * 3);
+            if (!rc) rc = dev_alloc(ctx, &st->mask[i], rows);
+            if (!rc) rc = dev_alloc(ctx, &st->id[i], rows);
+            if (!rc && rows && hipMemset(st->id[i], 0xFF, rows * sizeof(int32_t)) != hipSuccess)      // -1: nobody is seen yet
+                rc = fail(ctx, MPE_ERR_HIP, "mpe_smooth_create: hipMemset failed");
+        }
         return rc;
-    }
-    *out = st;
-    return MPE_OK;
+    });
 }
 
-int mpe_smooth_reset(mpe_ctx *ctx, void *stream, mpe_smooth_state *st) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_reset: NULL state");
-    DeviceGuard dg(ctx);
-    HIPCHK(ctx, launch_smooth_reset(static_cast<hipStream_t>(stream), st));
-    return MPE_OK;
-}
+int mpe_smooth_reset(mpe_ctx *ctx, void *stream, mpe_smooth_state *st) { return reset_state(ctx, "mpe_smooth_reset", stream, st, launch_smooth_reset); }
 
-int mpe_smooth_launches(mpe_ctx *ctx, const mpe_smooth_state *st, int64_t *n) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_launches: NULL argument");
-    *n = st->launches;
-    return MPE_OK;
-}
+int mpe_smooth_launches(mpe_ctx *ctx, const mpe_smooth_state *st, int64_t *n) { return state_launches(ctx, "mpe_smooth_launches", st, n); }
 
 int mpe_smooth_batch(mpe_ctx *ctx, void *stream, mpe_smooth_state *st, const mpe_smooth_args *a) {
     if (!ctx) return MPE_ERR_INVALID;
     if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: NULL argument");
     DeviceGuard dg(ctx);
-    if (a->pcap != st->pcap || a->n_joints != st->J || a->pose_f64 != st->pose_f64)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: pcap %d / joints %d / pose_f64 %d, the state was made for %d / %d / %d", a->pcap,
-                    a->n_joints, a->pose_f64, st->pcap, st->J, st->pose_f64);
-    if (a->n_frames < 0 || (a->joint_flags & ~1) || !(a->lambda >= 0.25 && a->lambda <= 1.0))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: n_frames %d / joint_flags %d / lambda %g; lambda is within [0.25, 1]", a->n_frames,
-                    a->joint_flags, a->lambda);
-    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "mpe_smooth_batch: %d frames over 2^23 per call", a->n_frames);
-    if (a->n_frames == 0) return MPE_OK;
+    if (!(a->lambda >= 0.25 && a->lambda <= 1.0))            // in front of the shared check, as the tracker's gate is
+        return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: lambda %g; it is within [0.25, 1]", a->lambda);
+    bool run;
+    const int rc = check_pose_rows(ctx, "mpe_smooth_batch", st, a, &run);
+    if (rc || !run) return rc;
     if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_poses_out || !a->d_flags_out || !a->d_vel || !a->d_n_samples)
         return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: NULL argument");
     if (a->d_poses_out == a->d_poses) return fail(ctx, MPE_ERR_INVALID, "mpe_smooth_batch: d_poses_out is d_poses (the window reads the raw poses)");
@@ -1505,97 +1513,58 @@ int mpe_skel_destroy(mpe_ctx *ctx, mpe_skel_state *st) {
 }
 
 int mpe_skel_create(mpe_ctx *ctx, const mpe_skel_config *cfg, mpe_skel_state **out) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: NULL argument");
-    *out = nullptr;
-    if (!cfg || !cfg->bones) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: NULL argument");
-    const int32_t pcap = cfg->pcap, n_joints = cfg->n_joints, pose_f64 = cfg->pose_f64, tid_cap = cfg->tid_cap, n_bones = cfg->n_bones;
-    const int32_t *bones = cfg->bones;
-    const double bin_width = cfg->bin_width;
-    if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || (pose_f64 & ~1) || tid_cap < 1 || n_bones < 1 || n_bones > MPE_SKEL_MAX_BONES)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: pcap %d / joints %d / pose_f64 %d / tid_cap %d / n_bones %d; joints 1 .. %d, bones 1 .. %d",
-                    pcap, n_joints, pose_f64, tid_cap, n_bones, MPE_MAX_JOINTS, MPE_SKEL_MAX_BONES);
-    if (!(bin_width > 0.0) || !std::isfinite(bin_width))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: bin_width %g; it is finite and > 0", bin_width);
-    for (int b = 0; b < n_bones; ++b) {
-        const int32_t jp = bones[2 * b], jc = bones[2 * b + 1];
-        if (jp < 0 || jp >= n_joints || jc < 0 || jc >= n_joints || jp == jc)
-            return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: bone %d is (%d, %d); two different joints within 0 .. %d", b, jp, jc, n_joints - 1);
-    }
-    if (pcap > MPE_TRACK_MAX_PERSONS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_skel_create: pcap %d over %d", pcap, MPE_TRACK_MAX_PERSONS);
-    const uint64_t hist_bytes = (uint64_t)tid_cap * n_bones * MPE_SKEL_BINS * sizeof(uint32_t);
-    if (hist_bytes > MPE_SKEL_MAX_HIST_BYTES)
-        return fail(ctx, MPE_ERR_CAPACITY, "mpe_skel_create: tid_cap %d x %d bones need %llu bytes of histogram, over %u", tid_cap, n_bones,
-                    (unsigned long long)hist_bytes, (unsigned)MPE_SKEL_MAX_HIST_BYTES);
-    DeviceGuard dg(ctx);
-    mpe_skel_state *st = new (std::nothrow) mpe_skel_state();
-    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_skel_create: out of memory");
-    st->pcap = pcap;
-    st->J = n_joints;
-    st->pose_f64 = pose_f64;
-    st->tid_cap = tid_cap;
-    st->n_bones = n_bones;
-    st->bin_width = bin_width;
-    const size_t pairs = (size_t)tid_cap * n_bones;
-    int rc = dev_alloc(ctx, &st->bones, (size_t)n_bones * 2);
-    if (!rc) rc = dev_alloc(ctx, &st->hist, pairs * MPE_SKEL_BINS);
-    if (!rc) rc = dev_alloc(ctx, &st->len, pairs);
-    if (!rc) rc = dev_alloc(ctx, &st->count, pairs);
-    if (!rc) rc = dev_alloc(ctx, &st->ctr, 3);
-    std::vector<uint32_t> sched;
-    skel_schedule(bones, n_bones, &sched, st->steps_upto);
-    if (!rc) rc = dev_alloc(ctx, &st->sched, sched.size(), false);
-    if (!rc && (hipMemcpy(st->bones, bones, (size_t)n_bones * 2 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(st->sched, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
-        rc = fail(ctx, MPE_ERR_HIP, "mpe_skel_create: hipMemcpy failed");
-    if (rc) {
-        const std::string why = ctx->err;
-        mpe_skel_destroy(ctx, st);
-        ctx->err = why;
+    return create_state(ctx, "mpe_skel_create", out, mpe_skel_destroy, [&](mpe_skel_state *st) {
+        if (!cfg || !cfg->bones) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: NULL argument");
+        const int32_t pcap = cfg->pcap, n_joints = cfg->n_joints, pose_f64 = cfg->pose_f64, tid_cap = cfg->tid_cap, n_bones = cfg->n_bones;
+        const int32_t *bones = cfg->bones;
+        const double bin_width = cfg->bin_width;
+        if (pcap < 1 || n_joints < 1 || n_joints > MPE_MAX_JOINTS || (pose_f64 & ~1) || tid_cap < 1 || n_bones < 1 || n_bones > MPE_SKEL_MAX_BONES)
+            return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: pcap %d / joints %d / pose_f64 %d / tid_cap %d / n_bones %d; joints 1 .. %d, bones 1 .. %d",
+                        pcap, n_joints, pose_f64, tid_cap, n_bones, MPE_MAX_JOINTS, MPE_SKEL_MAX_BONES);
+        if (!(bin_width > 0.0) || !std::isfinite(bin_width))
+            return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: bin_width %g; it is finite and > 0", bin_width);
+        for (int b = 0; b < n_bones; ++b) {
+            const int32_t jp = bones[2 * b], jc = bones[2 * b + 1];
+            if (jp < 0 || jp >= n_joints || jc < 0 || jc >= n_joints || jp == jc)
+                return fail(ctx, MPE_ERR_INVALID, "mpe_skel_create: bone %d is (%d, %d); two different joints within 0 .. %d", b, jp, jc, n_joints - 1);
+        }
+        if (pcap > MPE_TRACK_MAX_PERSONS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_skel_create: pcap %d over %d", pcap, MPE_TRACK_MAX_PERSONS);
+        const uint64_t hist_bytes = (uint64_t)tid_cap * n_bones * MPE_SKEL_BINS * sizeof(uint32_t);
+        if (hist_bytes > MPE_SKEL_MAX_HIST_BYTES)
+            return fail(ctx, MPE_ERR_CAPACITY, "mpe_skel_create: tid_cap %d x %d bones need %llu bytes of histogram, over %u", tid_cap, n_bones,
+                        (unsigned long long)hist_bytes, (unsigned)MPE_SKEL_MAX_HIST_BYTES);
+        st->pcap = pcap;
+        st->J = n_joints;
+        st->pose_f64 = pose_f64;
+        st->tid_cap = tid_cap;
+        st->n_bones = n_bones;
+        st->bin_width = bin_width;
+        const size_t pairs = (size_t)tid_cap * n_bones;
+        int rc = dev_alloc(ctx, &st->bones, (size_t)n_bones * 2);
+        if (!rc) rc = dev_alloc(ctx, &st->hist, pairs * MPE_SKEL_BINS);
+        if (!rc) rc = dev_alloc(ctx, &st->len, pairs);
+        if (!rc) rc = dev_alloc(ctx, &st->count, pairs);
+        if (!rc) rc = dev_alloc(ctx, &st->ctr, 3);
+        std::vector<uint32_t> sched;
+        skel_schedule(bones, n_bones, &sched, st->steps_upto);
+        if (!rc) rc = dev_alloc(ctx, &st->sched, sched.size(), false);
+        if (!rc && (hipMemcpy(st->bones, bones, (size_t)n_bones * 2 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(st->sched, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
+            rc = fail(ctx, MPE_ERR_HIP, "mpe_skel_create: hipMemcpy failed");
         return rc;
-    }
-    *out = st;
-    return MPE_OK;
+    });
 }
 
-int mpe_skel_reset(mpe_ctx *ctx, void *stream, mpe_skel_state *st) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_reset: NULL state");
-    DeviceGuard dg(ctx);
-    HIPCHK(ctx, launch_skel_reset(static_cast<hipStream_t>(stream), st));
-    return MPE_OK;
-}
+int mpe_skel_reset(mpe_ctx *ctx, void *stream, mpe_skel_state *st) { return reset_state(ctx, "mpe_skel_reset", stream, st, launch_skel_reset); }
 
-int mpe_skel_launches(mpe_ctx *ctx, const mpe_skel_state *st, int64_t *n) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_launches: NULL argument");
-    *n = st->launches;
-    return MPE_OK;
-}
-
-namespace {
-
-// what observe and fit check alike -> MPE_OK with *run = false for a call without frames
-int skel_check(mpe_ctx *ctx, const char *who, const mpe_skel_state *st, const mpe_skel_args *a, bool *run) {
-    *run = false;
-    if (a->pcap != st->pcap || a->n_joints != st->J || a->pose_f64 != st->pose_f64)
-        return fail(ctx, MPE_ERR_INVALID, "%s: pcap %d / joints %d / pose_f64 %d, the state was made for %d / %d / %d", who, a->pcap, a->n_joints,
-                    a->pose_f64, st->pcap, st->J, st->pose_f64);
-    if (a->n_frames < 0 || (a->joint_flags & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "%s: n_frames %d / joint_flags %d", who, a->n_frames, a->joint_flags);
-    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "%s: %d frames over 2^23 per call", who, a->n_frames);
-    *run = a->n_frames > 0;
-    return MPE_OK;
-}
-
-}  // namespace
+int mpe_skel_launches(mpe_ctx *ctx, const mpe_skel_state *st, int64_t *n) { return state_launches(ctx, "mpe_skel_launches", st, n); }
 
 int mpe_skel_observe_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const mpe_skel_args *a) {
     if (!ctx) return MPE_ERR_INVALID;
     if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_observe_batch: NULL argument");
     DeviceGuard dg(ctx);
     bool run;
-    const int rc = skel_check(ctx, "mpe_skel_observe_batch", st, a, &run);
+    const int rc = check_pose_rows(ctx, "mpe_skel_observe_batch", st, a, &run);
     if (rc || !run) return rc;
     if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_observe_batch: NULL argument");
     HIPCHK(ctx, launch_skel_observe(static_cast<hipStream_t>(stream), st, *a));
@@ -1643,7 +1612,7 @@ int mpe_skel_fit_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const mpe
     if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: NULL argument");
     DeviceGuard dg(ctx);
     bool run;
-    const int rc = skel_check(ctx, "mpe_skel_fit_batch", st, a, &run);
+    const int rc = check_pose_rows(ctx, "mpe_skel_fit_batch", st, a, &run);
     if (rc) return rc;
     if (a->iters < 1 || a->iters > MPE_SKEL_MAX_ITERS)
         return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: iters %d; 1 .. %d", a->iters, MPE_SKEL_MAX_ITERS);
@@ -1673,57 +1642,39 @@ int mpe_track_score_destroy(mpe_ctx *ctx, mpe_track_score_state *st) {
 
 int mpe_track_score_create(mpe_ctx *ctx, int32_t pcap, int32_t gcap, int32_t gid_cap, int32_t tid_cap, int32_t max_frames,
                            mpe_track_score_state **out) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_create: NULL argument");
-    *out = nullptr;
-    if (pcap < 1 || gcap < 1 || gid_cap < 1 || tid_cap < 1 || max_frames < 1)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_create: pcap %d / gcap %d / gid_cap %d / tid_cap %d / max_frames %d, all >= 1", pcap, gcap,
-                    gid_cap, tid_cap, max_frames);
-    if (pcap > MPE_TRACK_MAX_PERSONS || gcap > MPE_TRACK_MAX_PERSONS)
-        return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_score_create: pcap %d / gcap %d over %d", pcap, gcap, MPE_TRACK_MAX_PERSONS);
-    if ((int64_t)gid_cap * tid_cap > MPE_TRACK_SCORE_MAX_TABLE)
-        return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_score_create: gid_cap %d * tid_cap %d over %d", gid_cap, tid_cap, MPE_TRACK_SCORE_MAX_TABLE);
-    DeviceGuard dg(ctx);
-    mpe_track_score_state *st = new (std::nothrow) mpe_track_score_state();
-    if (!st) return fail(ctx, MPE_ERR_NOMEM, "mpe_track_score_create: out of memory");
-    st->pcap = pcap;
-    st->gcap = gcap;
-    st->gid_cap = gid_cap;
-    st->tid_cap = tid_cap;
-    st->max_frames = max_frames;
-    int rc = dev_alloc(ctx, &st->totals, MPE_TS_TOTALS);
-    if (!rc) rc = dev_alloc(ctx, &st->ident, (size_t)4 * gid_cap);
-    if (!rc) rc = dev_alloc(ctx, &st->pred_count, tid_cap);
-    if (!rc) rc = dev_alloc(ctx, &st->table, (size_t)gid_cap * tid_cap);
-    if (!rc) rc = dev_alloc(ctx, &st->rec, (size_t)max_frames * gid_cap, false);
-    if (!rc) rc = dev_alloc(ctx, &st->fstat, (size_t)max_frames * 8, false);
-    if (!rc) rc = dev_alloc(ctx, &st->mmask, (size_t)max_frames * 2, false);
-    if (!rc) rc = dev_alloc(ctx, &st->merr, (size_t)max_frames * pcap, false);
-    if (!rc && hipMemset(st->ident, 0xFF, gid_cap * sizeof(int32_t)) != hipSuccess)                  // last = -1: no track yet
-        rc = fail(ctx, MPE_ERR_HIP, "mpe_track_score_create: hipMemset failed");
-    if (rc) {
-        const std::string why = ctx->err;
-        mpe_track_score_destroy(ctx, st);
-        ctx->err = why;
+    return create_state(ctx, "mpe_track_score_create", out, mpe_track_score_destroy, [&](mpe_track_score_state *st) {
+        if (pcap < 1 || gcap < 1 || gid_cap < 1 || tid_cap < 1 || max_frames < 1)
+            return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_create: pcap %d / gcap %d / gid_cap %d / tid_cap %d / max_frames %d, all >= 1", pcap, gcap,
+                        gid_cap, tid_cap, max_frames);
+        if (pcap > MPE_TRACK_MAX_PERSONS || gcap > MPE_TRACK_MAX_PERSONS)
+            return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_score_create: pcap %d / gcap %d over %d", pcap, gcap, MPE_TRACK_MAX_PERSONS);
+        if ((int64_t)gid_cap * tid_cap > MPE_TRACK_SCORE_MAX_TABLE)
+            return fail(ctx, MPE_ERR_CAPACITY, "mpe_track_score_create: gid_cap %d * tid_cap %d over %d", gid_cap, tid_cap, MPE_TRACK_SCORE_MAX_TABLE);
+        st->pcap = pcap;
+        st->gcap = gcap;
+        st->gid_cap = gid_cap;
+        st->tid_cap = tid_cap;
+        st->max_frames = max_frames;
+        int rc = dev_alloc(ctx, &st->totals, MPE_TS_TOTALS);
+        if (!rc) rc = dev_alloc(ctx, &st->ident, (size_t)4 * gid_cap);
+        if (!rc) rc = dev_alloc(ctx, &st->pred_count, tid_cap);
+        if (!rc) rc = dev_alloc(ctx, &st->table, (size_t)gid_cap * tid_cap);
+        if (!rc) rc = dev_alloc(ctx, &st->rec, (size_t)max_frames * gid_cap, false);
+        if (!rc) rc = dev_alloc(ctx, &st->fstat, (size_t)max_frames * 8, false);
+        if (!rc) rc = dev_alloc(ctx, &st->mmask, (size_t)max_frames * 2, false);
+        if (!rc) rc = dev_alloc(ctx, &st->merr, (size_t)max_frames * pcap, false);
+        if (!rc && hipMemset(st->ident, 0xFF, gid_cap * sizeof(int32_t)) != hipSuccess)                  // last = -1: no track yet
+            rc = fail(ctx, MPE_ERR_HIP, "mpe_track_score_create: hipMemset failed");
         return rc;
-    }
-    *out = st;
-    return MPE_OK;
+    });
 }
 
 int mpe_track_score_reset(mpe_ctx *ctx, void *stream, mpe_track_score_state *st) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_reset: NULL state");
-    DeviceGuard dg(ctx);
-    HIPCHK(ctx, launch_track_score_reset(static_cast<hipStream_t>(stream), st));
-    return MPE_OK;
+    return reset_state(ctx, "mpe_track_score_reset", stream, st, launch_track_score_reset);
 }
 
 int mpe_track_score_launches(mpe_ctx *ctx, const mpe_track_score_state *st, int64_t *n) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_track_score_launches: NULL argument");
-    *n = st->launches;
-    return MPE_OK;
+    return state_launches(ctx, "mpe_track_score_launches", st, n);
 }
 
 int mpe_track_score_batch(mpe_ctx *ctx, void *stream, mpe_track_score_state *st, const mpe_track_score_args *a) {
@@ -2082,32 +2033,19 @@ int mpe_calib_destroy(mpe_ctx *ctx, mpe_calib_state *st) {
 }
 
 int mpe_calib_create(mpe_ctx *ctx, mpe_calib_state **out) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!out) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_create: NULL argument");
-    *out = nullptr;
-    DeviceGuard dg(ctx);
-    mpe_calib_state *st = new (std::nothrow) mpe_calib_state();
-    if (st) st->host = new (std::nothrow) mpe_calib_host();
-    if (!st || !st->host) {
-        delete st;
-        return fail(ctx, MPE_ERR_NOMEM, "mpe_calib_create: out of memory");
-    }
-    st->V = ctx->cfg.n_cameras;
-    st->max_frames = ctx->cfg.max_frames;
-    int rc = dev_alloc(ctx, &st->E, (size_t)st->V * 12);
-    if (!rc) rc = dev_alloc(ctx, &st->acc, (size_t)st->V * MPE_CALIB_SUMS);
-    if (!rc) rc = dev_alloc(ctx, &st->n_obs, st->V);
-    if (!rc) rc = dev_alloc(ctx, &st->n_skipped, st->V);
-    if (!rc) rc = dev_alloc(ctx, &st->S, calib_workspace_doubles(st->max_frames, st->V), false);
-    if (!rc) rc = calib_start(ctx, nullptr, st, &ctx->hcfg.P[0][0]);
-    if (rc) {
-        const std::string why = ctx->err;
-        mpe_calib_destroy(ctx, st);
-        ctx->err = why;
+    return create_state(ctx, "mpe_calib_create", out, mpe_calib_destroy, [&](mpe_calib_state *st) {
+        st->host = new (std::nothrow) mpe_calib_host();
+        if (!st->host) return fail(ctx, MPE_ERR_NOMEM, "mpe_calib_create: out of memory");
+        st->V = ctx->cfg.n_cameras;
+        st->max_frames = ctx->cfg.max_frames;
+        int rc = dev_alloc(ctx, &st->E, (size_t)st->V * 12);
+        if (!rc) rc = dev_alloc(ctx, &st->acc, (size_t)st->V * MPE_CALIB_SUMS);
+        if (!rc) rc = dev_alloc(ctx, &st->n_obs, st->V);
+        if (!rc) rc = dev_alloc(ctx, &st->n_skipped, st->V);
+        if (!rc) rc = dev_alloc(ctx, &st->S, calib_workspace_doubles(st->max_frames, st->V), false);
+        if (!rc) rc = calib_start(ctx, nullptr, st, &ctx->hcfg.P[0][0]);
         return rc;
-    }
-    *out = st;
-    return MPE_OK;
+    });
 }
 
 int mpe_calib_reset(mpe_ctx *ctx, void *stream, mpe_calib_state *st) {
@@ -2136,12 +2074,7 @@ int mpe_calib_get_extrinsics(mpe_ctx *ctx, const mpe_calib_state *st, double *ac
     return MPE_OK;
 }
 
-int mpe_calib_launches(mpe_ctx *ctx, const mpe_calib_state *st, int64_t *n) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st || !n) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_launches: NULL argument");
-    *n = st->launches;
-    return MPE_OK;
-}
+int mpe_calib_launches(mpe_ctx *ctx, const mpe_calib_state *st, int64_t *n) { return state_launches(ctx, "mpe_calib_launches", st, n); }
 
 int mpe_calib_batch(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_batch *b, const mpe_calib_args *a) {
     int rc = check_batch(ctx, b);

@@ -17,6 +17,7 @@
 // would accept.  Of the columns >= R (all zero) only the lowest unused one is tried: the others give the same sums
 // later in itertools order.  The search stack lives in registers, lane d holding depth d's entry.
 #include "mpe_internal.h"
+#include "pose_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -30,12 +31,9 @@ constexpr int EVAL_NMAX = 64;                 // max(G, R) the device search tak
 // tell such rows apart; a few seconds of one wave at worst
 constexpr long long EVAL_NODE_BUDGET = 1ll << 24;
 
-struct EvalK {
-    int pcap, J, gcap, pose_f64, joint_flags;
+struct EvalK : PoseRows {             // no track ids here: PoseRows::tid stays null
+    int gcap;
     uint32_t used;
-    const void *poses;
-    const uint8_t *flags;
-    const int32_t *n_persons;
     const float *gt_xyz;
     const uint8_t *gt_joint;
     const int32_t *n_gt_in;
@@ -47,10 +45,6 @@ struct EvalK {
     int32_t *n_gt, *n_res, *status;
 };
 
-__device__ inline bool present(const EvalK &a, size_t fp, int j) {
-    return !a.joint_flags || a.flags[fp * a.J + j] != 0;
-}
-
 __device__ double pair_error(const EvalK &a, size_t fp, size_t fg) {
     const uint8_t *gj = a.gt_joint + fg * a.J;
     const float *gt = a.gt_xyz + fg * a.J * 3;
@@ -59,7 +53,7 @@ __device__ double pair_error(const EvalK &a, size_t fp, size_t fg) {
         double tot = 0.0;
         int n = 0;
         for (int j = 0; j < a.J; ++j) {
-            if (!gj[j] || !((a.used >> j) & 1u) || !present(a, fp, j)) continue;
+            if (!gj[j] || !((a.used >> j) & 1u) || !joint_flag(a, fp, j)) continue;
             const double dx = p[3 * j] - (double)gt[3 * j];
             const double dy = p[3 * j + 1] - (double)gt[3 * j + 1];
             const double dz = p[3 * j + 2] - (double)gt[3 * j + 2];
@@ -75,7 +69,7 @@ __device__ double pair_error(const EvalK &a, size_t fp, size_t fg) {
     float tot = 0.f;
     int n = 0;
     for (int j = 0; j < a.J; ++j) {
-        if (!gj[j] || !((a.used >> j) & 1u) || !present(a, fp, j)) continue;
+        if (!gj[j] || !((a.used >> j) & 1u) || !joint_flag(a, fp, j)) continue;
         const float dx = p[3 * j] - gt[3 * j];
         const float dy = p[3 * j + 1] - gt[3 * j + 1];
         const float dz = p[3 * j + 2] - gt[3 * j + 2];
@@ -96,7 +90,7 @@ __global__ void __launch_bounds__(256) k_eval_table(EvalK a) {
     if (threadIdx.x == 0) {
         int R = 0;
         if (!skip) {
-            const int np = min(max(a.n_persons[f], 0), a.pcap);
+            const int np = rows_in_frame(a, f);
             for (int p = 0; p < np; ++p)
                 if (a.joint_flags || a.flags[(size_t)f * a.pcap + p]) s_det[R++] = p;
         }
@@ -117,7 +111,7 @@ __global__ void __launch_bounds__(256) k_eval_table(EvalK a) {
             for (int g = 0; g < G && !bad; ++g) {
                 const uint8_t *gj = a.gt_joint + ((size_t)f * a.gcap + g) * a.J;
                 for (int j = 0; j < a.J; ++j)
-                    if (gj[j] && ((a.used >> j) & 1u) && !present(a, fp, j)) { bad = 1; break; }
+                    if (gj[j] && ((a.used >> j) & 1u) && !joint_flag(a, fp, j)) { bad = 1; break; }
             }
         }
         a.invalid[o] = bad;
@@ -222,8 +216,8 @@ __global__ void __launch_bounds__(64) k_eval_assign(EvalK a) {
 }  // namespace
 
 hipError_t launch_eval(hipStream_t s, const mpe_eval_args &x) {
-    EvalK a{x.pcap, x.n_joints, x.gcap, x.pose_f64, x.joint_flags, x.used_joint_mask, x.d_poses, x.d_flags,
-            x.d_n_persons, x.d_gt_xyz, x.d_gt_joint, x.d_n_gt_in, x.d_skip, x.d_table, x.d_assign, x.d_err,
+    EvalK a{{x.n_frames, x.pcap, x.n_joints, x.pose_f64, x.joint_flags, x.d_poses, x.d_flags, x.d_n_persons, nullptr},
+            x.gcap, x.used_joint_mask, x.d_gt_xyz, x.d_gt_joint, x.d_n_gt_in, x.d_skip, x.d_table, x.d_assign, x.d_err,
             x.d_invalid, x.d_n_gt, x.d_n_res, x.d_status};
     hipLaunchKernelGGL(k_eval_table, dim3(x.n_frames), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();

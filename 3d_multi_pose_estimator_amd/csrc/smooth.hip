@@ -10,6 +10,7 @@
 // k_smooth_carry   writes the last W virtual frames (ids, masks, coordinates widened to f64) into the other half of the
 //                  state.  It reads what the filter reads and writes nothing the filter reads.
 #include "mpe_internal.h"
+#include "pose_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -20,14 +21,10 @@ namespace {
 constexpr int SMO_PCAP = MPE_TRACK_MAX_PERSONS;
 constexpr int SMO_AGES = MPE_SMOOTH_MAX_WINDOW + 1;
 
-struct SmoothK {
-    int n_frames, pcap, J, W, joint_flags, fill;
+struct SmoothK : PoseRows {
+    int W, fill;
     uint32_t jmask;                  // joint_mask, cut to the J joints
     double lambda;
-    const void *poses;
-    const uint8_t *flags;
-    const int32_t *n_persons;
-    const int32_t *tid;
     void *poses_out;
     uint8_t *flags_out;
     double *vel;
@@ -52,18 +49,12 @@ __device__ inline void row_of(const SmoothK &a, int vf, int p, int32_t *id, uint
         return;
     }
     const int f = vf - a.W;
-    if (p >= min(max(a.n_persons[f], 0), a.pcap)) return;
+    if (p >= rows_in_frame(a, f)) return;
     const size_t fp = (size_t)f * a.pcap + p;
     const int32_t t = a.tid[fp];
     if (t < 0) return;
-    uint32_t m = 0;
-    if (!a.joint_flags) {
-        if (!a.flags[fp]) return;
-        m = a.J >= 32 ? 0xFFFFFFFFu : (1u << a.J) - 1u;
-    } else {
-        for (int j = 0; j < a.J; ++j)
-            if (a.flags[fp * a.J + j]) m |= 1u << j;
-    }
+    const uint32_t m = flag_mask(a, fp);
+    if (!a.joint_flags && !m) return;                    // per-joint flags: a row with an id and no joint is still a row
     *id = t;
     *mask = m;
 }
@@ -73,13 +64,6 @@ __device__ inline double coord_of(const SmoothK &a, int vf, int row, int c) {
     if (vf < a.W) return a.o_pose[((size_t)vf * a.pcap + row) * a.J * 3 + c];
     return (double)static_cast<const T *>(a.poses)[((size_t)(vf - a.W) * a.pcap + row) * a.J * 3 + c];
 }
-
-template <typename T>
-struct Bits;
-template <>
-struct Bits<float> { typedef uint32_t type; };
-template <>
-struct Bits<double> { typedef uint64_t type; };
 
 template <typename T>
 __global__ void __launch_bounds__(256) k_smooth_filter(SmoothK a) {
@@ -129,7 +113,7 @@ __global__ void __launch_bounds__(256) k_smooth_filter(SmoothK a) {
                 if (q < 0 || !((s_mask[age * pcap + q] >> j) & 1u)) continue;
                 double x[3];
                 for (int c = 0; c < 3; ++c) x[c] = coord_of<T>(a, v - age, q, 3 * j + c);
-                if (!(__builtin_isfinite(x[0]) && __builtin_isfinite(x[1]) && __builtin_isfinite(x[2]))) continue;
+                if (!finite3(x[0], x[1], x[2])) continue;
                 if (n == 0) {
                     for (int c = 0; c < 3; ++c) xr[c] = x[c];
                     now = age == 0;
@@ -203,8 +187,9 @@ hipError_t launch_smooth_reset(hipStream_t s, mpe_smooth_state *st) {
 hipError_t launch_smooth(hipStream_t s, mpe_smooth_state *st, const mpe_smooth_args &x) {
     const int o = st->cur, n = o ^ 1, J = st->J;
     SmoothK a{};
-    a.n_frames = x.n_frames; a.pcap = st->pcap; a.J = J; a.W = st->W; a.joint_flags = x.joint_flags; a.fill = x.fill != 0;
-    a.jmask = x.joint_mask & (J >= 32 ? 0xFFFFFFFFu : (1u << J) - 1u);
+    a.n_frames = x.n_frames; a.pcap = st->pcap; a.J = J; a.pose_f64 = st->pose_f64; a.joint_flags = x.joint_flags;
+    a.W = st->W; a.fill = x.fill != 0;
+    a.jmask = x.joint_mask & joint_bits(J);
     a.lambda = x.lambda;
     a.poses = x.d_poses; a.flags = x.d_flags; a.n_persons = x.d_n_persons; a.tid = x.d_track_id;
     a.poses_out = x.d_poses_out; a.flags_out = x.d_flags_out; a.vel = x.d_vel; a.n_samples = x.d_n_samples;

@@ -22,6 +22,7 @@
 //                 from segment to segment (a value read there is final or a pointer further back: either serves) and
 //                 hands the ids of the last H frames to the next history.
 #include "mpe_internal.h"
+#include "pose_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -34,14 +35,11 @@ constexpr int TRK_CHILD = 0x100;
 constexpr int TRK_ROW = 0x7f;
 constexpr int TRK_SEG_WORDS = 8192;                  // rows of one k_track_resolve segment (32 KB of LDS)
 
-struct TrackK {
-    int n_frames, pcap, J, H, pose_f64, joint_flags;
+struct TrackK : PoseRows {           // PoseRows::tid stays null: the ids are this stage's output
+    int H;
     uint32_t used;                   // used_joint_mask, cut to the J joints
     double gate;
-    const void *poses;
-    const uint8_t *flags;
-    const int32_t *n_persons;
-    int32_t *tid;
+    int32_t *ids;                    // d_track_id, the working storage described above
     double *cost;
     int32_t *gap;
     int32_t *issued_out;
@@ -64,13 +62,8 @@ constexpr int TRK_BIRTH_BLOCKS = 1024;
 
 // used joints present in row p of batch frame f; 0: not a detection
 __device__ inline uint32_t row_mask(const TrackK &a, int f, int p) {
-    if (p >= min(max(a.n_persons[f], 0), a.pcap)) return 0u;
-    const size_t fp = (size_t)f * a.pcap + p;
-    if (!a.joint_flags) return a.flags[fp] ? a.used : 0u;
-    uint32_t m = 0;
-    for (int j = 0; j < a.J; ++j)
-        if (a.flags[fp * a.J + j]) m |= 1u << j;
-    return m & a.used;
+    if (p >= rows_in_frame(a, f)) return 0u;
+    return flag_mask(a, (size_t)f * a.pcap + p) & a.used;
 }
 
 template <typename TA, typename TB>
@@ -97,7 +90,7 @@ __global__ void __launch_bounds__(256) k_track_init(TrackK a) {
     if (i >= a.n_frames * a.pcap) return;
     const int f = i / a.pcap, p = i - f * a.pcap;
     const bool det = row_mask(a, f, p) != 0;
-    a.tid[i] = det ? 0 : -1;
+    a.ids[i] = det ? 0 : -1;
     a.gap[i] = det ? 0 : -1;
     a.cost[i] = -1.0;
 }
@@ -131,7 +124,7 @@ __global__ void __launch_bounds__(256) k_track_stage(TrackK a, int g) {
             const size_t o = (size_t)u * a.pcap + tx;
             if (!a.o_child[o]) cm = a.o_mask[o];
         } else {
-            const int32_t w = a.tid[(size_t)(u - a.H) * a.pcap + tx];
+            const int32_t w = a.ids[(size_t)(u - a.H) * a.pcap + tx];
             if (w >= 0 && !(w & TRK_CHILD)) cm = row_mask(a, u - a.H, tx);
         }
     }
@@ -190,9 +183,9 @@ __global__ void __launch_bounds__(256) k_track_stage(TrackK a, int g) {
             const size_t o = (size_t)f * a.pcap + p;
             a.gap[o] = g;
             a.cost[o] = m;
-            atomicOr(&a.tid[o], q);
+            atomicOr(&a.ids[o], q);
             if (hist) a.o_child[(size_t)u * a.pcap + q] = 1;
-            else atomicOr(&a.tid[(size_t)(u - a.H) * a.pcap + q], TRK_CHILD);
+            else atomicOr(&a.ids[(size_t)(u - a.H) * a.pcap + q], TRK_CHILD);
             bc[k] = INFINITY;
             bi[k] = -1;
         }
@@ -212,7 +205,7 @@ __global__ void __launch_bounds__(256) k_track_carry(TrackK a) {
             a.n_child[n] = a.o_child[o];
             a.n_id[n] = a.o_id[o];
         } else {
-            const int32_t w = a.tid[(size_t)(vf - a.H) * a.pcap + p];
+            const int32_t w = a.ids[(size_t)(vf - a.H) * a.pcap + p];
             a.n_mask[n] = row_mask(a, vf - a.H, p);
             a.n_child[n] = w >= 0 && (w & TRK_CHILD) ? 1 : 0;
             a.n_id[n] = -1;                              // detections: k_track_finish
@@ -268,7 +261,7 @@ __global__ void __launch_bounds__(256) k_track_birth_number(TrackK a) {
     const int incl = block_scan(mine, s);
     int id = s_base + incl - mine;
     for (size_t i = (size_t)f0 * a.pcap; i < (size_t)f1 * a.pcap; ++i)
-        if (a.gap[i] == 0) a.tid[i] = id++;
+        if (a.gap[i] == 0) a.ids[i] = id++;
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) {
         *a.n_count = s_base + incl;
         *a.issued_out = s_base + incl;
@@ -281,7 +274,7 @@ __global__ void __launch_bounds__(256) k_track_resolve(TrackK a) {
     const int v0 = a.H + f0;
     for (int i = threadIdx.x; i < n; i += 256) {
         const size_t o = (size_t)f0 * a.pcap + i;
-        const int g = a.gap[o], w = a.tid[o];
+        const int g = a.gap[o], w = a.ids[o];
         s_v[i] = g > 0 ? -2 - ((v0 + i / a.pcap - g) * TRK_PCAP + (w & TRK_ROW)) : w;
     }
     __syncthreads();
@@ -297,20 +290,20 @@ __global__ void __launch_bounds__(256) k_track_resolve(TrackK a) {
         }
         if (!__syncthreads_or(moved)) break;
     }
-    for (int i = threadIdx.x; i < n; i += 256) a.tid[(size_t)f0 * a.pcap + i] = s_v[i];
+    for (int i = threadIdx.x; i < n; i += 256) a.ids[(size_t)f0 * a.pcap + i] = s_v[i];
 }
 
 __global__ void __launch_bounds__(256) k_track_finish(TrackK a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_frames * a.pcap) return;
-    int w = a.tid[i];
+    int w = a.ids[i];
     if (w < -1) {
         while (w < -1) {
             const int t = -2 - w, vf = t / TRK_PCAP, row = t & TRK_ROW;
             w = vf < a.H ? a.o_id[(size_t)vf * a.pcap + row]
-                         : __hip_atomic_load(&a.tid[(size_t)(vf - a.H) * a.pcap + row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                         : __hip_atomic_load(&a.ids[(size_t)(vf - a.H) * a.pcap + row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        __hip_atomic_store(&a.tid[i], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&a.ids[i], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const int f = i / a.pcap, k = f + a.H - a.n_frames;
     if (k >= 0 && w >= 0) a.n_id[(size_t)k * a.pcap + (i - f * a.pcap)] = w;
@@ -348,10 +341,10 @@ hipError_t launch_track(hipStream_t s, mpe_track_state *st, const mpe_track_args
     const int o = st->cur, n = o ^ 1, J = st->J;
     TrackK a{};
     a.n_frames = x.n_frames; a.pcap = st->pcap; a.J = J; a.H = st->H; a.pose_f64 = st->pose_f64; a.joint_flags = x.joint_flags;
-    a.used = x.used_joint_mask & (J >= 32 ? 0xFFFFFFFFu : (1u << J) - 1u);
+    a.used = x.used_joint_mask & joint_bits(J);
     a.gate = x.gate;
     a.poses = x.d_poses; a.flags = x.d_flags; a.n_persons = x.d_n_persons;
-    a.tid = x.d_track_id; a.cost = x.d_link_cost; a.gap = x.d_link_gap; a.issued_out = x.d_issued;
+    a.ids = x.d_track_id; a.cost = x.d_link_cost; a.gap = x.d_link_gap; a.issued_out = x.d_issued;
     a.o_pose = st->pose[o]; a.o_mask = st->mask[o]; a.o_id = st->id[o]; a.o_child = st->child[o]; a.o_count = st->count + o;
     a.n_pose = st->pose[n]; a.n_mask = st->mask[n]; a.n_id = st->id[n]; a.n_child = st->child[n]; a.n_count = st->count + n;
     a.ws = st->ws;

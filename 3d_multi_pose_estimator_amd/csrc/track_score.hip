@@ -13,6 +13,7 @@
 // Integer atomics only: every output is the same whatever the order the hardware takes.  The one-to-one pairing behind
 // IDTP is not here: it runs once per recording on the host (assign_int.h, called by mpe_track_score_result).
 #include "mpe_internal.h"
+#include "pose_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -26,11 +27,10 @@ enum { T_FRAMES, T_NGT, T_NPRED, T_TP, T_FP, T_FN, T_IDSW, T_FRAG, T_IGN, T_OVER
 static_assert(T_STATUS + 1 == MPE_TS_TOTALS, "totals layout");
 static_assert(TS_CAP == 2 * TS_WAVE, "two rows per lane");
 
-struct TsK {
-    int n_frames, pcap, gcap, gid_cap, tid_cap, joint_flags;
+struct TsK : PoseRows {               // no coordinates here: PoseRows::poses stays null, J and pose_f64 0
+    int gcap, gid_cap, tid_cap;
     double thr;
-    const uint8_t *flags;
-    const int32_t *n_persons, *tid, *assign;
+    const int32_t *assign;
     const double *err;
     const uint8_t *invalid;
     const int32_t *n_res, *n_gt, *gt_id;
@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(TS_WAVE) k_ts_frame(TsK a) {
         if (lane < 2) a.mmask[(size_t)f * 2 + lane] = 0;
         return;
     }
-    const int n_p = min(max(a.n_persons[f], 0), pcap), n_g = min(max(a.n_gt[f], 0), gcap);
+    const int n_p = rows_in_frame(a, f), n_g = min(max(a.n_gt[f], 0), gcap);
     int n_det = n_p;
     if (!a.joint_flags) {
         n_det = 0;

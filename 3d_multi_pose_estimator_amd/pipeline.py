@@ -1016,15 +1016,7 @@ class Engine:
         B = db.n_frames
         if mode not in ('mlp', 'tri'):
             raise ValueError('mode must be mlp or tri')
-        want = torch.float32 if mode == 'mlp' else torch.float64
-        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, self.J, 3):
-            raise ValueError('poses must be %s [%d,%d,%d,3]' % (want, B, self.pcap, self.J))
-        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap) if mode == 'mlp' else (B, self.pcap, self.J)):
-            raise ValueError('flags do not match mode %s' % mode)
-        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
-            raise ValueError('n_persons must be int32 [%d]' % B)
-        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous()):
-            raise ValueError('poses, flags and n_persons must be contiguous')
+        _check_pose_rows(self.J, self.pcap, mode == 'tri', mode == 'tri', poses, flags, n_persons, B=B)
         on_device = isinstance(gt['xyz'], torch.Tensor)          # Engine.ground_truth's tensors are taken as they are
         if gt['xyz'].shape[0] != B or (not on_device and np.any(np.asarray(gt['n']) > gt['xyz'].shape[1])):
             raise ValueError('ground truth for %d frames, batch has %d' % (gt['xyz'].shape[0], B))
@@ -1102,17 +1094,9 @@ class Engine:
         if kind not in kinds:
             raise ValueError('kind must be ' + ' or '.join((', '.join(kinds[:-1]), kinds[-1])))
         tri = kind == 'triang'
-        want = torch.float64 if tri else torch.float32
-        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, self.J, 3):
-            raise ValueError('poses must be %s [%d,%d,%d,3]' % (want, B, self.pcap, self.J))
-        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, self.J) if tri else (B, self.pcap)):
-            raise ValueError('flags do not match kind %s' % kind)
-        if persons.dtype != torch.int32 or tuple(persons.shape) != (B, self.pcap, self.V):
-            raise ValueError('persons must be int32 [%d,%d,%d]' % (B, self.pcap, self.V))
-        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
-            raise ValueError('n_persons must be int32 [%d]' % B)
-        if not (poses.is_contiguous() and flags.is_contiguous() and persons.is_contiguous() and n_persons.is_contiguous()):
-            raise ValueError('persons, n_persons, poses and flags must be contiguous')
+        _check_pose_rows(self.J, self.pcap, tri, tri, poses, flags, n_persons, B=B)
+        if persons.dtype != torch.int32 or tuple(persons.shape) != (B, self.pcap, self.V) or not persons.is_contiguous():
+            raise ValueError('persons must be int32 [%d,%d,%d], contiguous' % (B, self.pcap, self.V))
         if joint_mask is None:
             joint_mask = {'est': sum(1 << j for j in self.params.used_joints), 'triang': (1 << self.J) - 1,
                           'gt': 1 << int(list(self.params.joint_list)[-1])}[kind]
@@ -1358,21 +1342,80 @@ class Engine:
         return out
 
 
-class Tracker:
+def _check_pose_rows(J, pcap, tri, per_joint, poses, flags, n_persons, ids=None, B=None, device=None):
+    """The tensors of the pose-row contract: poses f64 (tri) or f32 [B,pcap,J,3]; flags u8, [B,pcap,J]
+    (per_joint) or [B,pcap]; n_persons i32 [B]; ids i32 [B,pcap] where a stage takes them; all contiguous, and on `device`
+    where one is given.  B: the frames they must have (default: as many as poses has).  -> B"""
+    if B is None:
+        B = int(poses.shape[0]) if poses.dim() == 4 else -1
+    want = torch.float64 if tri else torch.float32
+    if poses.dtype != want or tuple(poses.shape) != (B, pcap, J, 3):
+        raise ValueError('poses must be %s [%s,%d,%d,3]' % (want, 'B' if B < 0 else B, pcap, J))
+    if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, pcap, J) if per_joint else (B, pcap)):
+        raise ValueError('flags must be uint8 %s' % ('[B,Pcap,J], one per joint' if per_joint else '[B,Pcap], one per row'))
+    if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
+        raise ValueError('n_persons must be int32 [%d]' % B)
+    if ids is not None and (ids.dtype != torch.int32 or tuple(ids.shape) != (B, pcap)):
+        raise ValueError('ids must be int32 [%d,%d]' % (B, pcap))
+    given = [t for t in (poses, flags, n_persons, ids) if t is not None]
+    if not all(t.is_contiguous() for t in given):
+        raise ValueError('poses, flags, n_persons and ids must be contiguous')
+    if device is not None and any(t.device != device for t in given):
+        raise ValueError('poses, flags, n_persons and ids must be on %s' % device)
+    return B
+
+
+class _DeviceState:
+    """What the state objects below share: the opaque state `_prefix`_create made on the engine's device, its launch
+    count, reset() and close().  `_noun` is the object's name in 'the ... is closed'."""
+    _prefix = _noun = None
+
+    def _create(self, eng, *args):
+        self.eng, self.state = eng, C.c_void_p()
+        eng._chk(getattr(eng.lib, self._prefix + '_create')(eng.ctx, *args, C.byref(self.state)))
+
+    def _open(self):
+        if not self.state:
+            raise RuntimeError('the %s is closed' % self._noun)
+
+    def launches(self):
+        """Kernels this object has enqueued so far."""
+        n = C.c_int64()
+        self.eng._chk(getattr(self.eng.lib, self._prefix + '_launches')(self.eng.ctx, self.state, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Back to the state after creation: a new sequence or recording (ordered on the current stream)."""
+        self.eng._chk(getattr(self.eng.lib, self._prefix + '_reset')(self.eng.ctx, self.eng._stream(), self.state))
+
+    def close(self):
+        if getattr(self, 'state', None) and self.eng.ctx:
+            getattr(self.eng.lib, self._prefix + '_destroy')(self.eng.ctx, self.state)
+        self.state = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Tracker(_DeviceState):
     """Engine.tracker's object: the device state of one sequence (the detections of the last max_gap + 1 frames with
     their ids, and the id count).  Mode 'gt' takes the ground-truth arrays as they are -- f32 poses [B,Gcap,J,3] with
     joint flags [B,Gcap,J], pcap = Gcap -- and gives the GT bodies the identities the wire format does not carry.  update() takes the frames of the sequence in order, in chunks of any size; the ids
     do not depend on the chunking.  Everything stays on the device and on the current stream: update() neither
     synchronises nor reads anything back."""
+    _prefix, _noun = 'mpe_track', 'tracker'
 
     def __init__(self, eng, mode, max_gap, gate, pcap):
         if mode not in ('mlp', 'tri', 'gt'):
             raise ValueError('mode must be mlp, tri or gt')
         if not gate > 0:
             raise ValueError('gate must be > 0')
-        self.eng, self.mode, self.max_gap, self.gate, self.pcap = eng, mode, int(max_gap), float(gate), pcap
-        self.state, self._issued = C.c_void_p(), None
-        eng._chk(eng.lib.mpe_track_create(eng.ctx, self.pcap, eng.J, self.max_gap, int(mode == 'tri'), C.byref(self.state)))
+        self.mode, self.max_gap, self.gate, self.pcap = mode, int(max_gap), float(gate), pcap
+        self._issued = None
+        self._create(eng, self.pcap, eng.J, self.max_gap, int(mode == 'tri'))
 
     def update(self, poses, flags, n_persons):
         """poses / flags / n_persons of the next B >= 0 frames, as mlp3d or triangulate returned them (shapes and types
@@ -1381,20 +1424,8 @@ class Tracker:
         detection), 'issued' [1] i32 (ids issued so far)}, device tensors."""
         eng, tri = self.eng, self.mode == 'tri'
         per_joint = self.mode != 'mlp'                   # 'gt': f32 poses like 'mlp', per-joint flags like 'tri'
-        if not self.state:
-            raise RuntimeError('the tracker is closed')
-        B = int(poses.shape[0]) if poses.dim() == 4 else -1
-        want = torch.float64 if tri else torch.float32
-        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, eng.J, 3):
-            raise ValueError('poses must be %s [B,%d,%d,3]' % (want, self.pcap, eng.J))
-        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if per_joint else (B, self.pcap)):
-            raise ValueError('flags do not match mode %s' % self.mode)
-        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
-            raise ValueError('n_persons must be int32 [%d]' % B)
-        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous()):
-            raise ValueError('poses, flags and n_persons must be contiguous')
-        if any(t.device != eng.device for t in (poses, flags, n_persons)):
-            raise ValueError('poses, flags and n_persons must be on %s' % eng.device)
+        self._open()
+        B = _check_pose_rows(eng.J, self.pcap, tri, per_joint, poses, flags, n_persons, device=eng.device)
         dev = eng.device
         out = {'ids': torch.empty((B, self.pcap), dtype=torch.int32, device=dev),
                'cost': torch.empty((B, self.pcap), dtype=torch.float64, device=dev),
@@ -1413,34 +1444,18 @@ class Tracker:
         eng._chk(eng.lib.mpe_track_batch(eng.ctx, eng._stream(), self.state, C.byref(a)))
         return out
 
-    def launches(self):
-        """Kernels this tracker has enqueued so far."""
-        n = C.c_int64()
-        self.eng._chk(self.eng.lib.mpe_track_launches(self.eng.ctx, self.state, C.byref(n)))
-        return n.value
-
     def reset(self):
         """Start a new sequence (ordered on the current stream)."""
-        self.eng._chk(self.eng.lib.mpe_track_reset(self.eng.ctx, self.eng._stream(), self.state))
+        super().reset()
         self._issued = None
 
-    def close(self):
-        if getattr(self, 'state', None) and self.eng.ctx:
-            self.eng.lib.mpe_track_destroy(self.eng.ctx, self.state)
-        self.state = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Calibrator:
+class Calibrator(_DeviceState):
     """Engine.calibrator's object: trial extrinsics and the 28 sums per camera on the device, the Levenberg-Marquardt
     state of the cameras in the library.  A pass is accumulate() over every batch of the recording, in any chunking (the
     sums are the same bits), then step(); passes repeat on the same batches and poses until the report says all_done.
     accumulate() stays on the current stream and neither synchronises nor reads back; step() synchronises."""
+    _prefix, _noun = 'mpe_calib', 'calibrator'
 
     def __init__(self, eng, kind, huber_px, min_obs, hold):
         if kind not in ('est', 'triang'):
@@ -1451,14 +1466,9 @@ class Calibrator:
         idx = [names.index(h) if isinstance(h, str) else int(h) for h in hold]
         if any(not 0 <= i < eng.V for i in idx):
             raise ValueError('hold names cameras of the engine')
-        self.eng, self.kind, self.huber_px, self.min_obs = eng, kind, float(huber_px), int(min_obs)
+        self.kind, self.huber_px, self.min_obs = kind, float(huber_px), int(min_obs)
         self.hold_mask = sum(1 << i for i in set(idx))
-        self.state = C.c_void_p()
-        eng._chk(eng.lib.mpe_calib_create(eng.ctx, C.byref(self.state)))
-
-    def _open(self):
-        if not self.state:
-            raise RuntimeError('the calibrator is closed')
+        self._create(eng)
 
     def accumulate(self, db, persons, n_persons, poses, flags, joint_mask=None, threshold=0.5):
         """The observations of one batch added to the pass (arguments as Engine.refine takes them)."""
@@ -1527,34 +1537,21 @@ class Calibrator:
         eng._chk(eng.lib.mpe_calib_set_extrinsics(eng.ctx, eng._stream(), self.state, E.ctypes.data_as(L.c_f64p)))
 
     def launches(self):
-        """Kernels this calibrator has enqueued so far."""
         self._open()
-        n = C.c_int64()
-        self.eng._chk(self.eng.lib.mpe_calib_launches(self.eng.ctx, self.state, C.byref(n)))
-        return n.value
+        return super().launches()
 
     def reset(self):
         """Start afresh from the engine's own extrinsics."""
         self._open()
-        self.eng._chk(self.eng.lib.mpe_calib_reset(self.eng.ctx, self.eng._stream(), self.state))
-
-    def close(self):
-        if getattr(self, 'state', None) and self.eng.ctx:
-            self.eng.lib.mpe_calib_destroy(self.eng.ctx, self.state)
-        self.state = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().reset()
 
 
-class Smoother:
+class Smoother(_DeviceState):
     """Engine.smoother's object: the device state of one sequence (the raw poses, presence and ids of the last `window`
     frames).  update() takes the frames of the sequence in order, in chunks of any size, with the ids Tracker.update
     gave them; the result does not depend on the chunking.  Everything stays on the device and on the current stream:
     update() neither synchronises nor reads anything back."""
+    _prefix, _noun = 'mpe_smooth', 'smoother'
 
     def __init__(self, eng, mode, window, decay, fill, pcap):
         if mode not in ('mlp', 'tri'):
@@ -1563,9 +1560,8 @@ class Smoother:
             raise ValueError('window must be within 0 .. %d' % L.MPE_SMOOTH_MAX_WINDOW)
         if not 0.25 <= decay <= 1.0:
             raise ValueError('decay must be within [0.25, 1]')
-        self.eng, self.mode, self.window, self.decay, self.fill, self.pcap = eng, mode, int(window), float(decay), bool(fill), pcap
-        self.state = C.c_void_p()
-        eng._chk(eng.lib.mpe_smooth_create(eng.ctx, self.pcap, eng.J, self.window, int(mode == 'tri'), C.byref(self.state)))
+        self.mode, self.window, self.decay, self.fill, self.pcap = mode, int(window), float(decay), bool(fill), pcap
+        self._create(eng, self.pcap, eng.J, self.window, int(mode == 'tri'))
 
     def update(self, poses, flags, n_persons, ids, joint_mask=None):
         """poses / flags / n_persons of the next B >= 0 frames as Tracker.update took them, and the 'ids' it returned.
@@ -1573,22 +1569,8 @@ class Smoother:
         new tensors; flags 2: a filled joint), 'vel' [B,Pcap,J,3] f64 (metres per frame), 'n_samples' [B,Pcap,J] u8
         (samples the window held)}, device tensors."""
         eng, tri = self.eng, self.mode == 'tri'
-        if not self.state:
-            raise RuntimeError('the smoother is closed')
-        B = int(poses.shape[0]) if poses.dim() == 4 else -1
-        want = torch.float64 if tri else torch.float32
-        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, eng.J, 3):
-            raise ValueError('poses must be %s [B,%d,%d,3]' % (want, self.pcap, eng.J))
-        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if tri else (B, self.pcap)):
-            raise ValueError('flags do not match mode %s' % self.mode)
-        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
-            raise ValueError('n_persons must be int32 [%d]' % B)
-        if ids.dtype != torch.int32 or tuple(ids.shape) != (B, self.pcap):
-            raise ValueError('ids must be int32 [%d,%d]' % (B, self.pcap))
-        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous() and ids.is_contiguous()):
-            raise ValueError('poses, flags, n_persons and ids must be contiguous')
-        if any(t.device != eng.device for t in (poses, flags, n_persons, ids)):
-            raise ValueError('poses, flags, n_persons and ids must be on %s' % eng.device)
+        self._open()
+        B = _check_pose_rows(eng.J, self.pcap, tri, tri, poses, flags, n_persons, ids, device=eng.device)
         dev = eng.device
         out = {'poses': torch.empty_like(poses), 'flags': torch.empty_like(flags),
                'vel': torch.empty((B, self.pcap, eng.J, 3), dtype=torch.float64, device=dev),
@@ -1602,33 +1584,12 @@ class Smoother:
         eng._chk(eng.lib.mpe_smooth_batch(eng.ctx, eng._stream(), self.state, C.byref(a)))
         return out
 
-    def launches(self):
-        """Kernels this smoother has enqueued so far."""
-        n = C.c_int64()
-        self.eng._chk(self.eng.lib.mpe_smooth_launches(self.eng.ctx, self.state, C.byref(n)))
-        return n.value
-
-    def reset(self):
-        """Start a new sequence (ordered on the current stream)."""
-        self.eng._chk(self.eng.lib.mpe_smooth_reset(self.eng.ctx, self.eng._stream(), self.state))
-
-    def close(self):
-        if getattr(self, 'state', None) and self.eng.ctx:
-            self.eng.lib.mpe_smooth_destroy(self.eng.ctx, self.state)
-        self.state = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Skeleton:
+class Skeleton(_DeviceState):
     """Engine.skeleton's object: the device state of one sequence (a histogram of lengths per track id and bone, the
     length table, the counters).  observe() adds frames in any order and chunking, update() reads the lengths off the
     histograms, fit() moves poses towards the lengths of their tracks.  Everything stays on the device and on the
-    current stream: only lengths() synchronises and reads back."""
+    current stream: only lengths() synchronises and reads back.  reset(): empty histograms, no lengths, counters at zero."""
+    _prefix, _noun = 'mpe_skel', 'skeleton'
 
     def __init__(self, eng, mode, bones, bin_mm, tid_cap, pcap):
         from .harness import skeleton as S
@@ -1644,32 +1605,17 @@ class Skeleton:
         if int(tid_cap) < 1 or int(tid_cap) * len(self.bones) * L.MPE_SKEL_BINS * 4 > L.MPE_SKEL_MAX_HIST_BYTES:
             raise ValueError('tid_cap must be within 1 .. %d for %d bones' % (L.MPE_SKEL_MAX_HIST_BYTES // (4 * L.MPE_SKEL_BINS * len(self.bones)),
                                                                             len(self.bones)))
-        self.eng, self.mode, self.bin_width, self.tid_cap, self.pcap = eng, mode, float(bin_mm) / 1000.0, int(tid_cap), int(pcap)
-        self.state = C.c_void_p()
+        self.mode, self.bin_width, self.tid_cap, self.pcap = mode, float(bin_mm) / 1000.0, int(tid_cap), int(pcap)
         flat = np.ascontiguousarray(self.bones, np.int32)
         cfg = L.mpe_skel_config()
         cfg.pcap, cfg.n_joints, cfg.pose_f64, cfg.tid_cap, cfg.n_bones = self.pcap, eng.J, int(mode == 'tri'), self.tid_cap, len(self.bones)
         cfg.bin_width, cfg.bones = self.bin_width, flat.ctypes.data_as(L.c_i32p)
-        eng._chk(eng.lib.mpe_skel_create(eng.ctx, C.byref(cfg), C.byref(self.state)))
+        self._create(eng, C.byref(cfg))
 
     def _args(self, poses, flags, n_persons, ids, joint_mask):
         eng, tri = self.eng, self.mode == 'tri'
-        if not self.state:
-            raise RuntimeError('the skeleton is closed')
-        B = int(poses.shape[0]) if poses.dim() == 4 else -1
-        want = torch.float64 if tri else torch.float32
-        if poses.dtype != want or tuple(poses.shape) != (B, self.pcap, eng.J, 3):
-            raise ValueError('poses must be %s [B,%d,%d,3]' % (want, self.pcap, eng.J))
-        if flags.dtype != torch.uint8 or tuple(flags.shape) != ((B, self.pcap, eng.J) if tri else (B, self.pcap)):
-            raise ValueError('flags do not match mode %s' % self.mode)
-        if n_persons.dtype != torch.int32 or tuple(n_persons.shape) != (B,):
-            raise ValueError('n_persons must be int32 [%d]' % B)
-        if ids.dtype != torch.int32 or tuple(ids.shape) != (B, self.pcap):
-            raise ValueError('ids must be int32 [%d,%d]' % (B, self.pcap))
-        if not (poses.is_contiguous() and flags.is_contiguous() and n_persons.is_contiguous() and ids.is_contiguous()):
-            raise ValueError('poses, flags, n_persons and ids must be contiguous')
-        if any(t.device != eng.device for t in (poses, flags, n_persons, ids)):
-            raise ValueError('poses, flags, n_persons and ids must be on %s' % eng.device)
+        self._open()
+        B = _check_pose_rows(eng.J, self.pcap, tri, tri, poses, flags, n_persons, ids, device=eng.device)
         a = L.mpe_skel_args()
         a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, self.pcap, eng.J, int(tri), int(tri)
         a.joint_mask = (1 << eng.J) - 1 if joint_mask is None else int(joint_mask)
@@ -1715,8 +1661,7 @@ class Skeleton:
     def set_lengths(self, table):
         """A caller's table [tid_cap, n_bones] (metres; an entry <= 0 or not finite: no length) in the place of the
         learned one, ordered on the current stream.  A host array is uploaded first."""
-        if not self.state:
-            raise RuntimeError('the skeleton is closed')
+        self._open()
         if not isinstance(table, torch.Tensor):
             table = torch.from_numpy(np.ascontiguousarray(table, np.float64))
         if table.dtype != torch.float64 or tuple(table.shape) != (self.tid_cap, len(self.bones)):
@@ -1725,44 +1670,22 @@ class Skeleton:
         self.eng._chk(self.eng.lib.mpe_skel_set_lengths(self.eng.ctx, self.eng._stream(), self.state, table.data_ptr()))
         table.record_stream(torch.cuda.current_stream(self.eng.device))
 
-    def launches(self):
-        """Kernels this skeleton has enqueued so far."""
-        n = C.c_int64()
-        self.eng._chk(self.eng.lib.mpe_skel_launches(self.eng.ctx, self.state, C.byref(n)))
-        return n.value
-
-    def reset(self):
-        """Empty histograms, no lengths, counters at zero (ordered on the current stream)."""
-        self.eng._chk(self.eng.lib.mpe_skel_reset(self.eng.ctx, self.eng._stream(), self.state))
-
-    def close(self):
-        if getattr(self, 'state', None) and self.eng.ctx:
-            self.eng.lib.mpe_skel_destroy(self.eng.ctx, self.state)
-        self.state = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TrackScore:
+class TrackScore(_DeviceState):
     """Engine.track_scorer's object: the device state of one recording (the totals, the per-identity carry, the
     identity x track table).  update() takes the frames in order, in chunks of any size; nothing depends on the chunking.
     Everything stays on the device and on the current stream: update() neither synchronises nor reads anything back;
     result() does both."""
+    _prefix, _noun = 'mpe_track_score', 'track scorer'
 
     def __init__(self, eng, mode, threshold_mm, gid_cap, tid_cap, max_frames, gcap, pcap):
         if mode not in ('mlp', 'tri'):
             raise ValueError('mode must be mlp or tri')
         if not threshold_mm > 0:
             raise ValueError('threshold_mm must be > 0')
-        self.eng, self.mode, self.threshold_mm = eng, mode, float(threshold_mm)
+        self.mode, self.threshold_mm = mode, float(threshold_mm)
         self.gid_cap, self.tid_cap, self.max_frames, self.gcap, self.pcap = int(gid_cap), int(tid_cap), int(max_frames), int(gcap), int(pcap)
-        self.state = C.c_void_p()
         self._status = torch.zeros((1,), dtype=torch.int32, device=eng.device)
-        eng._chk(eng.lib.mpe_track_score_create(eng.ctx, self.pcap, self.gcap, self.gid_cap, self.tid_cap, self.max_frames, C.byref(self.state)))
+        self._create(eng, self.pcap, self.gcap, self.gid_cap, self.tid_cap, self.max_frames)
 
     def update(self, ev, flags, n_persons, track_ids, gt_ids, gt_valid, skip=None):
         """ev: Engine.evaluate's dict for the next B >= 0 frames ('assign', 'err', 'invalid', 'n_res', 'n_gt' are read);
@@ -1771,8 +1694,7 @@ class TrackScore:
         frames to leave out.  -> {'frame_counts' [B,4] i32 (tp, fp, fn, idsw), 'match_tid' [B,Gcap] i32 (the matched
         track, -1 miss, -2 not counted), 'status' [1] i32 (sticky MPE_TRACK_SCORE_OVER_IDS)}, device tensors."""
         eng, tri = self.eng, self.mode == 'tri'
-        if not self.state:
-            raise RuntimeError('the track scorer is closed')
+        self._open()
         B = int(track_ids.shape[0]) if track_ids.dim() == 2 else -1
         P, G = self.pcap, self.gcap
         want = {'flags': (flags, torch.uint8, (B, P, eng.J) if tri else (B, P)), 'n_persons': (n_persons, torch.int32, (B,)),
@@ -1815,27 +1737,10 @@ class TrackScore:
                                                         table.ctypes.data))
         return {'last': ident[0], 'present': ident[1], 'matched': ident[2], 'bits': ident[3], 'pred_count': pred, 'table': table}
 
-    def launches(self):
-        """Kernels this scorer has enqueued so far."""
-        n = C.c_int64()
-        self.eng._chk(self.eng.lib.mpe_track_score_launches(self.eng.ctx, self.state, C.byref(n)))
-        return n.value
-
     def reset(self):
         """Start a new recording (ordered on the current stream)."""
-        self.eng._chk(self.eng.lib.mpe_track_score_reset(self.eng.ctx, self.eng._stream(), self.state))
+        super().reset()
         self._status.zero_()
-
-    def close(self):
-        if getattr(self, 'state', None) and self.eng.ctx:
-            self.eng.lib.mpe_track_score_destroy(self.eng.ctx, self.state)
-        self.state = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def explicit_m_cap(max_heads_per_frame):

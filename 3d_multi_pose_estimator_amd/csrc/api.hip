@@ -1788,6 +1788,37 @@ int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_r
     return MPE_OK;
 }
 
+int mpe_regroup_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_regroup_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames != b->n_frames || a->n_joints != ctx->cfg.n_joints)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: %d frames, the batch has %d; %d joints, the context has %d", a->n_frames,
+                    b->n_frames, a->n_joints, ctx->cfg.n_joints);
+    if (a->pcap < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: pcap %d must be at least 1", a->pcap);
+    if ((a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: pose_f64 %d and joint_flags %d must be 0 or 1", a->pose_f64, a->joint_flags);
+    if (a->pcap > MPE_REGROUP_MAX_PERSONS)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_regroup_batch: pcap %d over %d", a->pcap, MPE_REGROUP_MAX_PERSONS);
+    if (!(a->gate_px > 0.0) || !(a->clip_px >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: gate_px %g must be positive and clip_px %g must not be negative", a->gate_px,
+                    a->clip_px);
+    if (a->min_joints < 1 || a->min_joints > ctx->cfg.n_joints)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: min_joints %d outside 1..%d", a->min_joints, ctx->cfg.n_joints);
+    if (a->flags == 0 || (a->flags & ~(uint32_t)(MPE_REGROUP_RELEASE | MPE_REGROUP_ATTACH)))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: flags %u must be MPE_REGROUP_RELEASE, MPE_REGROUP_ATTACH or both", a->flags);
+    if (b->n_frames == 0) return MPE_OK;
+    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: NULL argument");
+    // d_cost is [n_heads][pcap]: a batch without heads has no table to point at, and no frame of it touches one
+    if (!a->d_persons_out || !a->d_change || !a->d_n_views || (!a->d_cost && b->n_heads > 0) || !a->d_counts || !a->d_status)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: NULL output");
+    HIPCHK(ctx, launch_regroup(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, ctx->cfg.min_views,
+                               ctx->cfg.max_heads_per_frame, ctx->d_status, *b, *a));
+    return MPE_OK;
+}
+
 static int geom_checks(mpe_ctx *ctx, const mpe_geom_args *a, const char *who) {
     if (!a) return fail(ctx, MPE_ERR_INVALID, "%s: NULL argument", who);
     if (!(a->sigma_m > 0.0) || !(a->clip_m >= 0.0))

@@ -9,6 +9,7 @@
 // that has stopped idles until no lane of its wave is active (no rebalancing).  No LDS, no atomics.  The file turns
 // contraction off; f64 quotients and roots are the language's correctly rounded ones.
 #include "mpe_internal.h"
+#include "project64.h"
 #include "reproject_select.h"
 
 #pragma clang fp contract(off)
@@ -32,38 +33,8 @@ struct RefineK {
     uint8_t *iters, *n_views;
 };
 
-struct Proj {                                 // the header's projection lines, kept for the Jacobian
-    double pc2, h0, h1, r, f, u2, px, py;
-};
-
-__device__ inline Proj project(const DevCfg *cfg, int c, double X0, double X1, double X2) {
-    const double *T = cfg->P[c];
-    double pc[3];
-    for (int i = 0; i < 3; ++i) pc[i] = ((T[4 * i] * X0 + T[4 * i + 1] * X1) + T[4 * i + 2] * X2) + T[4 * i + 3];
-    const double kd0 = cfg->dist[c][0], kd1 = cfg->dist[c][1], kd2 = cfg->dist[c][4];
-    Proj p;
-    p.pc2 = pc[2];
-    p.h0 = pc[0] / pc[2];
-    p.h1 = pc[1] / pc[2];
-    p.r = p.h0 * p.h0 + p.h1 * p.h1;
-    p.f = ((1.0 + kd0 * p.r) + (kd1 * p.r) * p.r) + ((kd2 * p.r) * p.r) * p.r;
-    const double d0 = p.h0 * p.f, d1 = p.h1 * p.f;
-    const float *K = cfg->K[c];
-    double u[3];
-    for (int i = 0; i < 3; ++i) u[i] = ((double)K[3 * i] * d0 + (double)K[3 * i + 1] * d1) + (double)K[3 * i + 2];
-    p.u2 = u[2];
-    p.px = u[0] / u[2];
-    p.py = u[1] / u[2];
-    return p;
-}
-
 __device__ inline double rho(double e, double huber) {
     return (huber <= 0.0 || e <= huber) ? e * e : (2.0 * huber) * e - huber * huber;
-}
-
-__device__ inline bool finite3(double a, double b, double c) {
-    const double inf = __builtin_huge_val();
-    return fabs(a) < inf && fabs(b) < inf && fabs(c) < inf;
 }
 
 __global__ void __launch_bounds__(32 * RF_GROUPS) k_refine(const DevCfg *__restrict__ cfg, RefineK a) {

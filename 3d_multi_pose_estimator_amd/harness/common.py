@@ -101,7 +101,48 @@ def build_parser(description):
                         '(mpe_refine_batch: at most ITERS Levenberg-Marquardt iterations per joint, 1..64) and the refined poses are scored; '
                         'one further line reports the solved joints, the share that moved and the mean cost before and after')
     p.add_argument('--refine-huber', type=float, default=0.0, metavar='PX', help='--refine: Huber threshold in pixels (0: plain least squares)')
+    p.add_argument('--regroup', type=float, default=0.0, metavar='PX',
+                   help='after the 3D stage the person proposals are repaired by reprojection consistency (mpe_regroup_batch: a skeleton whose mean '
+                        'distance from its row\'s projected pose is PX pixels or more is released, free skeletons within PX are attached to rows '
+                        'that lack their camera) and the 3D stage runs again on the new rows, before --refine; one further line reports the '
+                        'skeletons released, attached and left free and the rows below the minimum number of views.  It acts in '
+                        'metrics_from_model, metrics_from_triangulation and calibrate; the other harnesses accept and ignore it')
+    p.add_argument('--regroup-rounds', type=int, default=1, metavar='N', help='--regroup: alternations of regrouping and the 3D stage')
+    p.add_argument('--regroup-min-joints', type=int, default=3, metavar='N', help='--regroup: joints a (skeleton, person) pair needs to be judged at all')
+    p.add_argument('--regroup-clip', type=float, default=0.0, metavar='PX', help='--regroup: largest distance a joint contributes, pixels (0: no clip)')
     return p
+
+
+def regroup_stage(eng, args, db, persons, n_persons, poses, flags, mode, log, stage3d, joint_mask=None):
+    """--regroup: N times {regroup, the 3D stage again on the new rows} -> (persons, poses, flags); without the flag, the
+    arguments.  mode 'mlp' or 'triang'; stage3d(persons) -> (poses, flags); log takes one list per round of the batch's
+    counts and status (host arrays).  joint_mask: the joints whose poses stage3d fills in (None: those of the kind -- a
+    triangulation without all_joints flags the joints outside used_joints as emitted and leaves them at the origin, so
+    its caller names the used joints here)."""
+    gate = float(getattr(args, 'regroup', 0.0) or 0.0)
+    if not gate:
+        return persons, poses, flags
+    for rnd in range(max(1, int(args.regroup_rounds))):
+        rg = eng.regroup(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', gate_px=gate,
+                         clip_px=args.regroup_clip, min_joints=args.regroup_min_joints, joint_mask=joint_mask)
+        persons = rg['persons']
+        poses, flags = stage3d(persons)
+        while len(log) <= rnd:
+            log.append([])
+        log[rnd].append({k: rg[k].cpu().numpy() for k in ('counts', 'status')})
+    return persons, poses, flags
+
+
+def report_regroup(args, log):
+    """The further report line of --regroup -> its dict: released and attached over all rounds, free and below the minimum
+    number of views after the last."""
+    from .regroup import summary
+    every, last = summary([o for rnd in log for o in rnd]), summary(log[-1] if log else [])
+    r = {'released': every['released'], 'attached': every['attached'], 'free': last['free'], 'below_min_views': last['below_min_views'],
+         'copied': last['copied']}
+    print('Regrouped (gate %g px, %d round%s): %d skeletons released, %d attached, %d left free, %d rows below the minimum number of views'
+          % (args.regroup, len(log), '' if len(log) == 1 else 's', r['released'], r['attached'], r['free'], r['below_min_views']))
+    return r
 
 
 def geom_options(args):
@@ -561,6 +602,8 @@ def run(args, mode):
     tracker = summary = smoother = smoothed = gt_tracker = scorer = skeleton = boned = None
     last = {}                                                # what the track score of a batch needs from infer_device
     refined = []
+    regrouped = []                                           # --regroup: per round, the counts of every batch
+    used_mask = sum(1 << int(j) for j in parameters.used_joints)     # the joints both 3D stages of this script fill in
     if getattr(args, 'track', False):
         from .tracking import TrackSummary
         tracker, summary = eng.tracker(mode, max_gap=args.track_gap, gate=args.track_gate), TrackSummary()
@@ -587,8 +630,12 @@ def run(args, mode):
         t1 = time.time()
         if mode == 'mlp':
             poses, valid = eng.mlp3d(db, persons, n_persons)
+            persons, poses, valid = regroup_stage(eng, args, db, persons, n_persons, poses, valid, mode, regrouped,
+                                                  lambda rows: eng.mlp3d(db, rows, n_persons), used_mask)
         else:
             poses, jvalid = eng.triangulate(db, persons, n_persons)
+            persons, poses, jvalid = regroup_stage(eng, args, db, persons, n_persons, poses, jvalid, mode, regrouped,
+                                                   lambda rows: eng.triangulate(db, rows, n_persons), used_mask)
         torch.cuda.synchronize()
         t['match'] += t1 - t0
         t['3d'] += time.time() - t1
@@ -625,6 +672,9 @@ def run(args, mode):
             poses, flags = eng.mlp3d(db, persons, n_persons)
         else:
             poses, flags = eng.triangulate(db, persons, n_persons)
+        persons, poses, flags = regroup_stage(eng, args, db, persons, n_persons, poses, flags, mode, regrouped,
+                                              lambda rows: eng.mlp3d(db, rows, n_persons) if mode == 'mlp' else eng.triangulate(db, rows, n_persons),
+                                              used_mask)
         if refine:
             ref = eng.refine(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', max_iters=refine,
                              huber_px=args.refine_huber, out=poses)
@@ -723,6 +773,8 @@ def run(args, mode):
         print('Frames per second', n_data / max(1e-9, t['match'] + t['3d']))
         if 'eval' in t:
             print('Mean time for evaluation on the device', t['eval'] / n_data)
+    if getattr(args, 'regroup', 0.0):
+        out['regroup'] = report_regroup(args, regrouped)
     if refine:
         from .refine import summary as refine_summary
         out['refine'] = r = refine_summary(refined)

@@ -1150,6 +1150,40 @@ class Engine:
         self._chk(self.lib.mpe_refine_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
         return res
 
+    def regroup(self, db, persons, n_persons, poses, flags, kind, gate_px=15.0, clip_px=0.0, min_joints=3, joint_mask=None,
+                threshold=0.5, release=True, attach=True, out=None):
+        """The person proposals repaired by reprojection consistency (mpe_regroup_batch; include/mpe.h has the rule,
+        harness/regroup.py states it in numpy and the two agree bit for bit): the mean pixel distance of every head of a
+        frame from every person's projected pose, heads released from rows they miss by gate_px or more, free heads
+        attached (least cost first) to rows that lack their camera.  kind and joint_mask as refine takes them; clip_px > 0
+        bounds a joint's distance; a pair needs min_joints counting joints to be scored; out: the tensor that takes the
+        rows (`persons` itself regroups in place).  -> dict of device tensors: persons [B,Pcap,V] i32, change [B,Pcap,V]
+        u8 (0 kept, 1 released, 2 attached, 3 both), n_views [B,Pcap] i32, cost [n_heads,Pcap] f64 (-1: unscored), counts
+        [B,4] i32 (released, attached, free heads, rows below min_views), status [B] i32 (MPE_REGROUP_* bits: such
+        frames are copied through); one launch on the current stream.  The poses are not updated: run the 3D stage again
+        on the new rows."""
+        B, tri, joint_mask = self._pose_args(db, persons, n_persons, poses, flags, kind, joint_mask, ('est', 'triang'))
+        if out is None:
+            out = torch.empty_like(persons)
+        elif out.dtype != persons.dtype or tuple(out.shape) != tuple(persons.shape) or not out.is_contiguous() or out.device != persons.device:
+            raise ValueError('out must be a contiguous tensor of the type, shape and device of persons')
+        i32 = dict(dtype=torch.int32, device=self.device)
+        # a batch without heads has an empty table: its data_ptr() may be 0, and the entry point takes a NULL d_cost then
+        res = {'persons': out, 'change': torch.empty((B, self.pcap, self.V), dtype=torch.uint8, device=self.device),
+               'n_views': torch.empty((B, self.pcap), **i32),
+               'cost': torch.empty((db.n_heads, self.pcap), dtype=torch.float64, device=self.device),
+               'counts': torch.empty((B, 4), **i32), 'status': torch.empty((B,), **i32)}
+        a = L.mpe_regroup_args()
+        a.n_frames, a.pcap, a.n_joints = B, self.pcap, self.J
+        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
+        a.min_joints, a.gate_px, a.clip_px = int(min_joints), float(gate_px), float(clip_px)
+        a.flags = (L.MPE_REGROUP_RELEASE if release else 0) | (L.MPE_REGROUP_ATTACH if attach else 0)
+        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
+        a.d_persons_out, a.d_change, a.d_n_views = out.data_ptr(), res['change'].data_ptr(), res['n_views'].data_ptr()
+        a.d_cost, a.d_counts, a.d_status = res['cost'].data_ptr(), res['counts'].data_ptr(), res['status'].data_ptr()
+        self._chk(self.lib.mpe_regroup_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return res
+
     def calibrator(self, kind, huber_px=0.0, min_obs=50, hold=()):
         """A Calibrator for poses of `kind` ('est' or 'triang', as refine takes them): the camera extrinsics refined from
         a recording's own poses, the joints held fixed (mpe_calib_*; include/mpe.h has the rule, harness/calibrate.py

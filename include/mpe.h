@@ -3,7 +3,8 @@
  * inference path of gnns4hri/3D_multi_pose_estimator:
  *
  *   2D skeletons per camera -> graph featurisation -> 5-layer graph attention network
- *   -> greedy person clustering -> { MLP 3D regression | pairwise-DLT triangulation }.
+ *   -> greedy person clustering -> { MLP 3D regression | pairwise-DLT triangulation }
+ *   [-> regrouping of the proposals by reprojection consistency (mpe_regroup_batch) -> the 3D stage again].
  *
  * The reference has no FFI: its operator API is the set of Python symbols that
  * test/metrics_from_model.py:12-24 and test/metrics_from_triangulation.py:13-23 import.
@@ -547,6 +548,89 @@ typedef struct {
 int mpe_geom_scores_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_geom_args *a);
 int mpe_geom_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_geom_args *a,
                          int32_t *d_persons, int32_t *d_n_persons);
+
+/* Regrouping: the person proposals repaired by reprojection consistency -- the verification pass of multi-view association,
+ * between the matching stage and the refinement.  Once a row has a 3D pose, projecting the pose into a camera says which
+ * skeleton of that camera belongs to it: the stage computes the cost of EVERY head of a frame against EVERY person of the
+ * frame, releases the heads a row should not hold (a wrong person's skeleton, two persons exchanged in a camera) and
+ * attaches free heads to rows that lack their camera (a skeleton the clustering left out).  All arithmetic is binary64,
+ * every operation named below rounded on its own (nothing fused), quotients and roots correctly rounded; harness/regroup.py
+ * states the same in numpy, and the two agree bit for bit.
+ * Inputs.  The batch; d_persons / d_n_persons / d_poses / d_flags / pose_f64 / joint_flags / joint_mask / threshold exactly as
+ *   mpe_refine_batch takes them; gate_px > 0, clip_px >= 0, min_joints in 1..n_joints, flags (MPE_REGROUP_RELEASE |
+ *   MPE_REGROUP_ATTACH, at least one).  The rows of a frame are its persons p < min(d_n_persons[f], pcap); entries < 0 are
+ *   open.  Person p has a pose when joint_flags == 1 or d_flags[f][p] != 0.
+ * Cost of head h (camera c = d_head_cam[h]) against person p of the same frame, for every p that has a pose and every head of
+ *   the frame.  Joint j counts when bit j is set in joint_mask and in d_joint_mask[h]; d_vp[h][j][0] > threshold (strict);
+ *   with joint_flags == 1, d_flags[f][p][j] != 0; the pose's joint j, widened to f64, is finite; pc_2 > 0 for it in camera c;
+ *   and e is finite, where e is the pixel distance of mpe_refine_batch's projection lines (T, kd and K as stored there)
+ *   from the detection (x, y) = d_xy[h][j].  With clip_px > 0, an e > clip_px is replaced by clip_px.
+ *   cost = (the left-fold sum of e over the counting joints in increasing j, from 0.0) / n, n = their number.  With
+ *   n < min_joints (or a head whose camera index is outside 0..V-1, or a cost that is not finite) the pair is UNSCORED: -1.
+ *   A scored cost is finite and >= 0.  The table does not depend on d_persons.
+ * Bad rows.  An entry e >= 0 in column c of a row is bad when e >= the frame's head count, when head e is not of camera c, or
+ *   when another entry of the frame's rows names e too.  Any bad entry makes the frame MPE_REGROUP_BAD_ROWS.  A frame with
+ *   more heads than max_heads_per_frame is MPE_REGROUP_OVER_CAP (its rows are not looked at) and sets the sticky status bit
+ *   mpe_sync_status reports, as everywhere.  Either frame is COPIED THROUGH: its rows unchanged, d_change 0, d_n_views
+ *   counted from the rows as they are, d_counts 0; its cost table is still written.
+ * Release (MPE_REGROUP_RELEASE).  For every person with a pose and every camera c whose entry h is >= 0: if (p, h) is scored
+ *   and cost < gate_px does not hold, the entry becomes -1 and h is free.  Unscored pairs are kept (nothing can be said
+ *   about them); persons without a pose are left alone, and their heads are not free.
+ * Attach (MPE_REGROUP_ATTACH), after the release, per camera c, independently of the other cameras.  Heads: those of camera
+ *   c that no row of the frame names now (released ones included).  Persons: those with a pose whose entry for c is open
+ *   now.  A pair is linkable when it is scored and cost < gate_px.  The linkable pair of least cost -- ties to the lowest
+ *   head id, then the lowest p -- is written into the row and both leave; repeated until no linkable pair is left (the
+ *   greedy rule of mpe_track_batch).  A released head cannot return to the row that released it.
+ * d_n_persons is not changed and rows are not compacted: row p of the output still belongs to row p of d_poses.  A row may
+ *   end with fewer heads than min_views, or with none: the 3D stages decide from a row's heads whether it yields a pose.
+ * Outputs.  d_persons_out [n_frames][pcap][V] (may be d_persons itself); d_change [n_frames][pcap][V]: 0 kept, 1 released,
+ *   2 attached, 3 released and another head attached; d_n_views [n_frames][pcap]: entries >= 0 of the row afterwards, 0 for
+ *   p >= n_persons; d_cost [n_heads][pcap] f64: -1 for unscored pairs, for p >= n_persons and for persons without a pose
+ *   (required: the context holds no table of this size; it may be NULL only when the batch has no heads, where the table
+ *   is empty and nothing is written to it); d_counts [n_frames][4]: entries released, entries attached, heads
+ *   named by no row afterwards, persons with a pose and fewer than cfg.min_views heads afterwards; d_status [n_frames].
+ * Limits.  The stage does not merge two rows that hold the same body, does not found persons from the heads left free, and
+ *   does not update the pose: the caller alternates 3D stage, regroup, 3D stage again on the new rows.  joint_mask must
+ *   name only joints whose pose is filled in: mpe_triangulate_batch without flags bit 0 flags the joints outside
+ *   used_joints as emitted and leaves them at the origin, so after it the mask is cfg.used_joint_mask.
+ * One launch (one workgroup per frame), ordered on `stream`; keeps no state, neither synchronises nor allocates; n_frames == 0
+ *   does nothing; works on a context without weights and neither reads nor writes anything mpe_match_batch leaves behind
+ *   for mpe_mlp3d_batch.  MPE_ERR_INVALID for a gate_px that is not > 0 (or NaN), a negative (or NaN) clip_px, min_joints
+ *   outside 1..n_joints, flags 0 or with unknown bits, a NULL output, n_frames other than the batch's, n_joints other
+ *   than the context's, pcap < 1 or a pose_f64 / joint_flags other than 0 or 1; MPE_ERR_CAPACITY for
+ *   pcap > MPE_REGROUP_MAX_PERSONS. */
+enum {
+    MPE_REGROUP_BAD_ROWS = 1,
+    MPE_REGROUP_OVER_CAP = 2
+};
+enum {
+    MPE_REGROUP_RELEASE = 1,
+    MPE_REGROUP_ATTACH = 2
+};
+#define MPE_REGROUP_MAX_PERSONS 128
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t joint_mask;           /* bit j: joint j may count                                       */
+    float threshold;               /* 0.5, as for mpe_reproject_batch                                */
+    int32_t min_joints;            /* 1 .. n_joints: counting joints a scored pair needs             */
+    double gate_px;                /* pixels, > 0: a pair fits when its cost is below                */
+    double clip_px;                /* pixels, >= 0; 0: no clip                                       */
+    uint32_t flags;                /* MPE_REGROUP_RELEASE | MPE_REGROUP_ATTACH                       */
+    int32_t reserved;
+    const int32_t *d_persons;      /* [n_frames][pcap][V]                                            */
+    const int32_t *d_n_persons;    /* [n_frames]                                                     */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    int32_t *d_persons_out;        /* [n_frames][pcap][V]                                            */
+    uint8_t *d_change;             /* [n_frames][pcap][V]                                            */
+    int32_t *d_n_views;            /* [n_frames][pcap]                                               */
+    double *d_cost;                /* [n_heads][pcap]; NULL allowed when the batch has no heads      */
+    int32_t *d_counts;             /* [n_frames][4]                                                  */
+    int32_t *d_status;             /* [n_frames]                                                     */
+} mpe_regroup_args;
+int mpe_regroup_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_regroup_args *a);
 
 /* Clustering quality of the matching stage (test/sm_metrics.py:125-229, test/sm_metrics_without_gt.py:131-170): labels
  * from proposals, the ground-truth grouping of a frame's bodies_3D, and the four scores of two labelings.

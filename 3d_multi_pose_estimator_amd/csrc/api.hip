@@ -1508,6 +1508,7 @@ int mpe_skel_destroy(mpe_ctx *ctx, mpe_skel_state *st) {
     dev_free(ctx, st->count);
     dev_free(ctx, st->ctr);
     dev_free(ctx, st->sched);
+    dev_free(ctx, st->refine_tab);
     delete st;
     return MPE_OK;
 }
@@ -1548,8 +1549,12 @@ int mpe_skel_create(mpe_ctx *ctx, const mpe_skel_config *cfg, mpe_skel_state **o
         std::vector<uint32_t> sched;
         skel_schedule(bones, n_bones, &sched, st->steps_upto);
         if (!rc) rc = dev_alloc(ctx, &st->sched, sched.size(), false);
+        std::vector<uint32_t> tab;
+        st->n_colours = skel_refine_tables(bones, n_bones, n_joints, &tab);
+        if (!rc) rc = dev_alloc(ctx, &st->refine_tab, tab.size(), false);
         if (!rc && (hipMemcpy(st->bones, bones, (size_t)n_bones * 2 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(st->sched, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
+                    hipMemcpy(st->sched, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(st->refine_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
             rc = fail(ctx, MPE_ERR_HIP, "mpe_skel_create: hipMemcpy failed");
         return rc;
     });
@@ -1621,6 +1626,33 @@ int mpe_skel_fit_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const mpe
         return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: NULL argument");
     if (a->d_poses_out == a->d_poses) return fail(ctx, MPE_ERR_INVALID, "mpe_skel_fit_batch: d_poses_out is d_poses (rows are copied through from the input)");
     HIPCHK(ctx, launch_skel_fit(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
+int mpe_body_refine_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const mpe_batch *b, const mpe_body_refine_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    bool run;
+    rc = check_pose_rows(ctx, "mpe_body_refine_batch", st, a, &run);
+    if (rc) return rc;
+    if (a->n_joints != ctx->cfg.n_joints)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: %d joints, the context has %d", a->n_joints, ctx->cfg.n_joints);
+    if (a->sweeps < 1 || a->sweeps > MPE_SKEL_MAX_ITERS)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: sweeps %d; 1 .. %d", a->sweeps, MPE_SKEL_MAX_ITERS);
+    if (!(a->bone_weight >= 0.0) || !(a->huber_px >= 0.0) || !(a->threshold >= 0.0f))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: bone_weight %g, huber_px %g and threshold %g must not be negative", a->bone_weight,
+                    a->huber_px, (double)a->threshold);
+    if (!a->d_frame && a->n_frames != b->n_frames)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: n_frames %d without d_frame, the batch has %d", a->n_frames, b->n_frames);
+    if (!run) return MPE_OK;
+    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_persons || !a->d_poses_out || !a->d_status || !a->d_n_views ||
+        !a->d_cost || !a->d_err || !a->d_n_bones)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: NULL argument");
+    if (a->d_poses_out == a->d_poses)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: d_poses_out is d_poses (rows are copied through from the input)");
+    HIPCHK(ctx, launch_skel_refine(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, st, *b, *a));
     return MPE_OK;
 }
 

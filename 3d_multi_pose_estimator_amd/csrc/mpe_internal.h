@@ -233,6 +233,8 @@ struct mpe_skel_state {
     unsigned long long *ctr = nullptr;   // out_of_range, over_ids, status
     uint32_t *sched = nullptr;      // the steps of the fit (skel_schedule)
     int steps_upto[MPE_SKEL_MAX_ITERS + 1] = {};   // [iters]: the steps that hold the first `iters` sweeps
+    uint32_t *refine_tab = nullptr; // what the body fit reads of the bone list (skel_refine_tables)
+    int n_colours = 0;              // colours of the joints: two joints of one colour share no bone
 };
 
 // calib.hip: what mpe_calib_batch accumulates and mpe_calib_step reads.  The Levenberg-Marquardt state of the cameras lives
@@ -404,6 +406,9 @@ hipError_t launch_skel_reset(hipStream_t s, mpe_skel_state *st);
 hipError_t launch_skel_observe(hipStream_t s, mpe_skel_state *st, const mpe_skel_args &a);
 hipError_t launch_skel_update(hipStream_t s, mpe_skel_state *st, int min_samples);
 hipError_t launch_skel_fit(hipStream_t s, mpe_skel_state *st, const mpe_skel_args &a);
+// skel_refine.hip
+int skel_refine_tables(const int32_t *bones, int n_bones, int J, std::vector<uint32_t> *tab);
+hipError_t launch_skel_refine(hipStream_t s, const DevCfg *cfg, int V, mpe_skel_state *st, const mpe_batch &b, const mpe_body_refine_args &a);
 
 // track_score.hip
 hipError_t launch_track_score_reset(hipStream_t s, mpe_track_score_state *st);

@@ -94,6 +94,15 @@ def build_parser(description):
                         'fitted poses are scored, and one further line reports the tracks with a length, the rows and bones fitted, the '
                         'bone-length error before and after and the mean displacement.  Like --track and --smooth it acts in metrics_from_model '
                         'and metrics_from_triangulation; the other harnesses accept and ignore it')
+    p.add_argument('--bones-refine', type=int, default=0, metavar='SWEEPS',
+                   help='as --bones up to the length table, then the body-level fit in the place of the position-based one: every tracked pose '
+                        'is fitted to the pixels and to the bone lengths of its track together with SWEEPS sweeps, 1..64 (mpe_body_refine_batch, on '
+                        'the evaluated frames and their person proposals); the fitted poses are scored, and one further line reports the tracks, '
+                        'rows and bones fitted, the free joints, the one-view joints moved, the mean pixel cost and bone-length error before and '
+                        'after and the mean displacement.  Not together with --bones.')
+    p.add_argument('--bones-weight', type=float, default=300.0, metavar='PX_PER_M',
+                   help='--bones-refine: pixels of reprojection error a metre of bone-length error is worth')
+    p.add_argument('--bones-huber', type=float, default=0.0, metavar='PX', help='--bones-refine: Huber threshold of the pixel term, 0: plain least squares')
     p.add_argument('--bones-min', type=int, default=10, metavar='N', help='--bones: lengths a track needs of a bone before the bone is held to one')
     p.add_argument('--bones-bin', type=float, default=2.0, metavar='MM', help='--bones: bin width of the length histograms, millimetres')
     p.add_argument('--refine', type=int, default=0, metavar='ITERS',
@@ -584,7 +593,14 @@ def run(args, mode):
     bones = int(getattr(args, 'bones', 0) or 0)
     if bones and not (1 <= bones <= 64 and args.bones_bin > 0 and np.isfinite(args.bones_bin)):
         raise ValueError('--bones takes 1 .. 64 sweeps and --bones-bin a width > 0 (got %d, %g)' % (bones, args.bones_bin))
-    if smooth or track_score or bones:
+    bones_refine = int(getattr(args, 'bones_refine', 0) or 0)
+    if bones and bones_refine:
+        raise ValueError('--bones and --bones-refine are two fits of the same poses: give one')
+    if bones_refine and not (1 <= bones_refine <= 64 and args.bones_bin > 0 and np.isfinite(args.bones_bin) and args.bones_weight >= 0
+                             and args.bones_huber >= 0):
+        raise ValueError('--bones-refine takes 1 .. 64 sweeps, --bones-bin a width > 0, --bones-weight and --bones-huber no negative value '
+                         '(got %d, %g, %g, %g)' % (bones_refine, args.bones_bin, args.bones_weight, args.bones_huber))
+    if smooth or track_score or bones or bones_refine:
         args.track = True
     if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
         args.device_metrics = True
@@ -613,6 +629,9 @@ def run(args, mode):
     if bones:
         from .skeleton import SkeletonSummary
         skeleton, boned = eng.skeleton(mode, bin_mm=args.bones_bin), SkeletonSummary()
+    if bones_refine:
+        from .skeleton_refine import RefineSummary
+        skeleton, boned = eng.skeleton(mode, bin_mm=args.bones_bin), RefineSummary()
     if track_score:
         # GT identities: the GT bodies of the evaluated frames through a tracker of their own, same gate and gap
         gt_tracker = eng.tracker('gt', max_gap=args.track_gap, gate=args.track_gate, pcap=TRACK_SCORE_GCAP)
@@ -697,7 +716,11 @@ def run(args, mode):
                 p_sk = p_cur
                 skeleton.observe(p_sk, f_cur, n_in, tr['ids'])
                 skeleton.update(args.bones_min)
-                sk = skeleton.fit(p_sk, f_cur, n_in, tr['ids'], iters=bones)
+                if bones_refine:
+                    sk = eng.body_refine(skeleton, db, persons.index_select(0, keep), n_in, p_sk, f_cur, tr['ids'], sweeps=bones_refine,
+                                         bone_weight=float(args.bones_weight), huber_px=float(args.bones_huber), frames=keep.to(torch.int32))
+                else:
+                    sk = skeleton.fit(p_sk, f_cur, n_in, tr['ids'], iters=bones)
                 p_cur = sk['poses']
             poses, flags = poses.index_copy(0, keep, p_cur), flags.index_copy(0, keep, f_cur)
             torch.cuda.synchronize()
@@ -713,7 +736,7 @@ def run(args, mode):
             if smoother is not None:
                 smoothed.add(p_in.cpu().numpy(), f_in.cpu().numpy(), {k: sm[k].cpu().numpy() for k in ('poses', 'flags', 'n_samples')})
             if skeleton is not None:
-                boned.add(p_sk.cpu().numpy(), {k: sk[k].cpu().numpy() for k in ('poses', 'err', 'n_bones')})
+                boned.add(p_sk.cpu().numpy(), {k: v.cpu().numpy() for k, v in sk.items()})
         elif tracker is not None:
             tr = tracker.update(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
@@ -790,7 +813,12 @@ def run(args, mode):
         print('Smoothed (window %d, decay %g%s): %d joints fitted, %d filled, mean displacement %.3f mm'
               % (smooth, args.smooth_decay, ', fill' if args.smooth_fill else '', r['fitted'], r['filled'], r['mean_move_mm']))
         smoother.close()
-    if skeleton is not None:
+    if skeleton is not None and bones_refine:
+        from .skeleton_refine import report_line as body_line
+        out['bones_refine'] = r = boned.result(skeleton.lengths())
+        print(body_line(bones_refine, args.bones_weight, args.bones_huber, r))
+        skeleton.close()
+    elif skeleton is not None:
         from .skeleton import report_line as bones_line
         out['bones'] = r = boned.result(skeleton.lengths())
         print(bones_line(bones, args.bones_bin, args.bones_min, r))

@@ -109,6 +109,15 @@ class mpe_skel_args(C.Structure):
                 ('d_poses_out', C.c_void_p), ('d_err', C.c_void_p), ('d_n_bones', C.c_void_p)]
 
 
+class mpe_body_refine_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('sweeps', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float),
+                ('bone_weight', C.c_double), ('huber_px', C.c_double),
+                ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p),
+                ('d_persons', C.c_void_p), ('d_frame', C.c_void_p), ('d_poses_out', C.c_void_p), ('d_status', C.c_void_p),
+                ('d_n_views', C.c_void_p), ('d_cost', C.c_void_p), ('d_err', C.c_void_p), ('d_n_bones', C.c_void_p)]
+
+
 class mpe_track_score_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('gcap', C.c_int32), ('joint_flags', C.c_int32), ('threshold_mm', C.c_double),
                 ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p), ('d_assign', C.c_void_p),
@@ -227,6 +236,9 @@ MPE_SMOOTH_MAX_WINDOW, MPE_SMOOTH_FILLED = 15, 2
 # the caps of mpe_skel_create / mpe_skel_fit_batch and the sticky status bit of mpe_skel_observe_batch
 MPE_SKEL_BINS, MPE_SKEL_MAX_BONES, MPE_SKEL_MAX_ITERS, MPE_SKEL_OVER_IDS, MPE_SKEL_MAX_HIST_BYTES = 512, 32, 64, 1, 256 << 20
 
+# per-joint status bits of mpe_body_refine_batch
+MPE_BODY_REFINE_FREE, MPE_BODY_REFINE_MOVED, MPE_BODY_REFINE_BAD_START, MPE_BODY_REFINE_ONE_VIEW, MPE_BODY_REFINE_BAD_FRAME = 1, 2, 4, 8, 16
+
 # the sticky status bit of mpe_track_score_batch and the cap on gid_cap * tid_cap of mpe_track_score_create
 MPE_TRACK_SCORE_OVER_IDS, MPE_TRACK_SCORE_MAX_TABLE = 1, 1 << 22
 
@@ -308,6 +320,7 @@ SYMBOLS = {
     'mpe_skel_get_lengths': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_skel_fit_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_skel_args)]),
     'mpe_skel_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_body_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_body_refine_args)]),
     'mpe_track_score_create': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     'mpe_track_score_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_track_score_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1150,6 +1150,50 @@ class Engine:
         self._chk(self.lib.mpe_refine_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
         return res
 
+    def body_refine(self, sk, db, persons, n_persons, poses, flags, ids, sweeps=8, bone_weight=300.0, huber_px=0.0, joint_mask=None,
+                    threshold=0.5, frames=None):
+        """The body-level fit (mpe_body_refine_batch; include/mpe.h has the rule, harness/skeleton_refine.py states it in
+        numpy and the two agree bit for bit): every row whose track has lengths in the Skeleton `sk` is fitted to the
+        pixels and to the lengths together -- `sweeps` (1 .. 64) sweeps in which every free joint takes one
+        Levenberg-Marquardt step on its reprojection error over the cameras that saw it plus bone_weight (pixels per metre)
+        times the length error of its bones.  db: the batch the poses came from; persons [B,Pcap,V] / n_persons / poses / flags / ids: the pose rows of
+        B frames and the rows' heads; frames: int32 [B] device tensor, the frame of db each pose frame is observed in
+        (None: the poses have the frames of db, in order).  -> dict of device tensors: poses (a new tensor), status u8
+        and n_views u8 [B,Pcap,J] (MPE_BODY_REFINE_* bits), cost f64 [B,Pcap,4] (pixel and bone part before, then after;
+        -1 for a row that is not fitted), err f64 [B,Pcap,2], n_bones u8 [B,Pcap] as fit() returns them.  One launch on
+        the current stream; the state of `sk` is not changed (its launch count goes up by one)."""
+        if not isinstance(sk, Skeleton) or sk.eng is not self:
+            raise ValueError('sk must be a Skeleton of this engine')
+        if not 1 <= int(sweeps) <= L.MPE_SKEL_MAX_ITERS:
+            raise ValueError('sweeps must be within 1 .. %d' % L.MPE_SKEL_MAX_ITERS)
+        if not float(bone_weight) >= 0.0 or not float(huber_px) >= 0.0 or not float(threshold) >= 0.0:
+            raise ValueError('bone_weight, huber_px and threshold must not be negative')
+        base, B = sk._args(poses, flags, n_persons, ids, joint_mask)
+        if persons.dtype != torch.int32 or tuple(persons.shape) != (B, sk.pcap, self.V) or not persons.is_contiguous() or persons.device != poses.device:
+            raise ValueError('persons must be int32 [%d,%d,%d], contiguous, on the device of the poses' % (B, sk.pcap, self.V))
+        if frames is None:
+            if B != db.n_frames:
+                raise ValueError('without frames the poses must have the %d frames of the batch' % db.n_frames)
+        elif frames.dtype != torch.int32 or tuple(frames.shape) != (B,) or not frames.is_contiguous() or frames.device != poses.device:
+            raise ValueError('frames must be int32 [%d], contiguous, on the device of the poses' % B)
+        dev = self.device
+        out = {'poses': torch.empty_like(poses), 'status': torch.empty((B, sk.pcap, self.J), dtype=torch.uint8, device=dev),
+               'n_views': torch.empty((B, sk.pcap, self.J), dtype=torch.uint8, device=dev),
+               'cost': torch.empty((B, sk.pcap, 4), dtype=torch.float64, device=dev),
+               'err': torch.empty((B, sk.pcap, 2), dtype=torch.float64, device=dev),
+               'n_bones': torch.empty((B, sk.pcap), dtype=torch.uint8, device=dev)}
+        if B == 0:                           # nothing to do, and an empty frame map has no address to hand on
+            return out
+        a = L.mpe_body_refine_args()
+        for k in ('n_frames', 'pcap', 'n_joints', 'pose_f64', 'joint_flags', 'joint_mask', 'd_poses', 'd_flags', 'd_n_persons', 'd_track_id'):
+            setattr(a, k, getattr(base, k))
+        a.sweeps, a.threshold, a.bone_weight, a.huber_px = int(sweeps), float(threshold), float(bone_weight), float(huber_px)
+        a.d_persons, a.d_frame = persons.data_ptr(), None if frames is None else frames.data_ptr()
+        a.d_poses_out, a.d_status, a.d_n_views, a.d_cost, a.d_err, a.d_n_bones = (out[k].data_ptr() for k in ('poses', 'status', 'n_views', 'cost',
+                                                                                                               'err', 'n_bones'))
+        self._chk(self.lib.mpe_body_refine_batch(self.ctx, self._stream(), sk.state, C.byref(db.struct), C.byref(a)))
+        return out
+
     def regroup(self, db, persons, n_persons, poses, flags, kind, gate_px=15.0, clip_px=0.0, min_joints=3, joint_mask=None,
                 threshold=0.5, release=True, attach=True, out=None):
         """The person proposals repaired by reprojection consistency (mpe_regroup_batch; include/mpe.h has the rule,

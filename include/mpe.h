@@ -1238,6 +1238,82 @@ int mpe_skel_get_lengths(mpe_ctx *ctx, void *stream, mpe_skel_state *state, doub
 int mpe_skel_fit_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *state, const mpe_skel_args *a);
 int mpe_skel_launches(mpe_ctx *ctx, const mpe_skel_state *state, int64_t *n);
 
+/* The body-level fit: one cost per tracked row -- the reprojection error of every joint over the cameras that saw it plus
+ * the deviation of every bone from the length of its track -- minimised joint by joint, the neighbours held, by
+ * Levenberg-Marquardt steps of three unknowns.  mpe_refine_batch sees the pixels and not the body, mpe_skel_fit_batch the
+ * body and not the pixels; this call stands in for the pair, and it moves the joint one camera saw, which the refinement
+ * declines.  All binary64, every operation named below rounded on its own (nothing fused), quotients and roots correctly
+ * rounded.  harness/skeleton_refine.py states the same in numpy, and the two agree bit for bit.
+ *   Rows.  The pose rows of n_frames frames as mpe_skel_fit_batch takes them; detections, ACTIVE joints, LIVE and
+ *   CONSTRAINED bones and PROCESSED rows exactly as there.  Every row that is not processed is copied through bit for bit.
+ *   Frame map.  d_frame[f] is the frame of batch b whose heads pose-frame f is observed in; NULL: f itself, and n_frames
+ *   is then the batch's.  An entry outside 0 .. b->n_frames - 1: the frame's rows are copied through and every d_status
+ *   of the frame is MPE_BODY_REFINE_BAD_FRAME.
+ *   Observations.  Camera c observes active joint j of a processed row when mpe_reproject_batch, given d_persons /
+ *   d_n_persons / d_flags / joint_flags / joint_mask / threshold, would count (f, p, c, j) on the heads of frame
+ *   d_frame[f]; x, y = that detection.  A flag of any non-zero value is a flag: a joint mpe_smooth_batch filled in
+ *   (MPE_SMOOTH_FILLED) is present and observable.  n_views = the number of observing cameras.  An active joint whose
+ *   start has pc_2 <= 0 (or NaN) in an observing camera is BAD_START: it is held at its input and still anchors its
+ *   bones.  A joint is FREE when it is active, not BAD_START and has an observing camera or is an end of a constrained bone.
+ *   Colours, fixed at create time.  Over j increasing, colour[j] = the least colour no lower-numbered joint that shares a
+ *   bone with j holds.
+ *   Local cost C_j(Y) of joint j at Y, the neighbours at their working values: the left fold from 0.0 over the observing
+ *   cameras in increasing c of rho(e_c) -- projection, e, rho and the weight w_c are those of mpe_refine_batch -- then,
+ *   when kappa = bone_weight (pixels per metre) is > 0, over the constrained bones incident to j in list order, N the
+ *   other end and L the bone's length: d_a = Y_a - N_a ; s = (d_0*d_0 + d_1*d_1) + d_2*d_2 ; l = sqrt(s) ;
+ *   q = kappa*(l - L) ; C = C + q*q.  bone_weight == 0 adds no bone term anywhere.
+ *   One update of a free joint at Y.  A_kl and g_k from the observing cameras exactly as in mpe_refine_batch; then per
+ *   incident constrained bone in list order with l > 0: n_a = d_a / l ; m_a = kappa*n_a ; A_kl = A_kl + m_k*m_l ;
+ *   g_k = g_k + m_k*q (a bone whose l is not > 0 adds nothing here and still counts in the cost).  M = A +
+ *   lambda_j*diag(A), solved by the LDL^T lines of mpe_refine_batch; a pivot that is not > 0 or a delta that is not finite
+ *   rejects the update.  The trial Y + delta is accepted only if pc_2 > 0 there in every observing camera and
+ *   C_j(trial) < C_j(Y) (strict; a NaN rejects).  lambda_j starts at 1e-3 and lives across sweeps: accepted
+ *   max(lambda_j / 10, 1e-12), rejected lambda_j * 10.
+ *   Order.  For sweep = 1 .. sweeps, for colour = 0 .. n_colours - 1, every free joint of that colour takes one update,
+ *   reading its neighbours as they stood before the colour step; two joints of one colour share no bone, so the result is
+ *   that of the joints walked one by one in (sweep, colour, j) order.  The sweep count is fixed: no early exit.
+ *   d_poses_out: a joint that accepted at least one update gets its working value rounded once to the pose type;
+ *   everything else keeps the input bits.  d_status (bits below; _ONE_VIEW: n_views == 1) and d_n_views are 0 in a row
+ *   that is not processed (_BAD_FRAME apart).  d_cost[f][p] = {the pixel part and the bone part of the row's cost at the
+ *   start, then at the end}, -1.0 for a row that is not processed: the pixel part is the fold from 0.0 over the active
+ *   joints in increasing j of the joint's camera fold, the bone part the fold from 0.0 over the constrained bones in list
+ *   order of q*q (0.0 with bone_weight == 0); held joints count.  d_err and d_n_bones as mpe_skel_fit_batch defines them.
+ * One launch whatever n_frames is, counted by mpe_skel_launches, ordered on `stream`; it neither synchronises nor
+ * allocates, changes nothing in the state and needs no weights in the context.  n_frames == 0 does nothing.
+ * MPE_ERR_INVALID, with the values in mpe_last_error: sizes or a pose type other than the state's, n_joints other than the
+ * context's, joint_flags outside {0, 1}, sweeps outside 1 .. MPE_SKEL_MAX_ITERS, a negative (or NaN) bone_weight, huber_px
+ * or threshold, d_poses_out == d_poses, a NULL required pointer, d_frame == NULL with n_frames other than the batch's;
+ * n_frames > 2^23: MPE_ERR_CAPACITY. */
+enum {
+    MPE_BODY_REFINE_FREE = 1,
+    MPE_BODY_REFINE_MOVED = 2,
+    MPE_BODY_REFINE_BAD_START = 4,
+    MPE_BODY_REFINE_ONE_VIEW = 8,
+    MPE_BODY_REFINE_BAD_FRAME = 16
+};
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    int32_t sweeps;                /* 1 .. MPE_SKEL_MAX_ITERS                                        */
+    uint32_t joint_mask;
+    float threshold;               /* 0.5, as for mpe_reproject_batch                                */
+    double bone_weight;            /* pixels per metre, >= 0; 0: no bone term                        */
+    double huber_px;               /* pixels, >= 0; 0: plain least squares                           */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    const int32_t *d_n_persons;    /* [n_frames] */
+    const int32_t *d_track_id;     /* [n_frames][pcap], mpe_track_batch's */
+    const int32_t *d_persons;      /* [n_frames][pcap][V], head ids within frame d_frame[f] of the batch */
+    const int32_t *d_frame;        /* [n_frames] or NULL */
+    void *d_poses_out;             /* the type and shape of d_poses, another buffer */
+    uint8_t *d_status, *d_n_views; /* [n_frames][pcap][J] */
+    double *d_cost;                /* [n_frames][pcap][4] */
+    double *d_err;                 /* [n_frames][pcap][2] */
+    uint8_t *d_n_bones;            /* [n_frames][pcap] */
+} mpe_body_refine_args;
+int mpe_body_refine_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *state, const mpe_batch *b, const mpe_body_refine_args *a);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

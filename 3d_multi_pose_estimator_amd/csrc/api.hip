@@ -1851,6 +1851,42 @@ int mpe_regroup_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_
     return MPE_OK;
 }
 
+int mpe_consolidate_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_consolidate_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    const int J = ctx->cfg.n_joints;
+    if (a->n_frames != b->n_frames || a->n_joints != J)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: %d frames, the batch has %d; %d joints, the context has %d", a->n_frames,
+                    b->n_frames, a->n_joints, J);
+    if (a->pcap < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: pcap %d must be at least 1", a->pcap);
+    if ((a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: pose_f64 %d and joint_flags %d must be 0 or 1", a->pose_f64, a->joint_flags);
+    if (a->pcap > MPE_REGROUP_MAX_PERSONS)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_consolidate_batch: pcap %d over %d", a->pcap, MPE_REGROUP_MAX_PERSONS);
+    if (!(a->merge_m > 0.0) || !(a->found_m > 0.0) || !(a->clip_m >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: merge_m %g and found_m %g must be positive and clip_m %g must not be negative",
+                    a->merge_m, a->found_m, a->clip_m);
+    if (a->min_joints < 1 || a->min_joints > J) return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: min_joints %d outside 1..%d", a->min_joints, J);
+    if (a->found_min_views < 2) return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: found_min_views %d must be at least 2", a->found_min_views);
+    if (a->fcap < 1 || a->fcap > MPE_CONSOLIDATE_MAX_FREE)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: fcap %d outside 1..%d", a->fcap, MPE_CONSOLIDATE_MAX_FREE);
+    if (a->fcap * (3 * J + 1) > MPE_CONSOLIDATE_RAY_DOUBLES)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_consolidate_batch: fcap %d with %d joints over %d ray doubles", a->fcap, J, MPE_CONSOLIDATE_RAY_DOUBLES);
+    if (a->flags == 0 || (a->flags & ~(uint32_t)(MPE_CONSOLIDATE_MERGE | MPE_CONSOLIDATE_FOUND)))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: flags %u must be MPE_CONSOLIDATE_MERGE, MPE_CONSOLIDATE_FOUND or both", a->flags);
+    if (b->n_frames == 0) return MPE_OK;
+    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: NULL argument");
+    if (!a->d_persons_out || !a->d_n_persons_out || !a->d_change || !a->d_n_views || !a->d_dist || !a->d_pair || !a->d_free || !a->d_counts ||
+        !a->d_status)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: NULL output");
+    HIPCHK(ctx, launch_consolidate(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, ctx->cfg.max_heads_per_frame,
+                                   ctx->d_status, *b, *a));
+    return MPE_OK;
+}
+
 static int geom_checks(mpe_ctx *ctx, const mpe_geom_args *a, const char *who) {
     if (!a) return fail(ctx, MPE_ERR_INVALID, "%s: NULL argument", who);
     if (!(a->sigma_m > 0.0) || !(a->clip_m >= 0.0))

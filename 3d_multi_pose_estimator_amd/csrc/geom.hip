@@ -6,14 +6,15 @@
 // exceed GEOM_LDS_BYTES, in the context's table (indexed by the batch's head number; same code, same bits).  Phase 0:
 // the camera centres (thread c) and the word of every head (thread h: presence, the caller's joint mask, the confidence
 // test).  Phase 1: the ray of every (head, joint) that may vote, ONCE (a head takes part in (V - 1) P edge-nodes):
-// undistort_point of dlt_common.h, two Newton steps on the lens model, the rotation, the norm.  Phase 2: a 32-lane half of a wave is one edge-node (the pair
+// undistort_point of dlt_common.h, two Newton steps on the lens model, the rotation, the norm (rays64.h, shared with
+// consolidate.hip).  Phase 2: a 32-lane half of a wave is one edge-node (the pair
 // comes from the table k_topology / k_topology_explicit wrote, so implicit and explicit lists are one code path; the
 // pairs of 32 iterations are fetched by one load per lane beforehand, the loop itself touches the head records only),
 // lane j owns joint j: closest points of the two rays, clamped to the front of both cameras, their distance.  The votes
 // of the half are a ballot; every lane then folds the distances in increasing j through shuffles (a fixed order, whatever
 // the lanes did) and lane 0 stores.  No atomics.  The file turns contraction off; f64 quotients and roots are the
 // language's correctly rounded ones.
-#include "dlt_common.h"
+#include "rays64.h"
 
 #pragma clang fp contract(off)
 
@@ -43,32 +44,6 @@ struct GeomK {
 // per head: J unit rays (three doubles each), then one 8-byte word: the joints that may vote | the camera
 __device__ inline size_t rec_doubles(int J) { return (size_t)J * 3 + 1; }
 
-// Two Newton steps on the lens model from undistort_point's (x, y), the header's lines: the five fixed-point iterations
-// leave up to 1.5e-2 px at the image border, the steps bring a ray within 1e-6 px of its pixel everywhere.
-__device__ inline void polish_point(const DevCfg *cfg, int cam, double u, double v, double *px, double *py) {
-    const float *K = cfg->K[cam];
-    const double *dc = cfg->dist[cam];
-    const double k1 = dc[0], k2 = dc[1], p1 = dc[2], p2 = dc[3], k3 = dc[4];
-    const double xt = (u - (double)K[2]) * (1.0 / (double)K[0]), yt = (v - (double)K[5]) * (1.0 / (double)K[4]);
-    double x = *px, y = *py;
-    for (int it = 0; it < 2; ++it) {
-        const double r = x * x + y * y;
-        const double f = 1.0 + ((k3 * r + k2) * r + k1) * r;
-        const double fd = ((3.0 * k3) * r + 2.0 * k2) * r + k1;
-        const double tx = 2.0 * x, ty = 2.0 * y;
-        const double ex = ((x * f + p1 * (tx * y)) + p2 * (r + tx * x)) - xt;
-        const double ey = ((y * f + p1 * (r + ty * y)) + p2 * (tx * y)) - yt;
-        const double a = ((f + (tx * x) * fd) + p1 * ty) + (3.0 * p2) * tx;
-        const double b = ((tx * y) * fd + p1 * tx) + p2 * ty;
-        const double d = ((f + (ty * y) * fd) + (3.0 * p1) * ty) + p2 * tx;
-        const double det = a * d - b * b;
-        const double nx = x - (d * ex - b * ey) / det, ny = y - (a * ey - b * ex) / det;
-        x = nx, y = ny;
-    }
-    *px = x;
-    *py = y;
-}
-
 template <bool TABLE>
 __global__ void __launch_bounds__(GEOM_THREADS) k_geom(const DevCfg *__restrict__ cfg, GeomK a) {
     extern __shared__ double s_dyn[];
@@ -91,8 +66,7 @@ __global__ void __launch_bounds__(GEOM_THREADS) k_geom(const DevCfg *__restrict_
 
     // phase 0: the camera centres; per head the joints that may vote (present, asked for, confident) and the camera
     if (t < a.V) {
-        const double *T = cfg->P[t];
-        for (int k = 0; k < 3; ++k) s_o[t][k] = -((T[k] * T[3] + T[4 + k] * T[7]) + T[8 + k] * T[11]);
+        camera_centre(cfg, t, s_o[t]);
     }
     for (int h = t; h < H; h += GEOM_THREADS) {
         const int c = a.head_cam[h0 + h];
@@ -111,14 +85,7 @@ __global__ void __launch_bounds__(GEOM_THREADS) k_geom(const DevCfg *__restrict_
         if (!(((uint32_t)word.x >> j) & 1u)) continue;
         const int c = word.y;
         const double *px = a.xy + ((size_t)(h0 + h) * a.J + j) * 2;
-        double x, y;
-        dltc::undistort_point(cfg, c, px[0], px[1], &x, &y);
-        polish_point(cfg, c, px[0], px[1], &x, &y);
-        const double *T = cfg->P[c];
-        const double q0 = (T[0] * x + T[4] * y) + T[8], q1 = (T[1] * x + T[5] * y) + T[9], q2 = (T[2] * x + T[6] * y) + T[10];
-        const double n = sqrt((q0 * q0 + q1 * q1) + q2 * q2);
-        double *r = heads + (size_t)h * rec + (size_t)j * 3;
-        r[0] = q0 / n, r[1] = q1 / n, r[2] = q2 / n;
+        unit_ray(cfg, c, px[0], px[1], heads + (size_t)h * rec + (size_t)j * 3);
     }
     __syncthreads();                          // (also orders the table's global stores for this workgroup's reads)
 
@@ -144,27 +111,7 @@ __global__ void __launch_bounds__(GEOM_THREADS) k_geom(const DevCfg *__restrict_
             const bool vote = inside && mine && c1 != c2 && ((((uint32_t)w1.x & (uint32_t)w2.x) >> j) & 1u);
             double dist = 0.0;
             if (vote) {
-                const double *p1 = heads + (size_t)h1 * rec + (size_t)j * 3, *p2 = heads + (size_t)h2 * rec + (size_t)j * 3;
-                const double a0 = p1[0], a1 = p1[1], a2 = p1[2], b0 = p2[0], b1 = p2[1], b2 = p2[2];
-                const double o10 = s_o[c1][0], o11 = s_o[c1][1], o12 = s_o[c1][2], o20 = s_o[c2][0], o21 = s_o[c2][1], o22 = s_o[c2][2];
-                const double w0 = o10 - o20, w1_ = o11 - o21, w2_ = o12 - o22;
-                const double b = (a0 * b0 + a1 * b1) + a2 * b2;
-                const double d = (a0 * w0 + a1 * w1_) + a2 * w2_;
-                const double e = (b0 * w0 + b1 * w1_) + b2 * w2_;
-                const double den = 1.0 - b * b;
-                double t1, t2;
-                if (den < 1e-12) {
-                    t1 = 0.0;
-                    t2 = e;
-                } else {
-                    t1 = (b * e - d) / den;
-                    t2 = (e - b * d) / den;
-                }
-                if (t1 < 0.0) t1 = 0.0;
-                if (t2 < 0.0) t2 = 0.0;
-                const double g0 = (o10 + t1 * a0) - (o20 + t2 * b0), g1 = (o11 + t1 * a1) - (o21 + t2 * b1), g2 = (o12 + t1 * a2) - (o22 + t2 * b2);
-                dist = sqrt((g0 * g0 + g1 * g1) + g2 * g2);
-                if (a.clip > 0.0 && dist > a.clip) dist = a.clip;
+                dist = ray_distance(heads + (size_t)h1 * rec + (size_t)j * 3, heads + (size_t)h2 * rec + (size_t)j * 3, s_o[c1], s_o[c2], a.clip);
             }
             const uint32_t votes = (uint32_t)(__ballot(vote) >> (32 * half));
             double sum = 0.0;

@@ -421,6 +421,9 @@ hipError_t launch_refine(hipStream_t s, const DevCfg *cfg, int V, const mpe_batc
 // regroup.hip
 hipError_t launch_regroup(hipStream_t s, const DevCfg *cfg, int V, int min_views, int hmax, int32_t *sticky, const mpe_batch &b,
                           const mpe_regroup_args &a);
+// consolidate.hip
+hipError_t launch_consolidate(hipStream_t s, const DevCfg *cfg, int V, int hmax, int32_t *sticky, const mpe_batch &b,
+                              const mpe_consolidate_args &a);
 // calib.hip
 size_t calib_workspace_doubles(int max_frames, int V);
 hipError_t launch_calib(hipStream_t s, const DevCfg *cfg, int V, mpe_calib_state *st, const mpe_batch &b, const mpe_calib_args &a);

@@ -10,7 +10,7 @@ are IEEE doubles), in the header's order.  The observations of a camera are the 
 As a script:
 
     python -m 3d_multi_pose_estimator_amd.harness.calibrate --testfiles F.json --tmdir DIR --matcher geometric \
-        --rounds R --passes N [--calib-huber PX] [--hold NAME ...] [--regroup PX] [--refine ITERS] [--out tm.json]
+        --rounds R --passes N [--calib-huber PX] [--hold NAME ...] [--regroup PX] [--merge M] [--found M] [--refine ITERS] [--out tm.json]
 
 A round matches, triangulates, (with --regroup) regroups and (with --refine) refines every batch with the current engine,
 keeps batches and poses on the device, runs up to N passes and steps over them, and builds a new engine from the
@@ -392,7 +392,7 @@ def run(args):
     from ..lib import MpeError
     from ..parameters import parameters
     from ..pipeline import Engine
-    from .common import collect_work, match_stage, max_skeletons_per_camera, regroup_stage, report_regroup, teacher_scores
+    from .common import collect_work, match_stage, max_skeletons_per_camera, repair_stage, report_consolidate, report_regroup, teacher_scores
     true_calib = rig_calibration(args)
     names = list(parameters.used_cameras_skeleton_matching)
     calib = true_calib
@@ -420,8 +420,8 @@ def run(args):
     ppc = max(4, args.persons + 1, max_skeletons_per_camera(work))
 
     def stages(eng):
-        """Match, triangulate, (--regroup) regroup and (--refine) refine every batch with `eng`; batches and poses stay on the device."""
-        kept, regrouped = [], []
+        """Match, triangulate, (--regroup) regroup, (--merge, --found) consolidate and (--refine) refine every batch with `eng`; batches and poses stay on the device."""
+        kept, regrouped, consolidated = [], [], []
         for at in range(0, len(work), args.batch):
             chunk = work[at:at + args.batch]
             frames = [{c: [f[c][0], f[c][1]] for c in f if json.loads(f[c][0])} for f, _, _ in chunk]
@@ -431,14 +431,16 @@ def run(args):
             else:
                 persons, n_persons = match_stage(eng, args, db)
             poses, flags = eng.triangulate(db, persons, n_persons, all_joints=True)
-            persons, poses, flags = regroup_stage(eng, args, db, persons, n_persons, poses, flags, 'triang', regrouped,
-                                                  lambda rows: eng.triangulate(db, rows, n_persons, all_joints=True))
+            persons, n_persons, poses, flags = repair_stage(eng, args, db, persons, n_persons, poses, flags, 'triang', regrouped, consolidated,
+                                                            lambda rows, n: eng.triangulate(db, rows, n, all_joints=True))
             if args.refine:
                 eng.refine(db, persons, n_persons, poses, flags, 'triang', max_iters=args.refine, huber_px=args.refine_huber, out=poses)
             kept.append((db, persons, n_persons, poses, flags))
         eng.sync_status()
         if args.regroup:
             report_regroup(args, regrouped)
+        if args.merge or args.found:
+            report_consolidate(args, consolidated)
         return kept
 
     start = start_extrinsics(calib)

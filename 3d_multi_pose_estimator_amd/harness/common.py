@@ -119,27 +119,49 @@ def build_parser(description):
     p.add_argument('--regroup-rounds', type=int, default=1, metavar='N', help='--regroup: alternations of regrouping and the 3D stage')
     p.add_argument('--regroup-min-joints', type=int, default=3, metavar='N', help='--regroup: joints a (skeleton, person) pair needs to be judged at all')
     p.add_argument('--regroup-clip', type=float, default=0.0, metavar='PX', help='--regroup: largest distance a joint contributes, pixels (0: no clip)')
+    p.add_argument('--merge', type=float, default=0.0, metavar='M',
+                   help='after the 3D stage (and after --regroup) two person proposals whose poses lie within M metres of each other and that '
+                        'share no camera are merged into one (mpe_consolidate_batch), and the 3D stage runs again on the new rows; 0: off.  '
+                        'One further line reports the rows merged and founded and the skeletons left free.  It acts in metrics_from_model, '
+                        'metrics_from_triangulation and calibrate; the other harnesses accept and ignore it')
+    p.add_argument('--found', type=float, default=0.0, metavar='M',
+                   help='the skeletons that belong to no person proposal found new ones where their back-projected rays pass within M metres '
+                        'of each other (mpe_consolidate_batch, after --merge); 0: off')
+    p.add_argument('--found-min-views', type=int, default=0, metavar='N',
+                   help='--found: skeletons a founded person needs (0: the larger of 2 and the minimum number of views)')
     return p
 
 
-def regroup_stage(eng, args, db, persons, n_persons, poses, flags, mode, log, stage3d, joint_mask=None):
-    """--regroup: N times {regroup, the 3D stage again on the new rows} -> (persons, poses, flags); without the flag, the
-    arguments.  mode 'mlp' or 'triang'; stage3d(persons) -> (poses, flags); log takes one list per round of the batch's
-    counts and status (host arrays).  joint_mask: the joints whose poses stage3d fills in (None: those of the kind -- a
-    triangulation without all_joints flags the joints outside used_joints as emitted and leaves them at the origin, so
-    its caller names the used joints here)."""
+def repair_stage(eng, args, db, persons, n_persons, poses, flags, mode, log, clog, stage3d, joint_mask=None):
+    """--regroup / --merge / --found: N times {regroup (--regroup), consolidate (--merge, --found), the 3D stage again on the new
+    rows and the new row counts} -> (persons, n_persons, poses, flags); without the flags, the arguments.  mode 'mlp' or
+    'triang'; stage3d(persons, n_persons) -> (poses, flags); log takes one list per round of the batch's regroup counts and
+    status (host arrays), clog the same of consolidate.  joint_mask: the joints whose poses stage3d fills in (None: those of
+    the kind -- a triangulation without all_joints flags the joints outside used_joints as emitted and leaves them at the
+    origin, so its caller names the used joints here)."""
     gate = float(getattr(args, 'regroup', 0.0) or 0.0)
-    if not gate:
-        return persons, poses, flags
+    merge_m, found_m = float(getattr(args, 'merge', 0.0) or 0.0), float(getattr(args, 'found', 0.0) or 0.0)
+    if not gate and not merge_m and not found_m:
+        return persons, n_persons, poses, flags
+    kind = 'est' if mode == 'mlp' else 'triang'
     for rnd in range(max(1, int(args.regroup_rounds))):
-        rg = eng.regroup(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', gate_px=gate,
-                         clip_px=args.regroup_clip, min_joints=args.regroup_min_joints, joint_mask=joint_mask)
-        persons = rg['persons']
-        poses, flags = stage3d(persons)
-        while len(log) <= rnd:
-            log.append([])
-        log[rnd].append({k: rg[k].cpu().numpy() for k in ('counts', 'status')})
-    return persons, poses, flags
+        if gate:
+            rg = eng.regroup(db, persons, n_persons, poses, flags, kind, gate_px=gate, clip_px=args.regroup_clip,
+                             min_joints=args.regroup_min_joints, joint_mask=joint_mask)
+            persons = rg['persons']
+            while len(log) <= rnd:
+                log.append([])
+            log[rnd].append({k: rg[k].cpu().numpy() for k in ('counts', 'status')})
+        if merge_m or found_m:
+            cs = eng.consolidate(db, persons, n_persons, poses, flags, kind, merge_m=merge_m or 0.10, found_m=found_m or 0.05,
+                                 min_joints=args.regroup_min_joints, found_min_views=int(getattr(args, 'found_min_views', 0) or 0) or None,
+                                 joint_mask=joint_mask, merge=bool(merge_m), found=bool(found_m))
+            persons, n_persons = cs['persons'], cs['n_persons']
+            while len(clog) <= rnd:
+                clog.append([])
+            clog[rnd].append({k: cs[k].cpu().numpy() for k in ('counts', 'status')})
+        poses, flags = stage3d(persons, n_persons)
+    return persons, n_persons, poses, flags
 
 
 def report_regroup(args, log):
@@ -151,6 +173,17 @@ def report_regroup(args, log):
          'copied': last['copied']}
     print('Regrouped (gate %g px, %d round%s): %d skeletons released, %d attached, %d left free, %d rows below the minimum number of views'
           % (args.regroup, len(log), '' if len(log) == 1 else 's', r['released'], r['attached'], r['free'], r['below_min_views']))
+    return r
+
+
+def report_consolidate(args, clog):
+    """The further report line of --merge / --found -> its dict: rows merged and founded and skeletons placed over all rounds,
+    skeletons left free after the last."""
+    from .consolidate import summary
+    every, last = summary([o for rnd in clog for o in rnd]), summary(clog[-1] if clog else [])
+    r = {'merged': every['merged'], 'founded': every['founded'], 'placed': every['placed'], 'free': last['free'], 'copied': last['copied']}
+    print('Consolidated (merge %g m, found %g m): %d rows merged, %d founded from %d skeletons, %d left free'
+          % (args.merge, args.found, r['merged'], r['founded'], r['placed'], r['free']))
     return r
 
 
@@ -619,6 +652,7 @@ def run(args, mode):
     last = {}                                                # what the track score of a batch needs from infer_device
     refined = []
     regrouped = []                                           # --regroup: per round, the counts of every batch
+    consolidated = []                                        # --merge / --found: the same of the consolidation
     used_mask = sum(1 << int(j) for j in parameters.used_joints)     # the joints both 3D stages of this script fill in
     if getattr(args, 'track', False):
         from .tracking import TrackSummary
@@ -649,12 +683,12 @@ def run(args, mode):
         t1 = time.time()
         if mode == 'mlp':
             poses, valid = eng.mlp3d(db, persons, n_persons)
-            persons, poses, valid = regroup_stage(eng, args, db, persons, n_persons, poses, valid, mode, regrouped,
-                                                  lambda rows: eng.mlp3d(db, rows, n_persons), used_mask)
+            persons, n_persons, poses, valid = repair_stage(eng, args, db, persons, n_persons, poses, valid, mode, regrouped, consolidated,
+                                                            lambda rows, n: eng.mlp3d(db, rows, n), used_mask)
         else:
             poses, jvalid = eng.triangulate(db, persons, n_persons)
-            persons, poses, jvalid = regroup_stage(eng, args, db, persons, n_persons, poses, jvalid, mode, regrouped,
-                                                   lambda rows: eng.triangulate(db, rows, n_persons), used_mask)
+            persons, n_persons, poses, jvalid = repair_stage(eng, args, db, persons, n_persons, poses, jvalid, mode, regrouped, consolidated,
+                                                             lambda rows, n: eng.triangulate(db, rows, n), used_mask)
         torch.cuda.synchronize()
         t['match'] += t1 - t0
         t['3d'] += time.time() - t1
@@ -691,9 +725,9 @@ def run(args, mode):
             poses, flags = eng.mlp3d(db, persons, n_persons)
         else:
             poses, flags = eng.triangulate(db, persons, n_persons)
-        persons, poses, flags = regroup_stage(eng, args, db, persons, n_persons, poses, flags, mode, regrouped,
-                                              lambda rows: eng.mlp3d(db, rows, n_persons) if mode == 'mlp' else eng.triangulate(db, rows, n_persons),
-                                              used_mask)
+        persons, n_persons, poses, flags = repair_stage(eng, args, db, persons, n_persons, poses, flags, mode, regrouped, consolidated,
+                                                        lambda rows, n: eng.mlp3d(db, rows, n) if mode == 'mlp' else eng.triangulate(db, rows, n),
+                                                        used_mask)
         if refine:
             ref = eng.refine(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', max_iters=refine,
                              huber_px=args.refine_huber, out=poses)
@@ -798,6 +832,8 @@ def run(args, mode):
             print('Mean time for evaluation on the device', t['eval'] / n_data)
     if getattr(args, 'regroup', 0.0):
         out['regroup'] = report_regroup(args, regrouped)
+    if getattr(args, 'merge', 0.0) or getattr(args, 'found', 0.0):
+        out['consolidate'] = report_consolidate(args, consolidated)
     if refine:
         from .refine import summary as refine_summary
         out['refine'] = r = refine_summary(refined)

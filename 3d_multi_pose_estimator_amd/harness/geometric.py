@@ -81,6 +81,28 @@ def _dot(a, b):
     return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
 
 
+def pair_distance(o1, r1, o2, r2, clip=0.0):
+    """The header's closest-point lines, elementwise: the rays (o1, r1) of h1 and (o2, r2) of h2 ([..., 3], broadcast
+    against each other) -> (dist, clamped, parallel): the distance of the two rays at their closest points in front of
+    both cameras (clip > 0 bounds it), whether a ray parameter was negative, whether the den < 1e-12 branch was taken.
+    scores() and harness/consolidate.py both call this."""
+    with np.errstate(all='ignore'):
+        w = o1 - o2
+        b, d, e = _dot(r1, r2), _dot(r1, w), _dot(r2, w)
+        den = 1.0 - b * b
+        parallel = den < 1e-12
+        t1 = np.where(parallel, 0.0, (b * e - d) / den)
+        t2 = np.where(parallel, e, (e - b * d) / den)
+        clamped = (t1 < 0.0) | (t2 < 0.0)
+        t1 = np.where(t1 < 0.0, 0.0, t1)
+        t2 = np.where(t2 < 0.0, 0.0, t2)
+        g = (o1 + t1[..., None] * r1) - (o2 + t2[..., None] * r2)
+        dist = np.sqrt(_dot(g, g))
+        if clip > 0.0:
+            dist = np.where(dist > clip, clip, dist)
+    return dist, clamped, parallel
+
+
 def check_options(J, sigma, clip, min_joints, min_conf):
     if not sigma > 0.0 or not clip >= 0.0:
         raise ValueError('sigma must be positive and clip must not be negative')
@@ -114,21 +136,8 @@ def scores(calib, pb, sigma=0.10, clip=0.5, min_joints=1, joint_mask=None, min_c
     conf = np.asarray(pb.vp, np.float32)[:, :, 0] >= min_conf
     c1, c2 = head_cam[h1], head_cam[h2]
     vote = (c1 != c2)[:, None] & present[h1] & present[h2] & conf[h1] & conf[h2]
-    r1, r2, o1, o2 = r[h1], r[h2], o[c1][:, None, :], o[c2][:, None, :]
+    dist, clamped, parallel = pair_distance(o[c1][:, None, :], r[h1], o[c2][:, None, :], r[h2], clip)
     with np.errstate(all='ignore'):
-        w = o1 - o2
-        b, d, e = _dot(r1, r2), _dot(r1, w), _dot(r2, w)
-        den = 1.0 - b * b
-        parallel = den < 1e-12
-        t1 = np.where(parallel, 0.0, (b * e - d) / den)
-        t2 = np.where(parallel, e, (e - b * d) / den)
-        clamped = (t1 < 0.0) | (t2 < 0.0)
-        t1 = np.where(t1 < 0.0, 0.0, t1)
-        t2 = np.where(t2 < 0.0, 0.0, t2)
-        g = (o1 + t1[..., None] * r1) - (o2 + t2[..., None] * r2)
-        dist = np.sqrt(_dot(g, g))
-        if clip > 0.0:
-            dist = np.where(dist > clip, clip, dist)
         n = vote.sum(axis=1)
         total = np.zeros(len(pairs))
         for j in range(J):

@@ -157,6 +157,17 @@ class mpe_regroup_args(C.Structure):
                 ('d_counts', C.c_void_p), ('d_status', C.c_void_p)]
 
 
+class mpe_consolidate_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float), ('min_joints', C.c_int32),
+                ('merge_m', C.c_double), ('found_m', C.c_double), ('clip_m', C.c_double), ('found_min_views', C.c_int32),
+                ('fcap', C.c_int32), ('flags', C.c_uint32), ('reserved', C.c_int32),
+                ('d_persons', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_poses', C.c_void_p), ('d_flags', C.c_void_p),
+                ('d_persons_out', C.c_void_p), ('d_n_persons_out', C.c_void_p), ('d_change', C.c_void_p), ('d_n_views', C.c_void_p),
+                ('d_dist', C.c_void_p), ('d_pair', C.c_void_p), ('d_free', C.c_void_p), ('d_counts', C.c_void_p),
+                ('d_status', C.c_void_p)]
+
+
 class mpe_calib_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
                 ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float), ('reserved', C.c_int32),
@@ -250,6 +261,11 @@ MPE_REFINE_MAX_ITERS = 64
 MPE_REGROUP_BAD_ROWS, MPE_REGROUP_OVER_CAP = 1, 2
 MPE_REGROUP_RELEASE, MPE_REGROUP_ATTACH = 1, 2
 MPE_REGROUP_MAX_PERSONS = 128
+# per-frame status bits, the pass flags and the caps of mpe_consolidate_batch
+MPE_CONSOLIDATE_BAD_ROWS, MPE_CONSOLIDATE_OVER_CAP, MPE_CONSOLIDATE_FREE_OVER_CAP, MPE_CONSOLIDATE_ROWS_FULL = 1, 2, 4, 8
+MPE_CONSOLIDATE_MERGE, MPE_CONSOLIDATE_FOUND = 1, 2
+MPE_CONSOLIDATE_MAX_FREE = 64
+MPE_CONSOLIDATE_RAY_DOUBLES = 3520
 
 # per-camera status bits of mpe_calib_step and the sums a camera accumulates
 MPE_CALIB_HELD, MPE_CALIB_FEW_OBS, MPE_CALIB_CONVERGED, MPE_CALIB_STALLED, MPE_CALIB_ACCEPTED, MPE_CALIB_REJECTED = 1, 2, 4, 8, 16, 32
@@ -331,6 +347,7 @@ SYMBOLS = {
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_args)]),
     'mpe_regroup_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_regroup_args)]),
+    'mpe_consolidate_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_consolidate_args)]),
     'mpe_calib_create': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     'mpe_calib_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
     'mpe_calib_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1228,6 +1228,55 @@ class Engine:
         self._chk(self.lib.mpe_regroup_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
         return res
 
+    def consolidate(self, db, persons, n_persons, poses, flags, kind, merge_m=0.10, found_m=0.05, clip_m=0.0, min_joints=3,
+                    found_min_views=None, fcap=None, joint_mask=None, threshold=0.5, merge=True, found=True, out=None, n_out=None):
+        """The two repairs regroup leaves open (mpe_consolidate_batch; include/mpe.h has the rule, harness/consolidate.py
+        states it in numpy and the two agree bit for bit): rows whose poses lie within merge_m metres of each other (the
+        tracker's cost) and share no camera are merged into the lower row, and the skeletons no row names found new rows
+        where their rays pass within found_m metres of each other (the geometric matcher's distance, complete linkage).
+        kind and joint_mask as refine takes them; a pair of rows or of skeletons needs min_joints common joints to be
+        scored; clip_m > 0 bounds a joint's ray distance; found_min_views (default: max(2, the context's min_views)) heads
+        a founded row needs; fcap (default: min(max_heads_per_frame, 64)) free skeletons per frame the founding takes;
+        out / n_out: the tensors that take the rows and the row counts (`persons` / `n_persons` themselves consolidate in
+        place).  The two gate defaults are options, not findings.  -> dict of device tensors: persons [B,Pcap,V] i32,
+        n_persons [B] i32, change [B,Pcap,V] u8 (regroup's coding), n_views [B,Pcap] i32, dist [B,Pcap,Pcap] f64 and pair
+        [B,fcap,fcap] f64 (-1: unscored), free [B,fcap] i32 (head id per rank), counts [B,4] i32 (rows merged away, rows
+        founded, heads placed, heads left free), status [B] i32 (MPE_CONSOLIDATE_* bits); one launch on the current stream.
+        A founded row has no pose: run the 3D stage again on the new rows and the new n_persons."""
+        B, tri, joint_mask = self._pose_args(db, persons, n_persons, poses, flags, kind, joint_mask, ('est', 'triang'))
+        if out is None:
+            out = torch.empty_like(persons)
+        elif out.dtype != persons.dtype or tuple(out.shape) != tuple(persons.shape) or not out.is_contiguous() or out.device != persons.device:
+            raise ValueError('out must be a contiguous tensor of the type, shape and device of persons')
+        if n_out is None:
+            n_out = torch.empty_like(n_persons)
+        elif n_out.dtype != n_persons.dtype or tuple(n_out.shape) != tuple(n_persons.shape) or not n_out.is_contiguous() or n_out.device != n_persons.device:
+            raise ValueError('n_out must be a contiguous tensor of the type, shape and device of n_persons')
+        if found_min_views is None:
+            found_min_views = max(2, int(self.params.min_number_of_views))
+        if fcap is None:
+            fcap = max(1, min(self.hpf, L.MPE_CONSOLIDATE_MAX_FREE, L.MPE_CONSOLIDATE_RAY_DOUBLES // (3 * self.J + 1)))
+        fcap = int(fcap)
+        side = min(max(fcap, 0), L.MPE_CONSOLIDATE_MAX_FREE)         # (the entry point refuses an fcap outside 1..64)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        res = {'persons': out, 'n_persons': n_out, 'change': torch.empty((B, self.pcap, self.V), dtype=torch.uint8, device=self.device),
+               'n_views': torch.empty((B, self.pcap), **i32), 'dist': torch.empty((B, self.pcap, self.pcap), **f64),
+               'pair': torch.empty((B, side, side), **f64), 'free': torch.empty((B, side), **i32),
+               'counts': torch.empty((B, 4), **i32), 'status': torch.empty((B,), **i32)}
+        a = L.mpe_consolidate_args()
+        a.n_frames, a.pcap, a.n_joints = B, self.pcap, self.J
+        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
+        a.min_joints, a.merge_m, a.found_m, a.clip_m = int(min_joints), float(merge_m), float(found_m), float(clip_m)
+        a.found_min_views, a.fcap = int(found_min_views), fcap
+        a.flags = (L.MPE_CONSOLIDATE_MERGE if merge else 0) | (L.MPE_CONSOLIDATE_FOUND if found else 0)
+        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
+        a.d_persons_out, a.d_n_persons_out, a.d_change, a.d_n_views = out.data_ptr(), n_out.data_ptr(), res['change'].data_ptr(), res['n_views'].data_ptr()
+        a.d_dist, a.d_pair, a.d_free = res['dist'].data_ptr(), res['pair'].data_ptr(), res['free'].data_ptr()
+        a.d_counts, a.d_status = res['counts'].data_ptr(), res['status'].data_ptr()
+        self._chk(self.lib.mpe_consolidate_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return res
+
     def calibrator(self, kind, huber_px=0.0, min_obs=50, hold=()):
         """A Calibrator for poses of `kind` ('est' or 'triang', as refine takes them): the camera extrinsics refined from
         a recording's own poses, the joints held fixed (mpe_calib_*; include/mpe.h has the rule, harness/calibrate.py

@@ -4,7 +4,8 @@
  *
  *   2D skeletons per camera -> graph featurisation -> 5-layer graph attention network
  *   -> greedy person clustering -> { MLP 3D regression | pairwise-DLT triangulation }
- *   [-> regrouping of the proposals by reprojection consistency (mpe_regroup_batch) -> the 3D stage again].
+ *   [-> regrouping of the proposals by reprojection consistency (mpe_regroup_batch), split persons merged and new ones
+ *   founded from free skeletons (mpe_consolidate_batch) -> the 3D stage again].
  *
  * The reference has no FFI: its operator API is the set of Python symbols that
  * test/metrics_from_model.py:12-24 and test/metrics_from_triangulation.py:13-23 import.
@@ -589,7 +590,8 @@ int mpe_geom_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const m
  *   (required: the context holds no table of this size; it may be NULL only when the batch has no heads, where the table
  *   is empty and nothing is written to it); d_counts [n_frames][4]: entries released, entries attached, heads
  *   named by no row afterwards, persons with a pose and fewer than cfg.min_views heads afterwards; d_status [n_frames].
- * Limits.  The stage does not merge two rows that hold the same body, does not found persons from the heads left free, and
+ * Limits.  The stage does not merge two rows that hold the same body and does not found persons from the heads left free
+ *   (mpe_consolidate_batch, below, does both), and
  *   does not update the pose: the caller alternates 3D stage, regroup, 3D stage again on the new rows.  joint_mask must
  *   name only joints whose pose is filled in: mpe_triangulate_batch without flags bit 0 flags the joints outside
  *   used_joints as emitted and leaves them at the origin, so after it the mask is cfg.used_joint_mask.
@@ -631,6 +633,107 @@ typedef struct {
     int32_t *d_status;             /* [n_frames]                                                     */
 } mpe_regroup_args;
 int mpe_regroup_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_regroup_args *a);
+
+/* Consolidation: the two repairs the regrouping leaves open, between mpe_regroup_batch and the second 3D stage.  MERGE: two
+ * rows that hold the same body -- the greedy clustering gave each two or more views, so both got a pose, a few centimetres
+ * apart -- become one.  FOUND: the skeletons no row names (the clustering missed them, or the release freed them from a
+ * mixed row) found new rows where their back-projected rays meet.  All arithmetic is binary64, every operation named
+ * below rounded on its own (nothing fused), quotients and roots correctly rounded; harness/consolidate.py states the same
+ * in numpy, and the two agree bit for bit on every output.
+ * Inputs.  The batch; d_persons / d_n_persons / d_poses / d_flags / pose_f64 / joint_flags / joint_mask / threshold / pcap
+ *   exactly as mpe_regroup_batch takes them; merge_m > 0 and found_m > 0 (metres), clip_m >= 0, min_joints in 1..n_joints,
+ *   found_min_views >= 2, fcap in 1..MPE_CONSOLIDATE_MAX_FREE with fcap * (3 n_joints + 1) <= MPE_CONSOLIDATE_RAY_DOUBLES,
+ *   flags (MPE_CONSOLIDATE_MERGE | MPE_CONSOLIDATE_FOUND, at least one).  Rows, n = min(max(d_n_persons[f], 0), pcap), "has
+ *   a pose", the bad-row check and the head cap are mpe_regroup_batch's, word for word.  A frame that is
+ *   MPE_CONSOLIDATE_BAD_ROWS or MPE_CONSOLIDATE_OVER_CAP (the sticky status bit, as everywhere) is COPIED THROUGH: its rows and
+ *   d_n_persons_out[f] = d_n_persons[f] unchanged, d_change 0, d_counts 0, d_dist, d_pair and d_free filled with -1,
+ *   d_n_views counted from the rows as they are.
+ * Merge distances.  Joint j of row p is present when the row has a pose, bit j is set in joint_mask, with joint_flags == 1
+ *   d_flags[f][p][j] != 0, and its three coordinates, widened to f64, are finite.  The distance of rows p < q is the cost of
+ *   mpe_track_batch with p in the role of a, over the joints both have in increasing j: dx, dy, dz = a - b; s = dx*dx;
+ *   s = s + dy*dy; s = s + dz*dz; d = sqrt(s); the left-fold sum of d from 0.0, divided by the count n.  With
+ *   n < min_joints, or a result that is not finite, the pair is UNSCORED: -1.  d_dist [n_frames][pcap][pcap] holds the
+ *   distance at [p][q] for p < q < n and -1 everywhere else; it does not depend on d_persons and is written whatever flags.
+ * Merge (MPE_CONSOLIDATE_MERGE), first.  A pair (p, q), p < q < n, is mergeable NOW when neither row has been merged away,
+ *   it is scored and dist < merge_m (strict), and no camera holds an entry >= 0 in both rows as they are now.  The
+ *   mergeable pair of least (dist, p, q) merges: q's entries move into p's open columns, q becomes all -1 and is merged
+ *   away; repeated until no pair is mergeable.  Distances are not recomputed: p keeps its own pose's distances and tests
+ *   disjointness with its union.  Rows are not renumbered and the row count does not fall.  Rows that share a camera are
+ *   never merged: one of the two heads there is wrong, and which is for mpe_regroup_batch's release to decide.
+ * Free heads.  The heads of the frame that no row p < n names (merging does not change them), in increasing head id; K their
+ *   number.  d_free [n_frames][fcap]: the frame-local head id of ranks 0 .. min(K, fcap) - 1, -1 beyond.  With K > fcap the
+ *   frame gets MPE_CONSOLIDATE_FREE_OVER_CAP: the merge stands, nothing is founded and d_pair is -1.
+ * Pair costs.  Free heads a < b of different cameras (a in the role of h1): the mean ray distance of mpe_geom_scores_batch,
+ *   by its ray lines (five-iteration undistortion, two Newton steps, rotation, norm) and its closest-point lines (the
+ *   den < 1e-12 branch, both parameters clamped at 0, clip_m), folded as there: the sum over the voting joints in
+ *   increasing j from 0.0, divided by their number n.  Joint j votes when bit j is set in joint_mask and in both heads'
+ *   d_joint_mask and d_vp[h][j][0] > threshold (strict, mpe_regroup_batch's rule) for both.  With n < min_joints, two heads
+ *   of one camera, a head whose camera index is outside 0..V-1, or a cost that is not finite the pair is UNSCORED: -1.
+ *   d_pair [n_frames][fcap][fcap], indexed by rank, holds the cost at [a][b] for a < b < K and -1 everywhere else; written
+ *   whatever flags.
+ * Found (MPE_CONSOLIDATE_FOUND), after the merge.  A cursor (cost, a, b) starts below every pair.  Repeat: among the pairs with
+ *   both heads free now, scored, cost < found_m and strictly greater than the cursor in (cost, a, b) order, take the least;
+ *   with none, stop.  If the frame holds pcap rows already, set MPE_CONSOLIDATE_ROWS_FULL and stop.  The cursor becomes that
+ *   pair.  The tentative row holds a and b and grows: a candidate is a free head whose camera the tentative row lacks and
+ *   whose cost to EVERY member is scored and < found_m (complete linkage: no summation order); its key is (the largest of
+ *   those costs, head id); the candidate of least key joins; repeated until there is no candidate.  With found_min_views
+ *   heads or more the row is written at index n (every other column -1), n rises by one and the members stop being free;
+ *   otherwise the row is dissolved: its heads stay free, and the cursor keeps the seed from seeding again (every pair seeds
+ *   at most once, in increasing order).  Rows without a pose that exist already are left alone, and their heads are not
+ *   free.  A founded row has no pose yet: the caller runs the 3D stage again on d_persons_out AND d_n_persons_out.
+ * Outputs.  d_persons_out [n_frames][pcap][V] (may be d_persons itself); d_n_persons_out [n_frames] (may be d_n_persons):
+ *   n plus the rows founded; d_change [n_frames][pcap][V], mpe_regroup_batch's coding: bit 0, the entry held a head and
+ *   holds another or none now; bit 1, it holds a head it did not hold before; d_n_views [n_frames][pcap]: entries >= 0 of the
+ *   rows below the new count, 0 beyond; d_dist, d_pair, d_free as above (d_dist f64, d_pair f64, d_free i32);
+ *   d_counts [n_frames][4]: rows merged away, rows founded, heads placed by founding, heads named by no row afterwards;
+ *   d_status [n_frames].
+ * One launch (one workgroup per frame), ordered on `stream`; keeps no state, neither synchronises nor allocates; n_frames == 0
+ *   does nothing; works on a context without weights.  MPE_ERR_INVALID for a merge_m or found_m that is not > 0 (or NaN), a
+ *   negative (or NaN) clip_m, min_joints outside 1..n_joints, found_min_views < 2, fcap outside
+ *   1..MPE_CONSOLIDATE_MAX_FREE, flags 0 or with unknown bits, a NULL output, n_frames other than the batch's, n_joints
+ *   other than the context's, pcap < 1 or a pose_f64 / joint_flags other than 0 or 1; MPE_ERR_CAPACITY for
+ *   pcap > MPE_REGROUP_MAX_PERSONS or fcap * (3 n_joints + 1) > MPE_CONSOLIDATE_RAY_DOUBLES. */
+enum {
+    MPE_CONSOLIDATE_BAD_ROWS = 1,
+    MPE_CONSOLIDATE_OVER_CAP = 2,
+    MPE_CONSOLIDATE_FREE_OVER_CAP = 4,
+    MPE_CONSOLIDATE_ROWS_FULL = 8
+};
+enum {
+    MPE_CONSOLIDATE_MERGE = 1,
+    MPE_CONSOLIDATE_FOUND = 2
+};
+#define MPE_CONSOLIDATE_MAX_FREE 64
+#define MPE_CONSOLIDATE_RAY_DOUBLES 3520   /* 64 free heads of 18 joints: 3 doubles a ray, one word a head */
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t joint_mask;           /* bit j: joint j may count                                       */
+    float threshold;               /* 0.5, as for mpe_regroup_batch                                  */
+    int32_t min_joints;            /* 1 .. n_joints: joints a scored pair (of rows, of heads) needs  */
+    double merge_m;                /* metres, > 0: rows merge when their poses are closer            */
+    double found_m;                /* metres, > 0: heads link when their rays pass closer            */
+    double clip_m;                 /* metres, >= 0; 0: no clip                                       */
+    int32_t found_min_views;       /* >= 2: heads a founded row needs                                */
+    int32_t fcap;                  /* 1 .. MPE_CONSOLIDATE_MAX_FREE: free heads per frame taken      */
+    uint32_t flags;                /* MPE_CONSOLIDATE_MERGE | MPE_CONSOLIDATE_FOUND                  */
+    int32_t reserved;
+    const int32_t *d_persons;      /* [n_frames][pcap][V]                                            */
+    const int32_t *d_n_persons;    /* [n_frames]                                                     */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    int32_t *d_persons_out;        /* [n_frames][pcap][V]                                            */
+    int32_t *d_n_persons_out;      /* [n_frames]                                                     */
+    uint8_t *d_change;             /* [n_frames][pcap][V]                                            */
+    int32_t *d_n_views;            /* [n_frames][pcap]                                               */
+    double *d_dist;                /* [n_frames][pcap][pcap]                                         */
+    double *d_pair;                /* [n_frames][fcap][fcap]                                         */
+    int32_t *d_free;               /* [n_frames][fcap]                                               */
+    int32_t *d_counts;             /* [n_frames][4]                                                  */
+    int32_t *d_status;             /* [n_frames]                                                     */
+} mpe_consolidate_args;
+int mpe_consolidate_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_consolidate_args *a);
 
 /* Clustering quality of the matching stage (test/sm_metrics.py:125-229, test/sm_metrics_without_gt.py:131-170): labels
  * from proposals, the ground-truth grouping of a frame's bodies_3D, and the four scores of two labelings.

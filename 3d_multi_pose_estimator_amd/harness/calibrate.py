@@ -67,14 +67,12 @@ def project_camera(T, kd, K, X0, X1, X2, jacobian=False):
     return out
 
 
-def engine_cameras(calib):
-    """Indices into the calibration's arrays of the cameras an Engine is built for, in its order."""
-    return [calib.index(c) for c in calib.params.used_cameras_skeleton_matching]
+engine_cameras = R.engine_cameras             # the one mapping (harness/reprojection.py), under the name this module's callers use
 
 
 def start_extrinsics(calib):
     """cfg.P of an Engine built from `calib`: [V,3,4] float64."""
-    return np.ascontiguousarray(np.asarray(calib.P, np.float64)[engine_cameras(calib)])
+    return R.engine_calibration(calib)[0]
 
 
 def new_sums(V):
@@ -93,15 +91,14 @@ def observation_terms(calib, E, pb, persons, n_persons, poses, flags, joint_mask
     E = np.asarray(E, np.float64)
     sel, xy = R.selection(pb, persons, n_persons, flags, joint_mask, threshold)
     F, Pcap, V, J = sel.shape
-    idx = engine_cameras(calib)
-    _, kd, K = camera_constants64(calib)
+    _, kd, K = camera_constants64(calib)                                          # by camera slot, as E is
     X = poses.astype(np.float64)
     terms = np.zeros((F, Pcap, V, J, SUMS))
     summed = np.zeros(sel.shape, bool)
     finite = np.isfinite(X).all(axis=-1)                                          # [F,Pcap,J]
     with np.errstate(all='ignore'):
         for c in range(V):
-            p = project_camera(E[c], kd[idx[c]], K[idx[c]], X[..., 0], X[..., 1], X[..., 2], jacobian=True)
+            p = project_camera(E[c], kd[c], K[c], X[..., 0], X[..., 1], X[..., 2], jacobian=True)
             ok = sel[:, :, c] & finite & (p['pc'][2] > 0.0) & np.isfinite(p['px']) & np.isfinite(p['py'])
             summed[:, :, c] = ok
             rx = p['px'] - xy[:, :, c, :, 0]

@@ -7,16 +7,16 @@ score is rounded to float32.  Vectorised over the edge-nodes (and their joints) 
 """
 import numpy as np
 
+from .reprojection import engine_calibration
+
 DEFAULTS = dict(sigma=0.10, clip=0.5, min_joints=1, joint_mask=None, min_conf=0.0)
 
 
 def camera_constants(calib):
     """-> (K [V,3,3] f64 from the float32 intrinsics, dist [V,5], T [V,3,4]) in the order of the matching cameras (the index
-    head_cam holds)."""
-    p = calib.params
-    idx = [calib.index(c) for c in p.used_cameras_skeleton_matching]
-    return (np.asarray(calib.K32, np.float32)[idx].astype(np.float64), np.asarray(calib.dist, np.float64)[idx],
-            np.asarray(calib.P, np.float64)[idx])
+    head_cam holds; reprojection.engine_calibration)."""
+    P, dist, K32 = engine_calibration(calib)
+    return K32.astype(np.float64), dist, P
 
 
 def undistort(K, dist, cam, u, v):

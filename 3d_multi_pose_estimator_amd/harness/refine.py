@@ -15,9 +15,10 @@ MAX_ITERS = 64
 
 
 def camera_constants64(calib):
-    """-> (T [V,3,4], kd [V,3], K [V,3,3]) float64: P and the radial terms as stored, the float32 K widened."""
-    return (np.ascontiguousarray(calib.P, np.float64), np.ascontiguousarray(calib.dist[:, [0, 1, 4]], np.float64),
-            np.ascontiguousarray(calib.K32, np.float32).astype(np.float64))
+    """-> (T [V,3,4], kd [V,3], K [V,3,3]) float64, by camera slot (reprojection.engine_calibration): P and the radial
+    terms as stored, the float32 K widened."""
+    P, dist, K32 = R.engine_calibration(calib)
+    return P, np.ascontiguousarray(dist[:, [0, 1, 4]]), K32.astype(np.float64)
 
 
 def project64(T, kd, K, X0, X1, X2, jacobian=False):

@@ -46,11 +46,25 @@ def add_joint2_from_minus1(frames):
     return n
 
 
+def engine_cameras(calib):
+    """Indices into the calibration's arrays of the cameras an Engine is built for, in its order."""
+    return [calib.index(c) for c in calib.params.used_cameras_skeleton_matching]
+
+
+def engine_calibration(calib):
+    """-> (P [V,3,4] float64, dist [V,5] float64, K32 [V,3,3] float32) as the calibration stores them, over the cameras an
+    Engine is built for, in its order: row c belongs to camera slot c, the index head_cam and the columns of `persons`
+    hold.  A calibration may configure more cameras than are used (a camera-subset preset), so its own arrays are not
+    indexed by slot; every statement module takes its camera constants from here."""
+    idx = engine_cameras(calib)
+    return (np.ascontiguousarray(np.asarray(calib.P, np.float64)[idx]), np.ascontiguousarray(np.asarray(calib.dist, np.float64)[idx]),
+            np.ascontiguousarray(np.asarray(calib.K32, np.float32)[idx]))
+
+
 def camera_constants(calib):
-    """-> (T [V,3,4], kd [V,3], K [V,3,3]) float32."""
-    return (np.ascontiguousarray(calib.P, np.float64).astype(np.float32),
-            np.ascontiguousarray(calib.dist[:, [0, 1, 4]], np.float64).astype(np.float32),
-            np.ascontiguousarray(calib.K32, np.float32))
+    """-> (T [V,3,4], kd [V,3], K [V,3,3]) float32, by camera slot (engine_calibration)."""
+    P, dist, K32 = engine_calibration(calib)
+    return P.astype(np.float32), np.ascontiguousarray(dist[:, [0, 1, 4]]).astype(np.float32), K32
 
 
 def project(T, kd, K, X, Y, Z):

@@ -63,8 +63,7 @@ class Scene:
 
     def with_detections(self, noise_px, seed):
         """A copy of the batch whose detections are the rule's own projection of the bodies (+ seeded noise)."""
-        _, kd, K = pkg('harness.refine').camera_constants64(self.calib)
-        idx = CB().engine_cameras(self.calib)
+        _, kd, K = pkg('harness.refine').camera_constants64(self.calib)            # by camera slot, as E_true is
         rng = np.random.default_rng(seed)
         pb = copy.copy(self.pb)
         pb.xy = np.array(self.pb.xy, np.float64, copy=True)
@@ -74,7 +73,7 @@ class Scene:
                 c = int(pb.head_cam[h0 + i])
                 o = self.owners[f][self.names[c]][int(pb.skeleton_index[h0 + i])]
                 X = self.truth[f, o]
-                p = CB().project_camera(self.E_true[c], kd[idx[c]], K[idx[c]], X[:, 0], X[:, 1], X[:, 2])
+                p = CB().project_camera(self.E_true[c], kd[c], K[c], X[:, 0], X[:, 1], X[:, 2])
                 noise = noise_px * rng.normal(size=(J, 2)) if noise_px else np.zeros((J, 2))
                 pb.xy[h0 + i, :, 0], pb.xy[h0 + i, :, 1] = p['px'] + noise[:, 0], p['py'] + noise[:, 1]
         return pb
@@ -123,13 +122,12 @@ def camera_residuals(scene, c):
     calib = scene.calib
     sel, xy = pkg('harness.reprojection').selection(scene.pb, scene.persons, scene.n_persons, scene.flags, ALL_JOINTS)
     _, kd, K = pkg('harness.refine').camera_constants64(calib)
-    k = CB().engine_cameras(calib)[c]
     pick = sel[:, :, c]
     X = scene.truth[pick]
     obs = xy[:, :, c][pick]
 
     def fn(xi, E0):
-        p = CB().project_camera(CB().compose(E0, xi), kd[k], K[k], X[:, 0], X[:, 1], X[:, 2])
+        p = CB().project_camera(CB().compose(E0, xi), kd[c], K[c], X[:, 0], X[:, 1], X[:, 2])
         return np.concatenate([p['px'] - obs[:, 0], p['py'] - obs[:, 1]])
     return fn
 
@@ -174,11 +172,12 @@ def host_trial(A, g, lam, Ea):
 
 # ---- the small device cases --------------------------------------------------------------------------------------------
 
-def small_damage(frames, owners):
-    """Frame 0: person 1 loses its skeleton in the third camera; frame 1: a joint removed from a skeleton; frame 2: a
-    confidence below the threshold and one exactly at it."""
-    cams = list(frames[0])
-    cam = cams[2]
+def small_damage(frames, owners, used=None):
+    """Frame 0: person 1 loses its skeleton in the third camera (of two used cameras: the first); frame 1: a joint removed
+    from a skeleton; frame 2: a confidence below the threshold and one exactly at it.  used: the cameras the rig's engine
+    takes (default: every stream of the frame)."""
+    cams = list(frames[0]) if used is None else list(used)
+    cam = cams[2 % len(cams)]
     i = owners[0][cam].index(1)
     sks = json.loads(frames[0][cam][0])
     del sks[i]
@@ -198,7 +197,9 @@ def small(variant='panoptic', n_frames=3, n_bodies=2, pcap=None, seed=4300):
     """n_frames of the rig x n_bodies persons with the damage above, 1 px of noise, and both kinds of poses: 'triang' the
     bodies moved by a few millimetres (float64, joint flags, one of them off, all joints) and 'est' (float32, person
     flags, one of them off, the used joints)."""
-    s = Scene(variant, n_frames, n_bodies, seed=seed, noise_px=1.0, pcap=pcap, damage=small_damage if n_frames >= 3 and n_bodies >= 2 else None)
+    used = list(env(variant).params.used_cameras_skeleton_matching)
+    s = Scene(variant, n_frames, n_bodies, seed=seed, noise_px=1.0, pcap=pcap,
+              damage=(lambda frames, owners: small_damage(frames, owners, used)) if n_frames >= 3 and n_bodies >= 2 else None)
     rng = np.random.default_rng(seed + 7)
     tri = s.truth + rng.uniform(-0.004, 0.004, s.truth.shape)
     jf = s.flags.copy()

@@ -10,13 +10,13 @@ import json
 import numpy as np
 
 from conftest import env, oracle, pkg
-from refine_cases import only_seen_by
+from refine_cases import RIG_FRAMES, only_seen_by
 from regroup_cases import drop_skeleton, duplicate_skeleton, keep_joints, rows_from_owners, same_bits  # noqa: F401
 
 J = 18
 SHIFT = np.array([0.02, -0.01, 0.015])        # metres between the poses of two rows of one body: 27 mm
 NAMES = ('clean', 'split', 'chain', 'shared', 'edge', 'edge_up', 'lost', 'stray', 'short', 'unscored', 'tie', 'full', 'free_cap',
-         'bad_rows', 'degenerate', 'arplab', 'explicit', 'lanes')
+         'bad_rows', 'degenerate', 'arplab', 'explicit', 'lanes', 'ring23', 'arprobot')
 KEYS = ('persons', 'n_persons', 'change', 'n_views', 'dist', 'pair', 'free', 'counts', 'status')
 _made = {}
 
@@ -52,6 +52,10 @@ def spec_of(name):
         return 3, S(persons=3, noise_px=1.0), 1
     if name == 'lanes':
         return 4, S(persons=10), 0
+    if name == 'ring23':
+        return 3, S(persons=3, noise_px=1.0), 1                           # (frames 1 and 2: no body has a row)
+    if name == 'arprobot':
+        return 3, S(persons=3, noise_px=1.0), 1
     raise KeyError(name)
 
 
@@ -63,14 +67,17 @@ class Case:
     def __init__(self, name, pcap=None):
         syn, onp = pkg('synthetic'), oracle()
         self.name = name
-        self.variant = 'arplab' if name == 'arplab' else 'panoptic'
+        self.variant = name if name in ('arplab', 'ring23', 'arprobot') else 'panoptic'
         self.env = env(self.variant)
         calib, params = self.calib, self.params = self.env.calib, self.env.params
         cams = list(params.used_cameras_skeleton_matching)
         names = list(params.camera_names)
         self.cams, V = cams, len(cams)
         F, spec, rowless = spec_of(name)
-        frames, gts = syn.make_frames(calib, F, spec, seed=1234)
+        if name in RIG_FRAMES:
+            frames, gts = zip(*[syn.make_frame(calib, i, spec, seed=1234) for i in RIG_FRAMES[name]])
+        else:
+            frames, gts = syn.make_frames(calib, F, spec, seed=1234)
         frames = [{c: list(v) for c, v in f.items()} for f in frames]
         owners = [{c: list(v) for c, v in g['owner'].items()} for g in gts]
         bodies = [np.asarray(g['persons'], np.float64) for g in gts]
@@ -109,6 +116,14 @@ class Case:
             owners[1] = {c: [] for c in names}
         if name == 'free_cap':
             self.opts['fcap'] = 4
+        if name == 'ring23':
+            # frame 1: 69 heads less five skeletons, all free: exactly the 64 lanes of a wave, the 64 bits of a word
+            for cam, b in ((0, 0), (1, 0), (2, 1), (3, 1), (4, 2)):
+                drop_skeleton(frames[1], owners[1], names[cam], b)
+            self.opts['fcap'] = 64
+        if name == 'arprobot':
+            # two frames carry the two used streams only, the third all six
+            frames = [{c: v for c, v in fr.items() if c in cams or f == 2} for f, fr in enumerate(frames)]
 
         self.frames, self.owners, self.bodies = frames, owners, bodies
         self.processed = [onp.processed_input(f) for f in frames]
@@ -148,6 +163,14 @@ class Case:
                 splits[0] = [[2, 3, 4]]
             if name == 'degenerate' and f == 0:
                 keep = []
+            if name == 'ring23':
+                # frame 0: body 0 split into cameras 0..11 and 12..22, body 2 without a row; frames 1 and 2: no rows at all
+                if f == 0:
+                    splits[0] = [list(range(12, V))]
+                else:
+                    keep = []
+            if name == 'arprobot' and f == 1:
+                splits[0] = [[1]]                                         # a row per camera
             plans.append((keep, splits))
         built = []
         for f, (keep, splits) in enumerate(plans):
@@ -331,6 +354,24 @@ class Case:
         if name == 'arplab':
             assert pb.V == 6 and (c[:, 0] == 1).all() and (c[:, 1] == 1).all()
             assert all(self.founded(o, f) == [self.heads_of(f, 2)] for f in range(F))
+        if name == 'ring23':
+            assert pb.V == 23 and [pb.frame_counts(f)[1] for f in range(F)] == [69, 64, 69] and self.n_persons.tolist() == [3, 0, 0]
+            # frame 0: the two halves merged into a row of 23 views, body 2 founded with 23 views
+            assert c[0].tolist() == [1, 1, 23, 0] and o['status'][0] == 0 and self.founded(o, 0) == [self.heads_of(0, 2)]
+            assert o['n_views'][0, [0, 1, 3]].tolist() == [23, 23, 23] and (o['persons'][0, 0] >= 0).all() and (o['persons'][0, 2] == -1).all()
+            assert max(len(t[3]) for t in trace if t[0] == 0) == 23
+            # frame 1: 64 free heads in 64 slots, status 0, the three bodies founded
+            assert o['status'][1] == 0 and (o['free'][1] >= 0).sum() == 64 and o['free'].shape == (F, 64) and (o['pair'][1] >= 0).any()
+            assert sorted(self.founded(o, 1), key=sorted) == sorted((self.heads_of(1, b) for b in range(3)), key=sorted)
+            assert c[1].tolist() == [0, 3, 64, 0]
+            # frame 2: 69 free heads do not fit
+            assert o['status'][2] == CS.FREE_OVER_CAP and o['n_persons'][2] == 0 and c[2].tolist() == [0, 0, 0, 69] and (o['pair'][2] == -1).all()
+        if name == 'arprobot':
+            assert pb.V == 2 and [len(f) for f in self.frames] == [2, 2, 6] and not o['status'].any()
+            assert c[:, 0].tolist() == [0, 1, 0] and (c[:, 1:] == [1, 2, 0]).all()
+            for f in range(F):
+                assert self.founded(o, f) == [self.heads_of(f, 2)] and len(self.heads_of(f, 2)) == 2
+                assert [len(t[3]) for t in trace if t[0] == f and t[4]] == [2]        # the seed pair is the whole row: no growth round
         if name == 'explicit':
             assert pb.en_pair is not None and c.tolist() == [[1, 1, 5, 0]] and self.founded(o, 0) == [self.heads_of(0, 3)]
         if name == 'lanes':

@@ -7,10 +7,10 @@ import json
 import numpy as np
 
 from conftest import env, oracle, pkg
-from refine_cases import same_bits  # noqa: F401  (the GPU tests compare with it)
+from refine_cases import RIG_FRAMES, same_bits  # noqa: F401  (the GPU tests compare with it)
 
 J = 18
-NAMES = ('c1', 'clean', 'noisy', 'messy', 'far', '5x10', 'arplab', 'explicit')
+NAMES = ('c1', 'clean', 'noisy', 'messy', 'far', '5x10', 'arplab', 'explicit', 'ring23', 'arprobot')
 _made = {}
 
 
@@ -55,7 +55,7 @@ def no_common_joint(frame):
 def raw(name):
     """-> (variant, frames in wire format, per frame {camera: person of every skeleton})."""
     syn = pkg('synthetic')
-    variant = 'arplab' if name == 'arplab' else 'panoptic'
+    variant = name if name in ('arplab', 'ring23', 'arprobot') else 'panoptic'
     calib = env(variant).calib
     cams = list(calib.params.camera_names)
     if name == 'c1':
@@ -78,6 +78,12 @@ def raw(name):
     elif name == '5x10':
         fr, gt = syn.make_frames(calib, 2, syn.FrameSpec(persons=10), seed=1234)
         made = list(zip(fr, gt))
+    elif name in RIG_FRAMES:
+        made = [syn.make_frame(calib, i, syn.FrameSpec(persons=3, noise_px=1.0), seed=1234) for i in RIG_FRAMES[name]]
+        if name == 'arprobot':
+            # two frames carry the two used streams only, the third all six (four of them without a slot)
+            used = list(calib.params.used_cameras_skeleton_matching)
+            made = [({c: v for c, v in fr.items() if c in used or i == 2}, gt) for i, (fr, gt) in enumerate(made)]
     else:
         fr, gt = syn.make_frames(calib, 4, syn.FrameSpec(persons=3, noise_px=1.0), seed=1234)
         made = list(zip(fr, gt))
@@ -131,6 +137,15 @@ class Case:
             assert pb.n_frames == 2 and pb.max_heads_per_frame() == 50
         if name == 'arplab':
             assert pb.V == 6 and pb.n_frames == 4 and w['n_votes'].max() > 0
+        if name == 'ring23':
+            # 69 heads a frame: 2277 edge-nodes, eight whole chunks of 256 and a partial one
+            M = np.diff(np.asarray(pb.frame_en_off))
+            assert pb.V == 23 and pb.max_heads_per_frame() == 69 and M.tolist() == [2277] * 3 and 2277 % 256 == 229
+            assert (w['n_votes'] == J).all()
+        if name == 'arprobot':
+            pairs = pkg('harness.geometric').batch_pairs(pb)
+            assert pb.V == 2 and [len(f) for f in self.frames] == [2, 2, 6] and np.diff(np.asarray(pb.frame_en_off)).tolist() == [9] * 3
+            assert (pb.head_cam[pairs[:, 0]] == 0).all() and (pb.head_cam[pairs[:, 1]] == 1).all() and (w['n_votes'] == J).all()   # one camera pair
         if name == 'explicit':
             assert w['n_votes'][-1] == 0 and w['scores'][-1] == 0.0 and same_bits(w['scores'][:10], w['scores'][10:20])
 

@@ -10,11 +10,11 @@ import json
 import numpy as np
 
 from conftest import env, oracle, pkg
-from refine_cases import behind_camera, same_bits  # noqa: F401  (the GPU tests compare with same_bits)
+from refine_cases import RIG_FRAMES, behind_camera, same_bits  # noqa: F401  (the GPU tests compare with same_bits)
 
 J = 18
-NAMES = ('clean', 'swap', 'orphan', 'stray', 'noisy', 'crowd', 'tie', 'degenerate', 'bad_rows', 'explicit', 'arplab')
-RESTORED = ('swap', 'orphan', 'noisy', 'crowd', 'arplab')
+NAMES = ('clean', 'swap', 'orphan', 'stray', 'noisy', 'crowd', 'tie', 'degenerate', 'bad_rows', 'explicit', 'arplab', 'ring23', 'arprobot')
+RESTORED = ('swap', 'orphan', 'noisy', 'crowd', 'arplab', 'ring23', 'arprobot')
 _made = {}
 
 
@@ -83,7 +83,7 @@ class Case:
     def __init__(self, name, pcap=None):
         syn, onp = pkg('synthetic'), oracle()
         self.name = name
-        self.variant = 'arplab' if name == 'arplab' else 'panoptic'
+        self.variant = name if name in ('arplab', 'ring23', 'arprobot') else 'panoptic'
         self.env = env(self.variant)
         calib, params = self.calib, self.params = self.env.calib, self.env.params
         cams = list(params.used_cameras_skeleton_matching)
@@ -94,8 +94,12 @@ class Case:
                 'noisy': (6, syn.FrameSpec(persons=4, noise_px=2.0, joint_drop=0.3), 1234), 'crowd': (2, syn.FrameSpec(persons=10, noise_px=1.0), 1234),
                 'tie': (1, syn.FrameSpec(persons=3, noise_px=1.0), 1234), 'degenerate': (6, syn.FrameSpec(persons=3, noise_px=1.0), 1234),
                 'bad_rows': (4, syn.FrameSpec(persons=4, noise_px=1.0), 1234), 'explicit': (1, syn.FrameSpec(persons=4, noise_px=1.0), 1234),
-                'arplab': (3, syn.FrameSpec(persons=3, noise_px=1.0), 1234)}[name]
-        frames, gts = syn.make_frames(calib, spec[0], spec[1], seed=spec[2])
+                'arplab': (3, syn.FrameSpec(persons=3, noise_px=1.0), 1234), 'ring23': (3, syn.FrameSpec(persons=3, noise_px=1.0), 1234),
+                'arprobot': (3, syn.FrameSpec(persons=3, noise_px=1.0), 1234)}[name]
+        if name in RIG_FRAMES:
+            frames, gts = zip(*[syn.make_frame(calib, i, spec[1], seed=spec[2]) for i in RIG_FRAMES[name]])
+        else:
+            frames, gts = syn.make_frames(calib, spec[0], spec[1], seed=spec[2])
         frames = [{c: list(v) for c, v in f.items()} for f in frames]
         owners = [{c: list(v) for c, v in g['owner'].items()} for g in gts]
         bodies = [np.asarray(g['persons'], np.float64) for g in gts]
@@ -116,6 +120,12 @@ class Case:
                 drop_skeleton(frames[f], owners[f], names[1], 4)
         if name == 'tie':
             duplicate_skeleton(frames[0], owners[0], names[1], 2)
+        if name == 'arprobot':
+            # two frames carry the two used streams only, the third all six; frame 0: body 2 has no row and body 1 is
+            # missing from the first camera
+            frames = [{c: v for c, v in fr.items() if c in cams or f == 2} for f, fr in enumerate(frames)]
+            n_rows[0] = 2
+            drop_skeleton(frames[0], owners[0], cams[0], 1)
         if name == 'degenerate':
             n_rows[0] = 0
             frames[1] = {names[2]: frames[1][names[2]]}
@@ -179,6 +189,24 @@ class Case:
                 swap(rows, f, both, 0, 1)
                 for p in range(n_rows[f]):
                     orphan(rows, f, p, [c for c in range(V) if c != both and rows[f, p, c] >= 0][0])
+        if name == 'ring23':
+            # the attach phase runs one wave per camera, cameras beyond the kernel's wave count taking turns (4 waves:
+            # RG_WAVES = RG_THREADS / 64 in csrc/regroup.hip, camera c += RG_WAVES): frame f orphans person 2 in cameras
+            # f + 1 and f + 5 (4 apart: one wave serves both -- were RG_THREADS to change, the pair would have to follow) and
+            # person f % 2 in camera 22, and swaps persons 0 and 1 in camera 18 + f
+            for f in range(F):
+                swap(rows, f, 18 + f, 0, 1)
+                orphan(rows, f, 2, f + 1)
+                orphan(rows, f, 2, f + 5)
+                orphan(rows, f, f % 2, 22)
+        if name == 'arprobot':
+            # frame 0: row 1 holds body 2's head in the first camera -- released, and nothing fits in its place, so the
+            # row is left with one view; frames 1 and 2: a swap
+            assert rows[0, 1, 0] == -1
+            h0, H, _, _ = pb.frame_counts(0)
+            rows[0, 1, 0] = [i for i in range(H) if pb.head_cam[h0 + i] == 0 and owners[0][cams[0]][int(pb.skeleton_index[h0 + i])] == 2][0]
+            for f in (1, 2):
+                swap(rows, f, f % V, 0, 1)
         if name == 'noisy':
             for f in range(F):
                 orphan(rows, f, 3, (f + 1) % V)
@@ -210,7 +238,7 @@ class Case:
             self.pflags[3, 0] = 0
             self.truth[4, 0, 3] = np.nan                                  # frame 4: a joint that is not a number
             self.truth[5, 1] = behind_camera(calib, 2).astype(np.float64)  # frame 5: a pose behind camera 2
-            T = np.asarray(calib.P, np.float64).reshape(V, 3, 4)
+            T = pkg('harness.reprojection').engine_calibration(calib)[0]
             self.behind = [bool(T[c, 2, :3] @ self.truth[5, 1, 0] + T[c, 2, 3] <= 0.0) for c in range(V)]
             for c in range(V):
                 if not self.behind[c]:
@@ -281,6 +309,16 @@ class Case:
             assert o['counts'][0].tolist()[:2] == [2, 3]
         if name == 'arplab':
             assert pb.V == 6 and (o['counts'][:, 0] == 2).all() and (o['counts'][:, 1] == 5).all()
+        if name == 'ring23':
+            assert pb.V == 23 and pb.max_heads_per_frame() == 69 and pb.max_heads_per_frame() * self.pcap > 256
+            assert (o['counts'][:, 0] == 2).all() and (o['counts'][:, 1] == 5).all() and not o['status'].any()
+            for f in range(pb.n_frames):
+                assert o['change'][f, 0, 18 + f] == 3 and o['change'][f, 2, f + 1] == 2 and o['change'][f, 2, f + 5] == 2
+                assert o['change'][f, f % 2, 22] == 2
+        if name == 'arprobot':
+            assert pb.V == 2 and [len(f) for f in self.frames] == [2, 2, 6] and not o['status'].any()
+            assert o['counts'][0].tolist() == [1, 0, 2, 1] and o['n_views'][0, 1] == 1        # one view left, under min_views
+            assert (o['counts'][1:, :2] == 2).all() and not o['counts'][1:, 2:].any()
 
 
 def case(name, pcap=None):

@@ -23,9 +23,10 @@ def mods():
 
 
 def base(name):
-    """refine_cases.Case(name) and its noise-free batch, built once"""
+    """refine_cases.Case(name) and its noise-free batch, built once (a rig case with the row capacity of its engine)"""
     if name not in _cache:
-        c = rc.Case(name)
+        kw = rc.ENGINE.get(name)
+        c = rc.Case(name, pcap=kw['max_heads_per_frame'] // env(rc.variant_of(name)).params.min_number_of_views if kw else None)
         _cache[name] = (c, rc.noise_free(c))
     return _cache[name]
 
@@ -40,21 +41,22 @@ def lengths_of(bodies, bones):
 class Seq:
     """What one call takes: the batch, the rows' heads, the pose rows, the frame map, and the state of the statement."""
 
-    def __init__(self, pb, persons, n_persons, poses, flags, ids, state, mode, frames=None, joint_mask=ALL, truth=None):
+    def __init__(self, pb, persons, n_persons, poses, flags, ids, state, mode, frames=None, joint_mask=ALL, truth=None, calib=None):
+        self.calib = env().calib if calib is None else calib
         self.pb, self.persons, self.n_persons, self.poses, self.flags, self.ids = pb, persons, n_persons, poses, flags, ids
         self.state, self.mode, self.frames, self.joint_mask, self.truth = state, mode, frames, joint_mask, truth
         self.pcap = poses.shape[1]
 
     def run(self, **kw):
         SR = pkg('harness.skeleton_refine')
-        return SR.refine_sequence(self.state, env().calib, self.pb, self.persons, self.n_persons, self.poses, self.flags, self.ids, self.mode,
+        return SR.refine_sequence(self.state, self.calib, self.pb, self.persons, self.n_persons, self.poses, self.flags, self.ids, self.mode,
                                   self.joint_mask, frames=self.frames, **kw)
 
     def cut(self, sl):
         """the pose frames of a slice, observed through a frame map into the whole batch"""
         frames = (np.arange(len(self.poses)) if self.frames is None else self.frames)[sl].astype(np.int32)
         return Seq(self.pb, self.persons[sl], self.n_persons[sl], self.poses[sl], self.flags[sl], self.ids[sl], self.state, self.mode, frames,
-                   self.joint_mask, None if self.truth is None else self.truth[sl])
+                   self.joint_mask, None if self.truth is None else self.truth[sl], self.calib)
 
 
 def known(name, mode, exact=False, start='near', bones=None):
@@ -71,7 +73,28 @@ def known(name, mode, exact=False, start='near', bones=None):
     ids = np.where(row, np.arange(F * pcap).reshape(F, pcap), -1).astype(np.int32)
     st = S.new_state(max(F * pcap, 1), bones, 0.002, J)
     S.set_lengths(st, lengths_of(c.truth, st['bones']).reshape(F * pcap, -1))
-    return Seq(clean if exact else c.pb, c.persons, c.n_persons, poses, flags, ids, st, mode, truth=c.truth)
+    return Seq(clean if exact else c.pb, c.persons, c.n_persons, poses, flags, ids, st, mode, truth=c.truth, calib=c.calib)
+
+
+def rig(name, mode):
+    """known(name, mode) of a rig case of refine_cases ('ring23', 'arprobot': three frames, every (frame, row) a track) and
+    what the statement must show on it -> (Seq, the numbers asserted)"""
+    _, SR = mods()
+    s = known(name, mode)
+    c = base(name)[0]
+    info = rc.check(c)
+    ref = s.run(sweeps=4)
+    nv, st = ref['n_views'], ref['status']
+    assert [nv[f, :3].max(axis=1).tolist() for f in range(len(nv))] == info['n_views']
+    info['rows'] = nv.shape[0] * nv.shape[1]
+    if name == 'ring23':
+        assert info['rows'] % 2 == 1                                             # two rows share a wave: the last row is alone
+        assert (st[2, 1] & SR.ONE_VIEW).all() and not (st[:, 2] & SR.ONE_VIEW).any() and (st[:, :3] & SR.FREE).all()
+    if name == 'arprobot':
+        assert (nv[:, :3] == 2).all() and not (st & SR.ONE_VIEW).any() and (st[:, :3] & SR.FREE).all()
+    assert (st & SR.MOVED).any() and (ref['n_bones'][:, :3] > 0).all()
+    info['status'] = sorted(set(st[:, :3].reshape(-1).tolist()))
+    return s, info
 
 
 def spoiled(name, mode):
@@ -92,7 +115,8 @@ def spoiled(name, mode):
 
 
 def camera_centre(c):
-    P = np.asarray(env().calib.P[c], np.float64).reshape(3, 4)
+    """the centre of the camera of slot c"""
+    P = pkg('harness.reprojection').engine_calibration(env().calib)[0][c]
     return -P[:, :3].T @ P[:, 3]
 
 

@@ -84,15 +84,16 @@ def assert_same_sums(got, want, what):
 
 CASES = [('panoptic', kind, huber, moved) for kind in ('est', 'triang') for huber in (0.0, 5.0) for moved in (False, True)]
 CASES.append(('arplab', 'triang', 5.0, True))
+CASES.append(('arprobot', 'triang', 5.0, True))              # six cameras configured, calibration indices 4 and 5 used
 
 
 @pytest.mark.parametrize('variant,kind,huber,moved', CASES)
 def test_sums_bit_equal_to_host_statement(variant, kind, huber, moved):
     """8: 3 frames of the rig x 2 persons -- a person missing a camera, a joint absent, a confidence below the threshold and
     one at it, Pcap above the persons, a person / joint flag off -- through mpe_calib_read, for both kinds of poses, both
-    Huber settings, the engine's own extrinsics and a moved set; ARPLAB has six cameras."""
-    s = setup(('small', variant), variant, lambda **kw: cc.small(variant, **kw))
-    assert s.scene.pb.V == (6 if variant == 'arplab' else 5) and s.eng.pcap > 2
+    Huber settings, the engine's own extrinsics and a moved set; ARPLAB has six cameras, ARPLAB_ROBOT uses two of the six."""
+    s = setup(('small', variant), variant, lambda **kw: cc.small(variant, **kw), ppc=3 if variant == 'arprobot' else 2)   # two cameras: Pcap = ppc
+    assert s.scene.pb.V == {'arplab': 6, 'arprobot': 2}.get(variant, 5) and s.eng.pcap > 2
     cal = s.calibrator(kind, huber_px=huber)
     E = CB().start_extrinsics(s.scene.calib)
     if moved:
@@ -105,7 +106,11 @@ def test_sums_bit_equal_to_host_statement(variant, kind, huber, moved):
     assert want['n_obs'].min() > 20 and len(set(want['n_obs'].tolist())) > 1
     acc, tri = cal.extrinsics()
     assert cc.same_bits(acc, E) and cc.same_bits(tri, E)
-    assert cc.same_bits(np.asarray(s.eng.calib.P, np.float64), CB().start_extrinsics(s.scene.calib))     # the engine's own: untouched
+    idx = CB().engine_cameras(s.scene.calib)
+    assert cc.same_bits(np.asarray(s.eng.calib.P, np.float64)[idx], CB().start_extrinsics(s.scene.calib))     # the engine's own: untouched
+    if variant == 'arprobot':                                # the accepted extrinsics go back to the rows of their own cameras
+        new, old = np.asarray(cal.calibration().P, np.float64), np.asarray(s.eng.calib.P, np.float64)
+        assert idx == [4, 5] and cc.same_bits(new[idx], E) and cc.same_bits(new[:4], old[:4]) and not cc.same_bits(new[idx], old[idx])
 
 
 def test_tiling_borders():

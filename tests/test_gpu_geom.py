@@ -131,6 +131,23 @@ def test_ray_table_route_gives_the_lds_bits():
         big.eng.close()
 
 
+def test_ring23_rig_capacity_takes_the_ray_table_route():
+    """The 23-camera rig at its own capacity of 230 heads a frame (230 x 18 x 24 B > 48 KiB): the ray table in context
+    workspace gives the bits of the LDS route of the small engine and of the statement, 2277 edge-nodes a frame."""
+    s = setup('ring23')
+    assert s.eng.hpf * gc.J * 24 <= 48 * 1024
+    big = Setup('ring23', max_frames=4, max_heads_per_frame=230)
+    try:
+        assert big.eng.hpf == 230 and big.eng.hpf * gc.J * 24 > 48 * 1024
+        for opts in gc.option_sets(s.case.params):
+            got = big.device(**opts)
+            assert_same(got, s.device(**opts), ('table against LDS', opts))
+            assert_same(got, s.case.statement(**opts), ('table against the statement', opts))
+        big.eng.sync_status()
+    finally:
+        big.eng.close()
+
+
 def test_frames_over_capacity_score_zero_and_are_reported():
     """Frames beyond max_heads_per_frame (the host check skipped): zeros, means -1, and the sticky status bit."""
     MpeError = pkg('lib').MpeError

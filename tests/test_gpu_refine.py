@@ -22,10 +22,11 @@ class Setup:
 
     def __init__(self, name):
         import torch
-        e = env()
+        e = env(rc.variant_of(name))
         case = rc.Case(name)
         most = max([1] + [f[c][0].count('{') for f in case.frames for c in f])
-        self.eng = eng = pkg('pipeline').Engine(e.params, e.calib, max_frames=max(16, len(case.frames)), max_persons_per_camera=max(4, most))
+        self.eng = eng = pkg('pipeline').Engine(e.params, e.calib, max_frames=max(16, len(case.frames)), max_persons_per_camera=max(4, most),
+                                                **rc.ENGINE.get(name, {}))
         self.case = case = rc.Case(name, pcap=eng.pcap)
         self.db = eng.to_device(eng.pack(case.processed))
         self.persons, self.n_persons = torch.from_numpy(case.persons).cuda(), torch.from_numpy(case.n_persons).cuda()
@@ -43,7 +44,7 @@ class Setup:
 
     def statement(self, kind, joint_mask=None, **kw):
         poses, flags, mask = self.host[kind]
-        return pkg('harness.refine').refine(env().calib, self.db.host, self.case.persons, self.case.n_persons, poses, flags,
+        return pkg('harness.refine').refine(self.case.calib, self.db.host, self.case.persons, self.case.n_persons, poses, flags,
                                             mask if joint_mask is None else joint_mask, **kw)
 
 
@@ -91,6 +92,15 @@ def test_bit_equal_to_host_statement(name, kind):
         assert (st & 2).any()
     if name == 'hand made':
         assert (st & 16).sum() == 16 and ((st & 8).any() or kind == 'triang') and (want['n_views'] == 2).any()
+    if name in rc.RIGS:
+        info = rc.check(s.case)
+        print(name, info)
+        nv = want['n_views'][..., 5]                                    # joint 5 is in both masks
+        assert s.eng.V == info['V'] and s.eng.pcap == s.case.pcap == info.get('pcap', s.eng.pcap)
+        rows = [0, 1, 2] if kind == 'est' else [0, 2]                   # a person in one camera has no triangulated joint
+        assert nv[-1, rows].tolist() == [info['n_views'][-1][p] for p in rows] and (st & 2).any()
+        if name == 'ring23' and kind == 'est':
+            assert (st[2, 1] & 8).any() and not (st[:, [0, 2]] & 8).any()   # FEW_VIEWS on the device: the person camera 22 alone sees
 
 
 @pytest.mark.parametrize('kind', ['triang', 'est'])

@@ -104,6 +104,50 @@ def test_reproject_bit_equal_to_host_statement():
             eng.close()
 
 
+@pytest.mark.parametrize('name', ['ring23', 'arprobot'])
+def test_reproject_and_stats_on_rig_cases(name):
+    """The rig cases of refine_cases (persons from the generator's pairing, no network): 23 cameras, of which 18..22 sit in
+    lanes that own no joint, with an odd Pcap; and the camera-subset rig, whose slots 0 and 1 are calibration indices 4
+    and 5.  Every entry of d_res for the four kinds of test_reproject_bit_equal_to_host_statement -- float32 poses with
+    person flags ('est', and 'gt' with its one-joint mask), binary64 poses with joint flags, a one-joint mask -- and the
+    per-camera statistics (V rows, every camera counted)."""
+    import torch
+
+    import refine_cases as rc
+    R = pkg('harness.reprojection')
+    case = rc.Case(name)
+    info = rc.check(case)
+    print(name, info)
+    e = case.env
+    eng = pkg('pipeline').Engine(e.params, e.calib, max_frames=16, max_persons_per_camera=4, **rc.ENGINE.get(name, {}))
+    try:
+        case = rc.Case(name, pcap=eng.pcap)
+        assert eng.V == info['V'] and eng.pcap == info.get('pcap', eng.pcap)
+        db = eng.to_device(eng.pack(case.processed))
+        persons, n_persons = torch.from_numpy(case.persons).cuda(), torch.from_numpy(case.n_persons).cuda()
+        J = eng.J
+        every = np.ones((len(case.frames), eng.pcap, J), np.uint8)
+        used_mask = sum(1 << j for j in e.params.used_joints)
+        runs = {'est': (case.est, case.est_flags, 'est', used_mask, None), 'triang': (case.truth, every, 'triang', (1 << J) - 1, None),
+                'gt': (case.est, case.est_flags, 'gt', 1 << (J - 1), None),
+                'joint 3': (case.truth, every, 'triang', 1 << 3, 1 << 3)}
+        for what, (poses, flags, kind, mask, arg) in runs.items():
+            g = eng.reproject(db, persons, n_persons, torch.from_numpy(poses).cuda(), torch.from_numpy(flags).cuda(), kind, joint_mask=arg)
+            want = R.residuals(e.calib, db.host, case.persons, case.n_persons, poses, flags, mask)
+            got = g.cpu().numpy()
+            print(name, what, 'entries', got.size, 'counted', int((got >= 0).sum()), 'differing', int((got != want).sum()))
+            assert got.shape == (len(case.frames), eng.pcap, eng.V, J) and same_bits(got, want), (name, what)
+            assert (got >= 0).sum() > 0 and np.all(got[~(got >= 0)] == R.SENTINEL)
+            if what == 'triang':
+                st, ref = eng.residual_stats(g), R.stats([want.reshape(-1, eng.V, J)])
+                assert len(st['count']) == eng.V and st['count'].tolist() == ref['count'].tolist() == info['count']
+                assert same_bits(st['mid'], ref['mid']) and same_bits(st['median'], ref['median'])
+                assert np.allclose(st['sum'], ref['sum'], rtol=1e-12, atol=0)
+        eng.sync_status()
+    finally:
+        eng.close()
+
+
 def stat_buffers(rng, V, J):
     """Residual-shaped buffers whose cameras hold the cases of the issue."""
     def buf(groups, fill):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import refine_cases as rc
 import skel_cases as sc
 import skel_refine_cases as k
 from conftest import GOLDEN, env, harness_model_files, pkg
@@ -97,6 +98,33 @@ def test_known_cases_and_a_random_sequence(eng, name, mode, weight, huber):
     if name == 'random':
         assert (s.ids >= s.state['tid_cap']).any() and (st & SR.MOVED).sum() > 500 and not st[..., 3].any()
         assert not np.isfinite(s.poses).all() and (ref['n_bones'] == 0).sum() > 20
+
+
+@pytest.mark.parametrize('huber', [0.0, 5.0])
+@pytest.mark.parametrize('weight', [0.0, 300.0, 1e4])
+@pytest.mark.parametrize('mode', ['mlp', 'tri'])
+@pytest.mark.parametrize('name', rc.RIGS)
+def test_rig_cases(name, mode, weight, huber):
+    """the 23-camera rig (cameras 18..22 in lanes that own no joint, a person seen by cameras 19 and 22 only, one by camera
+    22 only, an odd number of rows) and the camera-subset rig (calibration indices 4 and 5 in slots 0 and 1), under the
+    option sets of test_known_cases_and_a_random_sequence (every bone weight and Huber threshold at 1, 5 and 64 sweeps):
+    all six outputs bit for bit"""
+    s, info = k.rig(name, mode)
+    print(name, mode, info)
+    e = env(rc.variant_of(name))
+    en = pkg('pipeline').Engine(e.params, e.calib, max_frames=16, max_persons_per_camera=4, **rc.ENGINE.get(name, {}))
+    en.dbs = {}
+    try:
+        assert en.V == info['V'] and en.J == k.J
+        sk = skeleton(en, s)
+        try:
+            for sweeps in (1, 5, 64):
+                kw = dict(sweeps=sweeps, bone_weight=weight, huber_px=huber)
+                k.same(call(en, sk, s, **kw), s.run(**kw), (name, mode, kw))
+        finally:
+            sk.close()
+    finally:
+        en.close()
 
 
 def narrow(s, F, pcap):

@@ -187,3 +187,12 @@ def test_refine_symbol_in_header_and_binding():
     M = RF()
     assert (M.SOLVED, M.MOVED, M.CONVERGED, M.FEW_VIEWS, M.BAD_START, M.MAX_ITERS) == (1, 2, 4, 8, 16, L.MPE_REFINE_MAX_ITERS)
     assert int(re.search(r'#define MPE_REFINE_MAX_ITERS (\d+)', hdr).group(1)) == L.MPE_REFINE_MAX_ITERS
+
+
+@pytest.mark.parametrize('name', rc.RIGS)
+def test_rig_cases_take_their_branches(name):
+    """the 23-camera case (cameras in lanes that own no joint, a person in two of them, one in a single camera, an odd row
+    capacity) and the camera-subset case (two views, slots 0 and 1 = calibration indices 4 and 5) are what they are for"""
+    info = rc.check(rc.Case(name))
+    print(name, info)
+    assert info['V'] == {'ring23': 23, 'arprobot': 2}[name]

@@ -119,3 +119,13 @@ def test_frame_map_and_rows_that_are_not_fitted():
     k.same(k.Seq(s.pb, s.persons, s.n_persons, s.poses, s.flags, s.ids, s.state, 'tri',
                  np.arange(F, dtype=np.int32)).run(sweeps=3), s.run(sweeps=3), 'identity')
     assert ident['status'][5, 0, 0] == SR.BAD_FRAME
+
+
+@pytest.mark.parametrize('mode', ['mlp', 'tri'])
+@pytest.mark.parametrize('name', ['ring23', 'arprobot'])
+def test_rig_sequences_take_their_branches(name, mode):
+    """the tracked sequences on the 23-camera and the camera-subset rig: views per row, ONE_VIEW where a single camera
+    sees the person, an odd number of rows on the ring (asserted in skel_refine_cases.rig)"""
+    s, info = k.rig(name, mode)
+    print(name, mode, info)
+    assert info['rows'] == len(s.poses) * s.pcap

@@ -9,6 +9,7 @@
 
 #include "mpe_internal.h"
 #include "assign_int.h"
+#include "relink_config.h"
 
 using namespace mpe;
 
@@ -76,7 +77,7 @@ int dev_alloc(mpe_ctx *ctx, T **p, size_t count, bool zero = true) {
     return MPE_OK;
 }
 
-// ---- the state objects of the sequence stages (mpe_track_*, mpe_smooth_*, mpe_skel_*, mpe_track_score_*, mpe_calib_*) ----
+// ---- the state objects of the sequence stages (mpe_track_*, mpe_relink_*, mpe_smooth_*, mpe_skel_*, mpe_track_score_*, mpe_calib_*) ----
 
 // What every *_create does around its own part.  fill(st) gets the zeroed host struct: it checks the sizes first (a
 // refusal there comes before anything is allocated on the device), sets the fields and allocates.  When it fails,
@@ -117,7 +118,7 @@ int state_launches(mpe_ctx *ctx, const char *who, const S *st, int64_t *n) {
     return MPE_OK;
 }
 
-// What the batch calls on pose rows (track, smooth, skel observe and fit) check alike: the sizes and the pose type the
+// What the batch calls on pose rows (track, relink, smooth, skel observe and fit) check alike: the sizes and the pose type the
 // state was made for, the frame count and the flag mode -> MPE_OK with *run = false for a call without frames.
 template <typename S, typename A>
 int check_pose_rows(mpe_ctx *ctx, const char *who, const S *st, const A *a, bool *run) {
@@ -1653,6 +1654,90 @@ int mpe_body_refine_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const 
     if (a->d_poses_out == a->d_poses)
         return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: d_poses_out is d_poses (rows are copied through from the input)");
     HIPCHK(ctx, launch_skel_refine(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, st, *b, *a));
+    return MPE_OK;
+}
+
+int mpe_relink_destroy(mpe_ctx *ctx, mpe_relink_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_relink_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    dev_free(ctx, st->bones);
+    dev_free(ctx, st->canon);
+    dev_free(ctx, st->last_pose);
+    dev_free(ctx, st->last_mask);
+    dev_free(ctx, st->sum);
+    dev_free(ctx, st->cnt);
+    dev_free(ctx, st->ctr);
+    dev_free(ctx, st->row_len);
+    dev_free(ctx, st->row_act);
+    dev_free(ctx, st->row_id);
+    dev_free(ctx, st->table);
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_relink_create(mpe_ctx *ctx, const mpe_relink_config *cfg, mpe_relink_state **out) {
+    return create_state(ctx, "mpe_relink_create", out, mpe_relink_destroy, [&](mpe_relink_state *st) {
+        char why[400];
+        const int bad = relink_check_config(cfg, why, sizeof why);
+        if (bad) return fail(ctx, bad, "mpe_relink_create: %s", why);
+        st->cfg = relink_copy_config(*cfg, &st->bones_host);
+        st->pcap = cfg->pcap;
+        st->J = cfg->n_joints;
+        st->pose_f64 = cfg->pose_f64;
+        st->tid_cap = cfg->tid_cap;
+        st->n_bones = cfg->n_bones;
+        st->max_frames = cfg->max_frames;
+        const size_t cap = (size_t)cfg->tid_cap, nb = (size_t)cfg->n_bones, rows = (size_t)cfg->max_frames * cfg->pcap;
+        int rc = dev_alloc(ctx, &st->bones, nb * 2);
+        if (!rc) rc = dev_alloc(ctx, &st->canon, 3 * cap);
+        if (!rc) rc = dev_alloc(ctx, &st->last_pose, cap * cfg->n_joints * 3);
+        if (!rc) rc = dev_alloc(ctx, &st->last_mask, cap);
+        if (!rc) rc = dev_alloc(ctx, &st->sum, cap * nb);
+        if (!rc) rc = dev_alloc(ctx, &st->cnt, cap * nb);
+        if (!rc) rc = dev_alloc(ctx, &st->ctr, 4);
+        if (!rc) rc = dev_alloc(ctx, &st->row_len, rows * nb, false);
+        if (!rc) rc = dev_alloc(ctx, &st->row_act, rows, false);
+        if (!rc) rc = dev_alloc(ctx, &st->row_id, rows, false);
+        if (!rc) rc = dev_alloc(ctx, &st->table, (size_t)cfg->pcap * cap, false);
+        if (!rc && (hipMemcpy(st->bones, st->bones_host.data(), nb * 2 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemset(st->canon, 0xFF, 3 * cap * sizeof(int32_t)) != hipSuccess))       // -1: no id seen, no record, never present
+            rc = fail(ctx, MPE_ERR_HIP, "mpe_relink_create: hipMemcpy failed");
+        return rc;
+    });
+}
+
+int mpe_relink_reset(mpe_ctx *ctx, void *stream, mpe_relink_state *st) { return reset_state(ctx, "mpe_relink_reset", stream, st, launch_relink_reset); }
+
+int mpe_relink_launches(mpe_ctx *ctx, const mpe_relink_state *st, int64_t *n) { return state_launches(ctx, "mpe_relink_launches", st, n); }
+
+int mpe_relink_batch(mpe_ctx *ctx, void *stream, mpe_relink_state *st, const mpe_relink_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_relink_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    bool run;
+    const int rc = check_pose_rows(ctx, "mpe_relink_batch", st, a, &run);
+    if (rc || !run) return rc;
+    if (a->n_frames > st->max_frames)
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_relink_batch: %d frames, the state was made for %d per call", a->n_frames, st->max_frames);
+    if (st->frame + a->n_frames > 0x7FFFFFFFll) return fail(ctx, MPE_ERR_CAPACITY, "mpe_relink_batch: the sequence is over 2^31 - 1 frames");
+    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_ids || !a->d_link_cost || !a->d_link_gap)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_relink_batch: NULL argument");
+    HIPCHK(ctx, launch_relink(static_cast<hipStream_t>(stream), st, *a));
+    return MPE_OK;
+}
+
+int mpe_relink_read(mpe_ctx *ctx, void *stream, mpe_relink_state *st, int64_t *h_counters, int32_t *h_status) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_relink_read: NULL state");
+    DeviceGuard dg(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned long long ctr[4] = {0, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(ctr, st->ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (h_counters)
+        for (int i = 0; i < 3; ++i) h_counters[i] = (int64_t)ctr[i];
+    if (h_status) *h_status = (int32_t)ctr[3];
     return MPE_OK;
 }
 

@@ -237,6 +237,28 @@ struct mpe_skel_state {
     int n_colours = 0;              // colours of the joints: two joints of one colour share no bone
 };
 
+// relink.hip: what mpe_relink_batch carries from call to call (canon and one record per canonical id), the counters, and
+// the per-call scratch sized for max_frames frames at create time.  Nothing is double-buffered: one workgroup walks the
+// frames of a call in order.  `frame` lives on the host: every call knows how many frames the calls before it had.
+struct mpe_relink_state {
+    int pcap = 0, J = 0, pose_f64 = 0, tid_cap = 0, n_bones = 0, max_frames = 0;
+    mpe_relink_config cfg = {};     // the options as created; cfg.bones points at bones_host
+    std::vector<int32_t> bones_host;
+    int64_t frame = 0;              // frames seen since create / reset
+    int64_t launches = 0;           // kernels enqueued since mpe_relink_create
+    int32_t *bones = nullptr;       // [n_bones][2] (parent, child)
+    int32_t *canon = nullptr;       // [3][tid_cap]: canon, last_frame, seen (the last frame the record was present in)
+    double *last_pose = nullptr;    // [tid_cap][J][3]
+    uint32_t *last_mask = nullptr;  // [tid_cap]
+    double *sum = nullptr;          // [tid_cap][n_bones]
+    int32_t *cnt = nullptr;         // [tid_cap][n_bones]
+    unsigned long long *ctr = nullptr;   // births, linked, over_ids, status
+    double *row_len = nullptr;      // scratch [max_frames * pcap][n_bones]
+    uint32_t *row_act = nullptr;    // scratch [max_frames * pcap]
+    int32_t *row_id = nullptr;      // scratch [max_frames * pcap]
+    double *table = nullptr;        // scratch [pcap][tid_cap]
+};
+
 // calib.hip: what mpe_calib_batch accumulates and mpe_calib_step reads.  The Levenberg-Marquardt state of the cameras lives
 // on the host (api.hip, csrc/calib_solve.h).
 struct mpe_calib_host;
@@ -406,6 +428,9 @@ hipError_t launch_skel_reset(hipStream_t s, mpe_skel_state *st);
 hipError_t launch_skel_observe(hipStream_t s, mpe_skel_state *st, const mpe_skel_args &a);
 hipError_t launch_skel_update(hipStream_t s, mpe_skel_state *st, int min_samples);
 hipError_t launch_skel_fit(hipStream_t s, mpe_skel_state *st, const mpe_skel_args &a);
+// relink.hip
+hipError_t launch_relink_reset(hipStream_t s, mpe_relink_state *st);
+hipError_t launch_relink(hipStream_t s, mpe_relink_state *st, const mpe_relink_args &a);
 // skel_refine.hip
 int skel_refine_tables(const int32_t *bones, int n_bones, int J, std::vector<uint32_t> *tab);
 hipError_t launch_skel_refine(hipStream_t s, const DevCfg *cfg, int V, mpe_skel_state *st, const mpe_batch &b, const mpe_body_refine_args &a);

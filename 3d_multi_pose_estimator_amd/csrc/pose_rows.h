@@ -1,4 +1,4 @@
-// The pose rows the sequence stages read (track, smooth, eval, track_score), stated once: DESIGN.md 2.1.
+// The pose rows the sequence stages read (track, relink, smooth, eval, track_score), stated once: DESIGN.md 2.1.
 // Integer and predicate logic only.  What makes a row a detection differs from stage to stage and stays in the stage;
 // so does every line of arithmetic on the coordinates.  skel.hip keeps its own copy of these fields and tests: with
 // PoseRows in front of its kernel arguments k_skel_fit measured 1.9 % slower (profiles/pose_rows_timing.txt).

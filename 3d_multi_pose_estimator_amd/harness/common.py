@@ -104,6 +104,18 @@ def build_parser(description):
                    help='--bones-refine: pixels of reprojection error a metre of bone-length error is worth')
     p.add_argument('--bones-huber', type=float, default=0.0, metavar='PX', help='--bones-refine: Huber threshold of the pixel term, 0: plain least squares')
     p.add_argument('--bones-min', type=int, default=10, metavar='N', help='--bones: lengths a track needs of a bone before the bone is held to one')
+    p.add_argument('--relink', type=float, default=0.0, metavar='GATE_MM',
+                   help='implies --track; right after the tracker a re-identifier gives a track that is born the id of a track lost '
+                        'track-gap + 2 .. --relink-max-gap frames ago when their bone lengths agree within GATE_MM millimetres on average '
+                        '(mpe_relink_batch: causal, the state carried across --batch chunks); its ids, not the tracker\'s, go to --smooth, '
+                        '--bones, --bones-refine, --track-score and the Tracks line, and one further line reports the births, the links, the '
+                        'tracks before and after and the mean and largest link gap.  The gate and the other --relink values are options, not '
+                        'findings.')
+    p.add_argument('--relink-max-gap', type=int, default=150, metavar='N', help='--relink: most frames since the lost track was last seen')
+    p.add_argument('--relink-reach', type=float, default=0.0, metavar='M',
+                   help='--relink: a returning person is at most M metres (mean joint distance) from where the lost track was last seen; 0: anywhere')
+    p.add_argument('--relink-speed', type=float, default=0.0, metavar='M_PER_FRAME', help='--relink-reach grows by this per frame of gap')
+    p.add_argument('--relink-min-bones', type=int, default=8, metavar='N', help='--relink: fewest bones a birth and a lost track must have in common')
     p.add_argument('--bones-bin', type=float, default=2.0, metavar='MM', help='--bones: bin width of the length histograms, millimetres')
     p.add_argument('--refine', type=int, default=0, metavar='ITERS',
                    help='implies --device-metrics; every joint is moved to the minimum of its reprojection error over the cameras that saw it '
@@ -633,7 +645,16 @@ def run(args, mode):
                              and args.bones_huber >= 0):
         raise ValueError('--bones-refine takes 1 .. 64 sweeps, --bones-bin a width > 0, --bones-weight and --bones-huber no negative value '
                          '(got %d, %g, %g, %g)' % (bones_refine, args.bones_bin, args.bones_weight, args.bones_huber))
-    if smooth or track_score or bones or bones_refine:
+    relink = float(getattr(args, 'relink', 0.0) or 0.0)
+    if relink != 0.0:                                        # a NaN as well
+        relink_options = {'gate_m': relink / 1000.0, 'min_gap': args.track_gap + 2, 'max_gap': args.relink_max_gap, 'reach_m': args.relink_reach,
+                          'reach_per_frame_m': args.relink_speed, 'min_bones': args.relink_min_bones}
+        from . import relink as relink_rule
+        try:
+            relink_rule.check_options(relink_options, len(relink_rule.S.BONES_18))
+        except ValueError as e:
+            raise ValueError('--relink: %s' % e)
+    if smooth or track_score or bones or bones_refine or relink:
         args.track = True
     if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
         args.device_metrics = True
@@ -648,7 +669,7 @@ def run(args, mode):
     T_i1 = torch.from_numpy(calib.T_i32[1])
     J = eng.J
     t = {'match': 0.0, '3d': 0.0}
-    tracker = summary = smoother = smoothed = gt_tracker = scorer = skeleton = boned = None
+    tracker = summary = smoother = smoothed = gt_tracker = scorer = skeleton = boned = relinker = relinked = None
     last = {}                                                # what the track score of a batch needs from infer_device
     refined = []
     regrouped = []                                           # --regroup: per round, the counts of every batch
@@ -657,6 +678,18 @@ def run(args, mode):
     if getattr(args, 'track', False):
         from .tracking import TrackSummary
         tracker, summary = eng.tracker(mode, max_gap=args.track_gap, gate=args.track_gate), TrackSummary()
+    if relink:
+        relinker, relinked = eng.relinker(mode, **relink_options), relink_rule.RelinkSummary()
+
+    def track(p_in, f_in, n_in):
+        """the tracker, then with --relink the re-identifier: its ids take the place of the tracker's, and a birth it linked is
+        no birth (the gap of the link stands where the tracker wrote 0)"""
+        tr = tracker.update(p_in, f_in, n_in)
+        if relinker is not None:
+            rl = relinker.update(p_in, f_in, n_in, tr['ids'])
+            relinked.add(tr['ids'].cpu().numpy(), {k: rl[k].cpu().numpy() for k in ('ids', 'link_gap')})
+            tr = dict(tr, ids=rl['ids'], gap=torch.where(tr['gap'] == 0, rl['link_gap'], tr['gap']))
+        return tr
     if smooth:
         from .smoothing import SmoothSummary
         smoother, smoothed = eng.smoother(mode, window=smooth, decay=args.smooth_decay, fill=args.smooth_fill), SmoothSummary(mode)
@@ -740,7 +773,7 @@ def run(args, mode):
         if smoother is not None or skeleton is not None:
             # track, then smooth, then bones, then scoring: the fitted poses of the tracked frames take the place of the raw ones
             p_in, f_in, n_in = poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep)
-            tr = tracker.update(p_in, f_in, n_in)
+            tr = track(p_in, f_in, n_in)
             p_cur, f_cur = p_in, f_in
             if smoother is not None:
                 sm = smoother.update(p_in, f_in, n_in, tr['ids'])
@@ -772,7 +805,7 @@ def run(args, mode):
             if skeleton is not None:
                 boned.add(p_sk.cpu().numpy(), {k: v.cpu().numpy() for k, v in sk.items()})
         elif tracker is not None:
-            tr = tracker.update(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
+            tr = track(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
         if scorer is not None:
             last.update(flags=flags, n_persons=n_persons, ids=tr['ids'])
@@ -844,6 +877,10 @@ def run(args, mode):
         print('Tracks (gate %g m, gap %d): %d, mean length %.3f frames, %d born after the first frame'
               % (args.track_gate, args.track_gap, out['tracks']['tracks'], out['tracks']['mean_length'], out['tracks']['late_births']))
         tracker.close()
+    if relinker is not None:
+        out['relink'] = r = relinked.result(relinker.counters())
+        print(relink_rule.report_line(relink, args.relink_max_gap, r))
+        relinker.close()
     if smoother is not None:
         out['smooth'] = r = smoothed.result()
         print('Smoothed (window %d, decay %g%s): %d joints fitted, %d filled, mean displacement %.3f mm'

@@ -109,6 +109,20 @@ class mpe_skel_args(C.Structure):
                 ('d_poses_out', C.c_void_p), ('d_err', C.c_void_p), ('d_n_bones', C.c_void_p)]
 
 
+class mpe_relink_config(C.Structure):
+    _fields_ = [('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32), ('tid_cap', C.c_int32), ('n_bones', C.c_int32),
+                ('max_frames', C.c_int32), ('min_gap', C.c_int32), ('max_gap', C.c_int32), ('min_samples', C.c_int32), ('min_bones', C.c_int32),
+                ('used_joint_mask', C.c_uint32), ('joint_mask', C.c_uint32), ('gate_m', C.c_double), ('max_bone_m', C.c_double),
+                ('reach_m', C.c_double), ('reach_per_frame_m', C.c_double), ('bones', c_i32p)]
+
+
+class mpe_relink_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('reserved', C.c_int32),
+                ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p),
+                ('d_ids', C.c_void_p), ('d_link_cost', C.c_void_p), ('d_link_gap', C.c_void_p)]
+
+
 class mpe_body_refine_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
                 ('joint_flags', C.c_int32), ('sweeps', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float),
@@ -247,6 +261,9 @@ MPE_SMOOTH_MAX_WINDOW, MPE_SMOOTH_FILLED = 15, 2
 # the caps of mpe_skel_create / mpe_skel_fit_batch and the sticky status bit of mpe_skel_observe_batch
 MPE_SKEL_BINS, MPE_SKEL_MAX_BONES, MPE_SKEL_MAX_ITERS, MPE_SKEL_OVER_IDS, MPE_SKEL_MAX_HIST_BYTES = 512, 32, 64, 1, 256 << 20
 
+# the caps of mpe_relink_create and the sticky status bit of mpe_relink_batch
+MPE_RELINK_MAX_TID_CAP, MPE_RELINK_MAX_GAP, MPE_RELINK_OVER_IDS = 4096, 1 << 30, 1
+
 # per-joint status bits of mpe_body_refine_batch
 MPE_BODY_REFINE_FREE, MPE_BODY_REFINE_MOVED, MPE_BODY_REFINE_BAD_START, MPE_BODY_REFINE_ONE_VIEW, MPE_BODY_REFINE_BAD_FRAME = 1, 2, 4, 8, 16
 
@@ -337,6 +354,12 @@ SYMBOLS = {
     'mpe_skel_fit_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_skel_args)]),
     'mpe_skel_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'mpe_body_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_body_refine_args)]),
+    'mpe_relink_create': (C.c_int, [C.c_void_p, C.POINTER(mpe_relink_config), C.POINTER(C.c_void_p)]),
+    'mpe_relink_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_relink_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_relink_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_relink_args)]),
+    'mpe_relink_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_relink_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_track_score_create': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     'mpe_track_score_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_track_score_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1088,6 +1088,18 @@ class Engine:
         (default: the engine's Pcap)."""
         return Skeleton(self, mode, bones, bin_mm, tid_cap, self.pcap if pcap is None else int(pcap))
 
+    def relinker(self, mode, bones=None, tid_cap=256, pcap=None, max_frames=None, **options):
+        """A Relinker for one tracked sequence of poses in `mode` ('mlp' or 'tri', as Engine.skeleton takes it): a track
+        that is born takes the id of a track lost min_gap .. max_gap frames ago when their bone lengths agree within
+        gate_m and, with reach_m > 0, the position is plausible (mpe_relink_batch).  It goes right after Tracker.update;
+        its ids, not the tracker's, then go to the smoother, the skeleton, the body fit and the scorer.  bones as
+        Engine.skeleton takes them; tid_cap: ids that have a record, 1 .. 4096; pcap: rows per frame when the poses are not
+        this engine's; max_frames: frames per update (default: the engine's).  options: harness.relink.DEFAULTS names them
+        (gate_m, min_gap, max_gap, min_samples, min_bones, max_bone_m, reach_m, reach_per_frame_m, used_joint_mask --
+        default: the parameters' used joints --, joint_mask); the defaults are options, not findings."""
+        return Relinker(self, mode, bones, tid_cap, self.pcap if pcap is None else int(pcap),
+                        self.max_frames if max_frames is None else int(max_frames), options)
+
     def _pose_args(self, db, persons, n_persons, poses, flags, kind, joint_mask, kinds):
         """The argument checks reproject and refine share -> (B, tri, joint_mask)."""
         B = db.n_frames
@@ -1796,6 +1808,68 @@ class Skeleton(_DeviceState):
         table = table.to(self.eng.device).contiguous()
         self.eng._chk(self.eng.lib.mpe_skel_set_lengths(self.eng.ctx, self.eng._stream(), self.state, table.data_ptr()))
         table.record_stream(torch.cuda.current_stream(self.eng.device))
+
+class Relinker(_DeviceState):
+    """Engine.relinker's object: the device state of one sequence (the canonical id of every tracker id seen, and per
+    canonical id the frame and pose it was last seen in and the sums and counts of its bone lengths).  update() takes the
+    frames of the sequence in order, in chunks of any size, with the ids Tracker.update gave them; the result does not
+    depend on the chunking.  Everything stays on the device and on the current stream: update() neither synchronises nor
+    reads anything back; counters() does both.  reset(): a new sequence."""
+    _prefix, _noun = 'mpe_relink', 'relinker'
+
+    def __init__(self, eng, mode, bones, tid_cap, pcap, max_frames, options):
+        from .harness import relink as R, skeleton as S
+        if mode not in ('mlp', 'tri'):
+            raise ValueError('mode must be mlp or tri')
+        if bones is None:
+            if eng.J != 18:
+                raise ValueError('bones must be given for %d joints (the default list is for 18)' % eng.J)
+            bones = S.BONES_18
+        self.bones = S.check_bones(bones, eng.J)
+        options = dict(options)
+        options.setdefault('used_joint_mask', sum(1 << j for j in eng.params.used_joints))
+        self.options = o = R.check_options(dict(options, tid_cap=tid_cap), len(self.bones))
+        if int(max_frames) < 1:
+            raise ValueError('max_frames must be at least 1')
+        self.mode, self.tid_cap, self.pcap, self.max_frames = mode, o['tid_cap'], int(pcap), int(max_frames)
+        flat = np.ascontiguousarray(self.bones, np.int32)
+        cfg = L.mpe_relink_config()
+        cfg.pcap, cfg.n_joints, cfg.pose_f64, cfg.tid_cap, cfg.n_bones = self.pcap, eng.J, int(mode == 'tri'), self.tid_cap, len(self.bones)
+        cfg.max_frames = self.max_frames
+        cfg.min_gap, cfg.max_gap, cfg.min_samples, cfg.min_bones = o['min_gap'], o['max_gap'], o['min_samples'], o['min_bones']
+        cfg.used_joint_mask, cfg.joint_mask = o['used_joint_mask'], o['joint_mask']
+        cfg.gate_m, cfg.max_bone_m, cfg.reach_m, cfg.reach_per_frame_m = o['gate_m'], o['max_bone_m'], o['reach_m'], o['reach_per_frame_m']
+        cfg.bones = flat.ctypes.data_as(L.c_i32p)
+        self._create(eng, C.byref(cfg))
+
+    def update(self, poses, flags, n_persons, ids):
+        """poses / flags / n_persons of the next B >= 0 frames as Tracker.update took them, and the 'ids' it returned.
+        -> {'ids' [B,Pcap] i32 (the canonical id; -1: no detection), 'link_cost' [B,Pcap] f64 (the bone-length cost of
+        a link in metres; -1.0 for a row that is no linked birth), 'link_gap' [B,Pcap] i32 (frames since the record was
+        last seen for a linked birth; 0 any other detection, -1 none)}, device tensors."""
+        eng, tri = self.eng, self.mode == 'tri'
+        self._open()
+        B = _check_pose_rows(eng.J, self.pcap, tri, tri, poses, flags, n_persons, ids, device=eng.device)
+        if B > self.max_frames:
+            raise ValueError('%d frames, the relinker was made for %d per update' % (B, self.max_frames))
+        dev = eng.device
+        out = {'ids': torch.empty((B, self.pcap), dtype=torch.int32, device=dev),
+               'link_cost': torch.empty((B, self.pcap), dtype=torch.float64, device=dev),
+               'link_gap': torch.empty((B, self.pcap), dtype=torch.int32, device=dev)}
+        a = L.mpe_relink_args()
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, self.pcap, eng.J, int(tri), int(tri)
+        a.d_poses, a.d_flags, a.d_n_persons, a.d_track_id = poses.data_ptr(), flags.data_ptr(), n_persons.data_ptr(), ids.data_ptr()
+        a.d_ids, a.d_link_cost, a.d_link_gap = (out[k].data_ptr() for k in ('ids', 'link_cost', 'link_gap'))
+        eng._chk(eng.lib.mpe_relink_batch(eng.ctx, eng._stream(), self.state, C.byref(a)))
+        return out
+
+    def counters(self):
+        """The counters as they stand (synchronises) -> {'births' (tracks that began as themselves), 'linked' (births that
+        took a lost track's id), 'over_ids' (rows whose id has no record), 'status' (MPE_RELINK_OVER_IDS)}."""
+        ctr, status = (C.c_int64 * 3)(), C.c_int32()
+        self.eng._chk(self.eng.lib.mpe_relink_read(self.eng.ctx, self.eng._stream(), self.state, C.addressof(ctr), C.addressof(status)))
+        return {'births': int(ctr[0]), 'linked': int(ctr[1]), 'over_ids': int(ctr[2]), 'status': int(status.value)}
+
 
 class TrackScore(_DeviceState):
     """Engine.track_scorer's object: the device state of one recording (the totals, the per-identity carry, the

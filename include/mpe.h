@@ -1417,6 +1417,93 @@ typedef struct {
 } mpe_body_refine_args;
 int mpe_body_refine_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *state, const mpe_batch *b, const mpe_body_refine_args *a);
 
+/* Relink: a person who returns after a long gap gets the identity they had.  mpe_track_batch links a detection only a few
+ * frames back and only within its gate; whoever walks behind a pillar or leaves the volume comes back under a new id.  This
+ * stage sits between the tracker and everything that reads its ids: a newborn track takes the id of a lost track with the
+ * same bone lengths and, optionally, a plausible position.  It is causal (an id handed out is never revised), needs no
+ * weights, and a sequence fed in any chunking gets the same result.  The rule (harness/relink.py states it in numpy, and
+ * the two agree bit for bit):
+ *   State, fixed at create time (mpe_relink_config): the sizes, the bone list as mpe_skel_create takes it, and the options.
+ *   It holds frame (the frames seen), canon i32 [tid_cap] (-1 until the id has been seen) and one record per canonical id:
+ *   last_frame (-1: none), last_pose f64 [J][3] with its active-joint mask, sum f64 and cnt i32 [n_bones]; the int64
+ *   counters births, linked and over_ids and the sticky status word.
+ *   Detections, presence, ACTIVE joints, LIVE bones and the length of a bone exactly as mpe_skel_observe_batch defines them
+ *   (joint_mask cuts the joints that count at all).  A length is ACCEPTED when the bone is live, l > 0 and l <= max_bone_m.
+ *   Per frame, in order; f counts over the whole sequence and an empty frame counts too:
+ *   1. a detection with t >= tid_cap keeps its id, adds 1 to over_ids and sets MPE_RELINK_OVER_IDS; it takes no further part.
+ *   2. a detection with canon[t] >= 0 is KNOWN and its record canon[t] is PRESENT in this frame; every other detection is a
+ *      BIRTH.  A later row that repeats an id gets the same output id and touches nothing.
+ *   3. rows = the births in row order; columns = the records c in increasing c with last_frame >= 0, not present, and
+ *      min_gap <= g <= max_gap for g = f - last_frame.
+ *   4. cost of (row, column) over the bones in list order: a bone counts when the birth has an accepted length l of it and
+ *      the record cnt >= min_samples; m = sum / (double)cnt ; v = |l - m| ; cost = (the left fold of v from 0.0) /
+ *      (double)(the count of such bones), +inf with fewer than min_bones of them.
+ *   5. position gate, when reach_m > 0: d = the pair cost of mpe_track_batch between the birth's pose and last_pose over
+ *      the joints active in both and inside used_joint_mask; the pair is kept only when d < reach_m + reach_per_frame_m *
+ *      (double)g, product and sum rounded on their own; a pair with no common joint is not kept.
+ *   6. a pair is linkable when cost < gate_m (strict; a NaN never links).
+ *   7. greedy, as in mpe_track_batch: the linkable pair of least cost, ties to the lowest row, then the lowest column, is
+ *      linked and both are removed, until none is left.
+ *   8. a linked birth t -> c: canon[t] = c, d_link_cost and d_link_gap = g for that row, linked += 1.
+ *   9. an unlinked birth: canon[t] = t, births += 1.
+ *   10. every detection with t < tid_cap, taking the first row of each canonical id, updates its record: per accepted bone
+ *      sum = sum + l and cnt += 1; last_pose and its mask = this row's active joints; last_frame = f.
+ *   d_ids[f][p] = canon[t]; -1 where the input has no detection; t itself for t >= tid_cap.  d_link_cost[f][p] = -1.0
+ *   unless the row is a linked birth.  d_link_gap[f][p] = the gap of a linked birth, 0 for any other detection, -1 for none.
+ *   A canonical id is a tracker id and never larger than the id it replaces.  Nothing is contracted; sqrt and / are IEEE.
+ * mpe_relink_create allocates all device memory the calls need, scratch for max_frames frames per call included
+ * (MPE_ERR_CAPACITY for pcap > MPE_TRACK_MAX_PERSONS, tid_cap > MPE_RELINK_MAX_TID_CAP or max_frames > 2^23;
+ * MPE_ERR_INVALID, with the values in mpe_last_error, for a bone list mpe_skel_create would decline, an option that is
+ * not finite, gate_m or max_bone_m not > 0, a negative reach, min_gap < 1, max_gap < min_gap or > MPE_RELINK_MAX_GAP,
+ * min_samples < 1, min_bones outside 1 .. n_bones); no later call allocates.  mpe_relink_reset starts a new sequence,
+ * ordered on `stream`.  mpe_relink_batch is TWO kernels whatever n_frames is and whatever the frames hold
+ * (mpe_relink_launches counts them as mpe_track_launches does), ordered on `stream`; it neither synchronises nor
+ * allocates; n_frames == 0 does nothing.  MPE_ERR_INVALID: sizes or a pose type other than the state's, joint_flags
+ * outside {0, 1}, a NULL pointer; MPE_ERR_CAPACITY: n_frames > max_frames, or a sequence of 2^31 frames or more.
+ * mpe_relink_read is the only call that synchronises (`stream`): {births, linked, over_ids} and the status to host memory
+ * (either may be NULL).  Calls on one state belong on one stream. */
+#define MPE_RELINK_MAX_TID_CAP 4096
+#define MPE_RELINK_MAX_GAP (1 << 30)
+#define MPE_RELINK_OVER_IDS 1
+typedef struct mpe_relink_state mpe_relink_state;
+typedef struct {
+    int32_t pcap, n_joints;
+    int32_t pose_f64;              /* 0: f32 poses; 1: f64 */
+    int32_t tid_cap;               /* track ids 0 .. tid_cap - 1 have a record, 1 .. MPE_RELINK_MAX_TID_CAP */
+    int32_t n_bones;
+    int32_t max_frames;            /* frames per mpe_relink_batch, at most */
+    int32_t min_gap, max_gap;      /* frames since the lost track was last seen, both ends included */
+    int32_t min_samples;           /* a record's bone counts only with this many lengths */
+    int32_t min_bones;             /* fewest bones a birth and a record must have in common */
+    uint32_t used_joint_mask;      /* joints the position gate looks at */
+    uint32_t joint_mask;           /* joints that count at all */
+    double gate_m;                 /* a link needs a bone-length cost strictly below this, metres */
+    double max_bone_m;             /* longest length that is accepted */
+    double reach_m;                /* 0: no position gate */
+    double reach_per_frame_m;      /* growth of the position gate per frame of gap */
+    const int32_t *bones;          /* host, [n_bones][2] (parent, child); copied */
+} mpe_relink_config;
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    int32_t reserved;
+    const void *d_poses;
+    const uint8_t *d_flags;
+    const int32_t *d_n_persons;    /* [n_frames] */
+    const int32_t *d_track_id;     /* [n_frames][pcap], mpe_track_batch's */
+    int32_t *d_ids;                /* [n_frames][pcap] */
+    double *d_link_cost;           /* [n_frames][pcap] */
+    int32_t *d_link_gap;           /* [n_frames][pcap] */
+} mpe_relink_args;
+int mpe_relink_create(mpe_ctx *ctx, const mpe_relink_config *cfg, mpe_relink_state **out);
+int mpe_relink_reset(mpe_ctx *ctx, void *stream, mpe_relink_state *state);
+int mpe_relink_destroy(mpe_ctx *ctx, mpe_relink_state *state);
+int mpe_relink_batch(mpe_ctx *ctx, void *stream, mpe_relink_state *state, const mpe_relink_args *a);
+int mpe_relink_launches(mpe_ctx *ctx, const mpe_relink_state *state, int64_t *n);
+/* h_counters [3] = births, linked, over_ids; synchronises `stream`. */
+int mpe_relink_read(mpe_ctx *ctx, void *stream, mpe_relink_state *state, int64_t *h_counters, int32_t *h_status);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

@@ -177,6 +177,30 @@ int check_batch(mpe_ctx *ctx, const mpe_batch *b) {
     return MPE_OK;
 }
 
+// What the geometry calls on a batch's person rows (reproject, refine, regroup, consolidate, calib, body refine) check alike,
+// after check_batch: the frames of the batch, the joints of the context, pcap and the two modes -> MPE_OK with *run = false
+// for a call without frames.  takes_d_frame: the entry point has a d_frame list, and with one given (d_frame) the rows
+// name their frames and need not be as many as the batch has.
+template <typename A>
+int check_batch_rows(mpe_ctx *ctx, const char *who, const mpe_batch *b, const A *a, bool *run, bool takes_d_frame = false,
+                     const int32_t *d_frame = nullptr) {
+    *run = false;
+    if (!d_frame && a->n_frames != b->n_frames)
+        return fail(ctx, MPE_ERR_INVALID, "%s: n_frames %d%s, the batch has %d frames", who, a->n_frames, takes_d_frame ? " without d_frame" : "",
+                    b->n_frames);
+    if (a->n_joints != ctx->cfg.n_joints)
+        return fail(ctx, MPE_ERR_INVALID, "%s: %d joints, the context has %d", who, a->n_joints, ctx->cfg.n_joints);
+    if (a->pcap < 1) return fail(ctx, MPE_ERR_INVALID, "%s: pcap %d must be at least 1", who, a->pcap);
+    if ((a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "%s: pose_f64 %d and joint_flags %d must be 0 or 1", who, a->pose_f64, a->joint_flags);
+    *run = a->n_frames > 0;
+    return MPE_OK;
+}
+
+// the four arrays every one of them reads, tested where a call with frames has passed its value checks
+template <typename A>
+bool row_inputs_missing(const A *a) { return !a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags; }
+
 struct GemmProf {
     mpe_ctx *ctx;
     hipStream_t s;
@@ -1638,18 +1662,16 @@ int mpe_body_refine_batch(mpe_ctx *ctx, void *stream, mpe_skel_state *st, const 
     bool run;
     rc = check_pose_rows(ctx, "mpe_body_refine_batch", st, a, &run);
     if (rc) return rc;
-    if (a->n_joints != ctx->cfg.n_joints)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: %d joints, the context has %d", a->n_joints, ctx->cfg.n_joints);
+    bool rows_run;
+    rc = check_batch_rows(ctx, "mpe_body_refine_batch", b, a, &rows_run, true, a->d_frame);
+    if (rc) return rc;
     if (a->sweeps < 1 || a->sweeps > MPE_SKEL_MAX_ITERS)
         return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: sweeps %d; 1 .. %d", a->sweeps, MPE_SKEL_MAX_ITERS);
     if (!(a->bone_weight >= 0.0) || !(a->huber_px >= 0.0) || !(a->threshold >= 0.0f))
         return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: bone_weight %g, huber_px %g and threshold %g must not be negative", a->bone_weight,
                     a->huber_px, (double)a->threshold);
-    if (!a->d_frame && a->n_frames != b->n_frames)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: n_frames %d without d_frame, the batch has %d", a->n_frames, b->n_frames);
-    if (!run) return MPE_OK;
-    if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_track_id || !a->d_persons || !a->d_poses_out || !a->d_status || !a->d_n_views ||
-        !a->d_cost || !a->d_err || !a->d_n_bones)
+    if (!run || !rows_run) return MPE_OK;
+    if (row_inputs_missing(a) || !a->d_track_id || !a->d_poses_out || !a->d_status || !a->d_n_views || !a->d_cost || !a->d_err || !a->d_n_bones)
         return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: NULL argument");
     if (a->d_poses_out == a->d_poses)
         return fail(ctx, MPE_ERR_INVALID, "mpe_body_refine_batch: d_poses_out is d_poses (rows are copied through from the input)");
@@ -1876,11 +1898,10 @@ int mpe_reproject_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mp
     if (rc) return rc;
     if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_reproject_batch: NULL argument");
     DeviceGuard dg(ctx);
-    if (a->n_frames != b->n_frames || a->pcap < 1 || a->n_joints != ctx->cfg.n_joints || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_reproject_batch: bad sizes or modes");
-    if (b->n_frames == 0) return MPE_OK;
-    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags || !a->d_res)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_reproject_batch: NULL argument");
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_reproject_batch", b, a, &run);
+    if (rc || !run) return rc;
+    if (row_inputs_missing(a) || !a->d_res) return fail(ctx, MPE_ERR_INVALID, "mpe_reproject_batch: NULL argument");
     HIPCHK(ctx, launch_reproject(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
     return MPE_OK;
 }
@@ -1890,16 +1911,15 @@ int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_r
     if (rc) return rc;
     if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: NULL argument");
     DeviceGuard dg(ctx);
-    if (a->n_frames != b->n_frames || a->pcap < 1 || a->n_joints != ctx->cfg.n_joints || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: bad sizes or modes (%d frames, the batch has %d; %d joints, the context has %d)",
-                    a->n_frames, b->n_frames, a->n_joints, ctx->cfg.n_joints);
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_refine_batch", b, a, &run);
+    if (rc) return rc;
     if (a->max_iters < 1 || a->max_iters > MPE_REFINE_MAX_ITERS)
         return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: max_iters %d outside 1..%d", a->max_iters, MPE_REFINE_MAX_ITERS);
     if (!(a->step_tol >= 0.0) || !(a->huber_px >= 0.0))
         return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: step_tol %g and huber_px %g must not be negative", a->step_tol, a->huber_px);
-    if (b->n_frames == 0) return MPE_OK;
-    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags || !a->d_poses_out || !a->d_status || !a->d_cost0 || !a->d_cost1 ||
-        !a->d_iters || !a->d_n_views)
+    if (!run) return MPE_OK;
+    if (row_inputs_missing(a) || !a->d_poses_out || !a->d_status || !a->d_cost0 || !a->d_cost1 || !a->d_iters || !a->d_n_views)
         return fail(ctx, MPE_ERR_INVALID, "mpe_refine_batch: NULL argument");
     HIPCHK(ctx, launch_refine(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
     return MPE_OK;
@@ -1910,12 +1930,9 @@ int mpe_regroup_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_
     if (rc) return rc;
     if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: NULL argument");
     DeviceGuard dg(ctx);
-    if (a->n_frames != b->n_frames || a->n_joints != ctx->cfg.n_joints)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: %d frames, the batch has %d; %d joints, the context has %d", a->n_frames,
-                    b->n_frames, a->n_joints, ctx->cfg.n_joints);
-    if (a->pcap < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: pcap %d must be at least 1", a->pcap);
-    if ((a->pose_f64 & ~1) || (a->joint_flags & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: pose_f64 %d and joint_flags %d must be 0 or 1", a->pose_f64, a->joint_flags);
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_regroup_batch", b, a, &run);
+    if (rc) return rc;
     if (a->pcap > MPE_REGROUP_MAX_PERSONS)
         return fail(ctx, MPE_ERR_CAPACITY, "mpe_regroup_batch: pcap %d over %d", a->pcap, MPE_REGROUP_MAX_PERSONS);
     if (!(a->gate_px > 0.0) || !(a->clip_px >= 0.0))
@@ -1925,9 +1942,8 @@ int mpe_regroup_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_
         return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: min_joints %d outside 1..%d", a->min_joints, ctx->cfg.n_joints);
     if (a->flags == 0 || (a->flags & ~(uint32_t)(MPE_REGROUP_RELEASE | MPE_REGROUP_ATTACH)))
         return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: flags %u must be MPE_REGROUP_RELEASE, MPE_REGROUP_ATTACH or both", a->flags);
-    if (b->n_frames == 0) return MPE_OK;
-    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: NULL argument");
+    if (!run) return MPE_OK;
+    if (row_inputs_missing(a)) return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: NULL argument");
     // d_cost is [n_heads][pcap]: a batch without heads has no table to point at, and no frame of it touches one
     if (!a->d_persons_out || !a->d_change || !a->d_n_views || (!a->d_cost && b->n_heads > 0) || !a->d_counts || !a->d_status)
         return fail(ctx, MPE_ERR_INVALID, "mpe_regroup_batch: NULL output");
@@ -1942,12 +1958,9 @@ int mpe_consolidate_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const 
     if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: NULL argument");
     DeviceGuard dg(ctx);
     const int J = ctx->cfg.n_joints;
-    if (a->n_frames != b->n_frames || a->n_joints != J)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: %d frames, the batch has %d; %d joints, the context has %d", a->n_frames,
-                    b->n_frames, a->n_joints, J);
-    if (a->pcap < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: pcap %d must be at least 1", a->pcap);
-    if ((a->pose_f64 & ~1) || (a->joint_flags & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: pose_f64 %d and joint_flags %d must be 0 or 1", a->pose_f64, a->joint_flags);
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_consolidate_batch", b, a, &run);
+    if (rc) return rc;
     if (a->pcap > MPE_REGROUP_MAX_PERSONS)
         return fail(ctx, MPE_ERR_CAPACITY, "mpe_consolidate_batch: pcap %d over %d", a->pcap, MPE_REGROUP_MAX_PERSONS);
     if (!(a->merge_m > 0.0) || !(a->found_m > 0.0) || !(a->clip_m >= 0.0))
@@ -1961,9 +1974,8 @@ int mpe_consolidate_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const 
         return fail(ctx, MPE_ERR_CAPACITY, "mpe_consolidate_batch: fcap %d with %d joints over %d ray doubles", a->fcap, J, MPE_CONSOLIDATE_RAY_DOUBLES);
     if (a->flags == 0 || (a->flags & ~(uint32_t)(MPE_CONSOLIDATE_MERGE | MPE_CONSOLIDATE_FOUND)))
         return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: flags %u must be MPE_CONSOLIDATE_MERGE, MPE_CONSOLIDATE_FOUND or both", a->flags);
-    if (b->n_frames == 0) return MPE_OK;
-    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: NULL argument");
+    if (!run) return MPE_OK;
+    if (row_inputs_missing(a)) return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: NULL argument");
     if (!a->d_persons_out || !a->d_n_persons_out || !a->d_change || !a->d_n_views || !a->d_dist || !a->d_pair || !a->d_free || !a->d_counts ||
         !a->d_status)
         return fail(ctx, MPE_ERR_INVALID, "mpe_consolidate_batch: NULL output");
@@ -2265,14 +2277,14 @@ int mpe_calib_batch(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_b
     if (rc) return rc;
     if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: NULL argument");
     DeviceGuard dg(ctx);
-    if (a->n_frames != b->n_frames || a->pcap < 1 || a->n_joints != ctx->cfg.n_joints || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
-        return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: bad sizes or modes (%d frames, the batch has %d; %d joints, the context has %d)",
-                    a->n_frames, b->n_frames, a->n_joints, ctx->cfg.n_joints);
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_calib_batch", b, a, &run);
+    if (rc) return rc;
     if (!(a->huber_px >= 0.0)) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: huber_px %g must not be negative", a->huber_px);
     if (st->V != ctx->cfg.n_cameras || b->n_frames > st->max_frames)
         return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: the state belongs to another context");
-    if (b->n_frames == 0) return MPE_OK;
-    if (!a->d_persons || !a->d_n_persons || !a->d_poses || !a->d_flags) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: NULL argument");
+    if (!run) return MPE_OK;
+    if (row_inputs_missing(a)) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: NULL argument");
     HIPCHK(ctx, launch_calib(static_cast<hipStream_t>(stream), ctx->d_cfg, st->V, st, *b, *a));
     return MPE_OK;
 }

@@ -14,6 +14,7 @@
 // Two launches whatever the frame count.  The file turns contraction off; f64 quotients and roots are the language's
 // correctly rounded ones.
 #include "mpe_internal.h"
+#include "project64.h"
 #include "reproject_select.h"
 
 #pragma clang fp contract(off)
@@ -44,8 +45,6 @@ struct CalibK {
     unsigned long long *n_obs, *n_skipped;    // [V]
 };
 
-__device__ inline bool finite1(double a) { return fabs(a) < __builtin_huge_val(); }
-
 // the record of (frame f, row p, joint j, camera c) -> REC_*
 __device__ inline uint8_t observe(const DevCfg *cfg, const CalibK &a, int f, int p, int j, int c, double *rec) {
     const long long fp = (long long)f * a.pcap + p;
@@ -53,56 +52,35 @@ __device__ inline uint8_t observe(const DevCfg *cfg, const CalibK &a, int f, int
     uint32_t present = 0;
     const int head = sel_head(a.sel, f, fp, c, &present);
     if (!sel_joint(a.sel, fp, j, head, present)) return REC_ABSENT;
-    const size_t at = ((size_t)fp * a.J + j) * 3;
-    double X0, X1, X2;
-    if (a.pose_f64) {
-        const double *q = static_cast<const double *>(a.poses) + at;
-        X0 = q[0], X1 = q[1], X2 = q[2];
-    } else {
-        const float *q = static_cast<const float *>(a.poses) + at;
-        X0 = (double)q[0], X1 = (double)q[1], X2 = (double)q[2];
-    }
-    if (!(finite1(X0) && finite1(X1) && finite1(X2))) return REC_SKIPPED;
-    const double *T = a.E + 12 * c;
-    double pc[3];
-    for (int i = 0; i < 3; ++i) pc[i] = ((T[4 * i] * X0 + T[4 * i + 1] * X1) + T[4 * i + 2] * X2) + T[4 * i + 3];
-    if (!(pc[2] > 0.0)) return REC_SKIPPED;
-    const double kd0 = cfg->dist[c][0], kd1 = cfg->dist[c][1], kd2 = cfg->dist[c][4];
+    double X[3], pc[3];
+    load3(a.poses, a.pose_f64, (size_t)fp * a.J + j, X);
+    if (!finite3(X[0], X[1], X[2])) return REC_SKIPPED;
+    to_camera(a.E + 12 * c, X[0], X[1], X[2], pc);
+    if (!(pc[2] > 0.0)) return REC_SKIPPED;   // before the quotients: a skipped record computes nothing
     const float *K = cfg->K[c];
-    const double h0 = pc[0] / pc[2], h1 = pc[1] / pc[2];
-    const double r = h0 * h0 + h1 * h1;
-    const double fr = ((1.0 + kd0 * r) + (kd1 * r) * r) + ((kd2 * r) * r) * r;
-    const double d0 = h0 * fr, d1 = h1 * fr;
-    double u[3];
-    for (int i = 0; i < 3; ++i) u[i] = ((double)K[3 * i] * d0 + (double)K[3 * i + 1] * d1) + (double)K[3 * i + 2];
-    const double px = u[0] / u[2], py = u[1] / u[2];
-    if (!(finite1(px) && finite1(py))) return REC_SKIPPED;
+    const Proj pr = project_pc(pc, cfg->dist[c], K);
+    if (!finite3(pr.px, pr.py, 0.0)) return REC_SKIPPED;
     const double *o = a.xy + ((size_t)head * a.J + j) * 2;
-    const double rx = px - o[0], ry = py - o[1];
+    const double rx = pr.px - o[0], ry = pr.py - o[1];
     const double e = sqrt(rx * rx + ry * ry);
-    const double fd = (kd0 + (2.0 * kd1) * r) + ((3.0 * kd2) * r) * r;
-    const double da[3] = {1.0 / pc[2], 0.0, (-h0) / pc[2]}, db[3] = {0.0, 1.0 / pc[2], (-h1) / pc[2]};
+    // the derivatives of (h0, h1) by the camera-frame point, through the shared tail; then the six-vector of a rigid
+    // perturbation (w, tau) of the camera: d pc = w x pc + tau
+    const double fd = radial_slope(cfg->dist[c], pr);
+    const double da[3] = {1.0 / pc[2], 0.0, (-pr.h0) / pc[2]}, db[3] = {0.0, 1.0 / pc[2], (-pr.h1) / pc[2]};
     double cx[3], cy[3];
-    for (int k = 0; k < 3; ++k) {
-        const double qk = fd * (2.0 * (h0 * da[k] + h1 * db[k]));
-        const double mk = da[k] * fr + h0 * qk, nk = db[k] * fr + h1 * qk;
-        const double v0 = (double)K[0] * mk + (double)K[1] * nk, v1 = (double)K[3] * mk + (double)K[4] * nk;
-        const double v2 = (double)K[6] * mk + (double)K[7] * nk;
-        cx[k] = (v0 - px * v2) / u[2];
-        cy[k] = (v1 - py * v2) / u[2];
-    }
+    for (int k = 0; k < 3; ++k) jacobian_tail(pr, K, fd, da[k], db[k], cx + k, cy + k);
     rec[0] = cx[2] * pc[1] - cx[1] * pc[2];
     rec[1] = cx[0] * pc[2] - cx[2] * pc[0];
     rec[2] = cx[1] * pc[0] - cx[0] * pc[1];
     rec[3] = cx[0], rec[4] = cx[1], rec[5] = cx[2];
     rec[6] = rx;
-    rec[7] = (a.huber <= 0.0 || e <= a.huber) ? 1.0 : a.huber / e;
+    rec[7] = huber_weight(e, a.huber);
     rec[8] = cy[2] * pc[1] - cy[1] * pc[2];
     rec[9] = cy[0] * pc[2] - cy[2] * pc[0];
     rec[10] = cy[1] * pc[0] - cy[0] * pc[1];
     rec[11] = cy[0], rec[12] = cy[1], rec[13] = cy[2];
     rec[14] = ry;
-    rec[15] = (a.huber <= 0.0 || e <= a.huber) ? e * e : (2.0 * a.huber) * e - a.huber * a.huber;
+    rec[15] = rho(e, a.huber);
     return REC_SUMMED;
 }
 

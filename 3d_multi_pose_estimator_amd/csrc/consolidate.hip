@@ -11,6 +11,7 @@
 // head.  Every lane reaches every workgroup barrier.  Every count is an integer.
 #include "mpe_internal.h"
 #include "project64.h"
+#include "frame_rows.h"
 #include "rays64.h"
 
 #pragma clang fp contract(off)
@@ -20,11 +21,10 @@ namespace mpe {
 namespace {
 
 constexpr int CS_THREADS = 256;
-constexpr int CS_NAMED_WORDS = 1024;          // one bit per head of a frame: max_heads_per_frame <= 32767 (mpe_create)
 constexpr int CS_NONE = 0x7fffffff;
 static_assert(MPE_CONSOLIDATE_MAX_FREE == 64, "the free heads of a frame are the lanes of a wave and the bits of a word");
-static_assert(MPE_REGROUP_MAX_PERSONS * MPE_MAX_CAMERAS * 4 + CS_NAMED_WORDS * 4 + MPE_REGROUP_MAX_PERSONS * 6 +
-                      MPE_CONSOLIDATE_RAY_DOUBLES * 8 + MPE_CONSOLIDATE_MAX_FREE * 12 + MPE_MAX_CAMERAS * 24 + 64 <= 64 * 1024,
+static_assert(FRAME_ROWS_LDS + MPE_REGROUP_MAX_PERSONS * 5 + MPE_CONSOLIDATE_RAY_DOUBLES * 8 + MPE_CONSOLIDATE_MAX_FREE * 12 +
+                      MPE_MAX_CAMERAS * 24 + 64 <= 64 * 1024,
               "the rows, the named bits, the pose flags and the rays of the free heads of a frame fit LDS");
 
 struct ConsolidateK {
@@ -50,13 +50,7 @@ struct ConsolidateK {
 __device__ inline bool joint_of(const ConsolidateK &a, size_t fp, int j, double *X) {
     const size_t pj = fp * a.J + j;
     if (a.joint_flags && a.pflags[pj] == 0) return false;
-    if (a.pose_f64) {
-        const double *q = static_cast<const double *>(a.poses) + pj * 3;
-        X[0] = q[0], X[1] = q[1], X[2] = q[2];
-    } else {
-        const float *q = static_cast<const float *>(a.poses) + pj * 3;
-        X[0] = (double)q[0], X[1] = (double)q[1], X[2] = (double)q[2];
-    }
+    load3(a.poses, a.pose_f64, pj, X);
     return finite3(X[0], X[1], X[2]);
 }
 
@@ -88,7 +82,7 @@ __device__ inline bool before(double c1, int a1, int b1, double c0, int a0, int 
 
 __global__ void __launch_bounds__(CS_THREADS) k_consolidate(const DevCfg *__restrict__ cfg, ConsolidateK a) {
     __shared__ int32_t s_row[MPE_REGROUP_MAX_PERSONS * MPE_MAX_CAMERAS];      // [pcap][V], as the rows stand now
-    __shared__ uint32_t s_named[CS_NAMED_WORDS];                             // bit h: a row names head h
+    __shared__ uint32_t s_named[NAMED_WORDS];                                // bit h: a row names head h
     __shared__ uint32_t s_cams[MPE_REGROUP_MAX_PERSONS];                     // bit c: row p holds a head of camera c now
     __shared__ uint8_t s_pose[MPE_REGROUP_MAX_PERSONS];                      // person p has a pose
     __shared__ uint8_t s_gone[MPE_REGROUP_MAX_PERSONS];                      // row p was merged away
@@ -99,36 +93,22 @@ __global__ void __launch_bounds__(CS_THREADS) k_consolidate(const DevCfg *__rest
     __shared__ int32_t s_res[6];                                             // merged, founded, placed, K, rows now, rows full
     __shared__ int32_t s_bad;
     const int f = blockIdx.x, tid = threadIdx.x, V = a.V, pcap = a.pcap, J = a.J, fcap = a.fcap;
-    const int h0 = a.frame_head_off[f], H = a.frame_head_off[f + 1] - h0;
-    const int np_raw = a.n_persons[f];
-    const int np = np_raw < 0 ? 0 : np_raw > pcap ? pcap : np_raw;
-    const bool over = H > a.hmax;
-    const size_t fp0 = (size_t)f * pcap;
+    // the rows of the frame (frame_rows.h).  The Selection is put together here from the flat argument fields: as a member of
+    // ConsolidateK it cost this kernel 20 more spilled scalar registers and 6 % at 5x4
+    const Selection sel{V, J, a.joint_flags, a.joint_mask, a.threshold, a.frame_head_off, a.head_joint_mask, a.vp, a.persons, a.n_persons, a.pflags};
+    const FrameRows fr = frame_rows_load<CS_THREADS>(sel, pcap, a.hmax, f, s_row, s_pose, s_named, &s_bad);
+    const int h0 = fr.h0, H = fr.H, np_raw = fr.np_raw, np = fr.np;
+    const bool over = fr.over;
+    const size_t fp0 = fr.fp0;
     const int entries = pcap * V;
-
-    for (int i = tid; i < entries; i += CS_THREADS) s_row[i] = a.persons[fp0 * V + i];
-    for (int p = tid; p < pcap; p += CS_THREADS) {
-        s_pose[p] = p < np && (a.joint_flags || a.pflags[fp0 + p] != 0);
-        s_gone[p] = 0;
-    }
-    if (!over)
-        for (int w = tid; w < (H + 31) / 32; w += CS_THREADS) s_named[w] = 0;
+    for (int p = tid; p < pcap; p += CS_THREADS) s_gone[p] = 0;
     if (tid < 6) s_res[tid] = tid == 4 ? np : 0;
-    if (tid == 0) s_bad = 0;
     if (tid < V) camera_centre(cfg, tid, s_o[tid]);
     __syncthreads();
 
-    // the rows checked, every named head marked
-    if (!over)
-        for (int i = tid; i < np * V; i += CS_THREADS) {
-            const int e = s_row[i], c = i % V;
-            if (e < 0) continue;
-            bool bad = e >= H || a.head_cam[h0 + e] != c;
-            if (!bad) bad = ((atomicOr(&s_named[e >> 5], 1u << (e & 31)) >> (e & 31)) & 1u) != 0;
-            if (bad) s_bad = 1;
-        }
+    frame_rows_mark<CS_THREADS>(fr, V, a.head_cam, s_row, s_named, &s_bad);
     __syncthreads();
-    const bool copy = over || s_bad != 0;
+    const bool copy = frame_rows_copy(fr, &s_bad);
 
     // the pose distances; the camera set of every row
     for (int i = tid; i < pcap * pcap; i += CS_THREADS) {

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "project64.h"                // Bits<T> and finite3, the one definition of each (every including file has contraction off)
+
 namespace mpe {
 
 struct PoseRows {
@@ -33,17 +35,5 @@ __device__ inline uint32_t flag_mask(const PoseRows &r, size_t fp) {
 
 // joint j of row fp when the row is a detection: a per-row flag stands for every joint
 __device__ inline bool joint_flag(const PoseRows &r, size_t fp, int j) { return !r.joint_flags || r.flags[fp * r.J + j] != 0; }
-
-// the unsigned integer as wide as T: coordinates that are copied through keep their bits (a NaN its payload)
-template <typename T>
-struct Bits;
-template <>
-struct Bits<float> { typedef uint32_t type; };
-template <>
-struct Bits<double> { typedef uint64_t type; };
-
-__device__ inline bool finite3(double x, double y, double z) {
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
 
 }  // namespace mpe

@@ -11,6 +11,7 @@
 // head, person); no barrier inside the rounds (the waves run different numbers of them).  Every count is an integer.
 #include "mpe_internal.h"
 #include "project64.h"
+#include "frame_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -20,22 +21,16 @@ namespace {
 
 constexpr int RG_THREADS = 256;
 constexpr int RG_WAVES = RG_THREADS / 64;
-constexpr int RG_NAMED_WORDS = 1024;          // one bit per head of a frame: max_heads_per_frame <= 32767 (mpe_create)
-static_assert(MPE_REGROUP_MAX_PERSONS * MPE_MAX_CAMERAS * 4 + RG_NAMED_WORDS * 4 + MPE_REGROUP_MAX_PERSONS + 32 <= 64 * 1024,
-              "the rows, the named bits and the pose flags of a frame fit LDS");
+static_assert(FRAME_ROWS_LDS + 32 <= 64 * 1024, "the rows, the named bits and the pose flags of a frame fit LDS");
 
 struct RegroupK {
-    int pcap, V, J, pose_f64, joint_flags, min_joints, min_views, hmax;
-    uint32_t joint_mask, flags;
-    float threshold;
+    int pcap, pose_f64, min_joints, min_views, hmax;
+    uint32_t flags;
     double gate, clip;
-    const int32_t *frame_head_off, *head_cam;
-    const uint32_t *head_joint_mask;
-    const float *vp;
+    Selection sel;                            // the batch's heads and the rows with their flags (reproject_select.h)
+    const int32_t *head_cam;
     const double *xy;
-    const int32_t *persons, *n_persons;
     const void *poses;
-    const uint8_t *pflags;
     int32_t *persons_out;                     // may be `persons`: an entry is read and written by the same lane
     uint8_t *change;
     int32_t *n_views;
@@ -46,26 +41,22 @@ struct RegroupK {
 // the cost of head h (index into the batch's per-head arrays) against person p of frame f, -1 when unscored
 __device__ inline double pair_cost(const DevCfg *cfg, const RegroupK &a, size_t fp, int h) {
     const double inf = __builtin_huge_val();
+    const Selection &s = a.sel;
     const int c = a.head_cam[h];
-    if (c < 0 || c >= a.V) return -1.0;
-    const uint32_t present = a.head_joint_mask[h] & a.joint_mask;
+    if (c < 0 || c >= s.V) return -1.0;
+    const uint32_t present = s.head_joint_mask[h] & s.joint_mask;
     double sum = 0.0;
     int n = 0;
-    for (int j = 0; j < a.J; ++j) {
+    for (int j = 0; j < s.J; ++j) {
         if (!((present >> j) & 1u)) continue;
-        const size_t hj = (size_t)h * a.J + j, pj = fp * a.J + j;
-        if (!(a.vp[hj * 2] > a.threshold)) continue;
-        if (a.joint_flags && a.pflags[pj] == 0) continue;
-        double X0, X1, X2;
-        if (a.pose_f64) {
-            const double *q = static_cast<const double *>(a.poses) + pj * 3;
-            X0 = q[0], X1 = q[1], X2 = q[2];
-        } else {
-            const float *q = static_cast<const float *>(a.poses) + pj * 3;
-            X0 = (double)q[0], X1 = (double)q[1], X2 = (double)q[2];
-        }
+        const size_t hj = (size_t)h * s.J + j, pj = fp * s.J + j;
+        if (!(s.vp[hj * 2] > s.threshold)) continue;
+        if (s.joint_flags && s.flags[pj] == 0) continue;
+        double X[3];
+        load3(a.poses, a.pose_f64, pj, X);
+        const double X0 = X[0], X1 = X[1], X2 = X[2];
         if (!finite3(X0, X1, X2)) continue;
-        const Proj p = project(cfg, c, X0, X1, X2);
+        const Proj p = project(cfg->P[c], cfg->dist[c], cfg->K[c], X0, X1, X2);
         if (!(p.pc2 > 0.0)) continue;
         const double rx = p.px - a.xy[hj * 2], ry = p.py - a.xy[hj * 2 + 1];
         double e = sqrt(rx * rx + ry * ry);
@@ -86,24 +77,17 @@ __device__ inline bool before(double c1, int h1, int p1, double c0, int h0, int 
 
 __global__ void __launch_bounds__(RG_THREADS) k_regroup(const DevCfg *__restrict__ cfg, RegroupK a) {
     __shared__ int32_t s_row[MPE_REGROUP_MAX_PERSONS * MPE_MAX_CAMERAS];      // [pcap][V], as the rows stand now
-    __shared__ uint32_t s_named[RG_NAMED_WORDS];                             // bit h: a row names head h now
+    __shared__ uint32_t s_named[NAMED_WORDS];                                // bit h: a row names head h now
     __shared__ uint8_t s_pose[MPE_REGROUP_MAX_PERSONS];                      // person p has a pose
     __shared__ int32_t s_cnt[4];
     __shared__ int32_t s_bad;
-    const int f = blockIdx.x, tid = threadIdx.x, V = a.V, pcap = a.pcap;
-    const int h0 = a.frame_head_off[f], H = a.frame_head_off[f + 1] - h0;
-    int np = a.n_persons[f];
-    np = np < 0 ? 0 : np > pcap ? pcap : np;
-    const bool over = H > a.hmax;
-    const size_t fp0 = (size_t)f * pcap;
+    const int f = blockIdx.x, tid = threadIdx.x, V = a.sel.V, pcap = a.pcap;
+    const FrameRows fr = frame_rows_load<RG_THREADS>(a.sel, pcap, a.hmax, f, s_row, s_pose, s_named, &s_bad);
+    const int h0 = fr.h0, H = fr.H, np = fr.np;
+    const bool over = fr.over;
+    const size_t fp0 = fr.fp0;
     const int entries = pcap * V;
-
-    for (int i = tid; i < entries; i += RG_THREADS) s_row[i] = a.persons[fp0 * V + i];
-    for (int p = tid; p < pcap; p += RG_THREADS) s_pose[p] = p < np && (a.joint_flags || a.pflags[fp0 + p] != 0);
-    if (!over)
-        for (int w = tid; w < (H + 31) / 32; w += RG_THREADS) s_named[w] = 0;
     if (tid < 4) s_cnt[tid] = 0;
-    if (tid == 0) s_bad = 0;
     __syncthreads();
 
     // the cost table: every head of the frame against every row
@@ -113,17 +97,9 @@ __global__ void __launch_bounds__(RG_THREADS) k_regroup(const DevCfg *__restrict
         a.cost[(size_t)(h0 + hh) * pcap + p] = s_pose[p] ? pair_cost(cfg, a, fp0 + p, h0 + hh) : -1.0;
     }
 
-    // the rows checked, every named head marked
-    if (!over)
-        for (int i = tid; i < np * V; i += RG_THREADS) {
-            const int e = s_row[i], c = i % V;
-            if (e < 0) continue;
-            bool bad = e >= H || a.head_cam[h0 + e] != c;
-            if (!bad) bad = ((atomicOr(&s_named[e >> 5], 1u << (e & 31)) >> (e & 31)) & 1u) != 0;
-            if (bad) s_bad = 1;
-        }
+    frame_rows_mark<RG_THREADS>(fr, V, a.head_cam, s_row, s_named, &s_bad);
     __syncthreads();                          // also: this workgroup's d_cost stores are visible to it from here on
-    const bool copy = over || s_bad != 0;
+    const bool copy = frame_rows_copy(fr, &s_bad);
 
     if (!copy && (a.flags & MPE_REGROUP_RELEASE)) {
         for (int i = tid; i < np * V; i += RG_THREADS) {
@@ -170,7 +146,7 @@ __global__ void __launch_bounds__(RG_THREADS) k_regroup(const DevCfg *__restrict
     __syncthreads();
 
     for (int i = tid; i < entries; i += RG_THREADS) {
-        const int was = a.persons[fp0 * V + i], now = s_row[i];
+        const int was = a.sel.persons[fp0 * V + i], now = s_row[i];
         int code = 0;
         if (now != was) code = (was >= 0 ? 1 : 0) | (now >= 0 ? 2 : 0);
         a.persons_out[fp0 * V + i] = now;
@@ -200,9 +176,10 @@ __global__ void __launch_bounds__(RG_THREADS) k_regroup(const DevCfg *__restrict
 
 hipError_t launch_regroup(hipStream_t s, const DevCfg *cfg, int V, int min_views, int hmax, int32_t *sticky, const mpe_batch &b,
                           const mpe_regroup_args &x) {
-    RegroupK a{x.pcap, V, x.n_joints, x.pose_f64, x.joint_flags, x.min_joints, min_views, hmax, x.joint_mask, x.flags, x.threshold,
-               x.gate_px, x.clip_px, b.d_frame_head_off, b.d_head_cam, b.d_joint_mask, b.d_vp, b.d_xy, x.d_persons, x.d_n_persons,
-               x.d_poses, x.d_flags, x.d_persons_out, x.d_change, x.d_n_views, x.d_cost, x.d_counts, x.d_status, sticky};
+    RegroupK a{x.pcap, x.pose_f64, x.min_joints, min_views, hmax, x.flags, x.gate_px, x.clip_px,
+               Selection{V, x.n_joints, x.joint_flags, x.joint_mask, x.threshold, b.d_frame_head_off, b.d_joint_mask, b.d_vp, x.d_persons,
+                         x.d_n_persons, x.d_flags},
+               b.d_head_cam, b.d_xy, x.d_poses, x.d_persons_out, x.d_change, x.d_n_views, x.d_cost, x.d_counts, x.d_status, sticky};
     hipLaunchKernelGGL(k_regroup, dim3((unsigned)x.n_frames), dim3(RG_THREADS), 0, s, cfg, a);
     return hipGetLastError();
 }

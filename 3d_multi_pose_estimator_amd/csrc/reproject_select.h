@@ -1,6 +1,7 @@
 // Which (frame, person, camera, joint) entries mpe_reproject_batch counts (include/mpe.h has the rule), in three steps so
 // that a kernel can read the per-person and per-camera words once and keep the per-joint test for the lane that owns the
-// joint.  reproject.hip (one half wave per (frame, person, camera)) and refine.hip (one per (frame, person)) share it.
+// joint.  reproject.hip (one half wave per (frame, person, camera)), refine.hip (one per (frame, person)), skel_refine.hip
+// and calib.hip select by it; regroup.hip and frame_rows.h carry its fields.
 #pragma once
 #include "mpe_internal.h"
 

@@ -28,14 +28,13 @@ constexpr int SRW = 32, SRR = 64 / SRW;      // lanes per row and rows per workg
 static_assert(MPE_MAX_CAMERAS <= SRW && MPE_MAX_JOINTS <= SRW && MPE_SKEL_MAX_BONES <= SRW, "a row's 32 lanes hold its cameras, joints and bones");
 
 struct SkelRefineK {
-    int n_frames, pcap, V, J, n_bones, joint_flags, tid_cap, sweeps, n_colours, batch_frames;
+    int n_frames, pcap, V, J, n_bones, tid_cap, sweeps, n_colours, batch_frames;
     uint32_t jmask;
     double kappa, huber;
-    Selection sel;                            // which cameras observe a joint (reproject_select.h)
+    Selection sel;                            // which cameras observe a joint (reproject_select.h); the rows' flags and n_persons
     const double *xy;
     const void *poses;
-    const uint8_t *flags;
-    const int32_t *n_persons, *tid, *frame;
+    const int32_t *tid, *frame;
     void *poses_out;
     uint8_t *status, *n_views, *n_bones_out;
     double *cost, *err;
@@ -44,24 +43,13 @@ struct SkelRefineK {
     const uint32_t *tab;                      // skel_refine_tables
 };
 
-template <typename T>
-struct PoseBits;
-template <>
-struct PoseBits<float> { typedef uint32_t type; };
-template <>
-struct PoseBits<double> { typedef uint64_t type; };
-
-__device__ inline double rho(double e, double huber) {
-    return (huber <= 0.0 || e <= huber) ? e * e : (2.0 * huber) * e - huber * huber;
-}
-
 // the camera fold of the local cost at X; *front: pc_2 > 0 in every observing camera
 __device__ inline double pixel_cost(const DevCfg *cfg, const SkelRefineK &a, const int *heads, int j, uint32_t obs, double X0, double X1, double X2,
                                     bool *front) {
     double C = 0.0;
     for (int c = 0; c < a.V; ++c) {
         if (!((obs >> c) & 1u)) continue;
-        const Proj p = project(cfg, c, X0, X1, X2);
+        const Proj p = project(cfg->P[c], cfg->dist[c], cfg->K[c], X0, X1, X2);
         if (!(p.pc2 > 0.0)) *front = false;
         const double *o = a.xy + ((size_t)heads[c] * a.J + j) * 2;
         const double rx = p.px - o[0], ry = p.py - o[1];
@@ -85,7 +73,7 @@ __global__ void __launch_bounds__(64) k_skel_refine(const DevCfg *__restrict__ c
     __shared__ double s_fold[SRR][SRW];       // a value per lane for the folds lane 0 of the row takes in order
     __shared__ int s_head[SRR][SRW];          // camera c's head for the row
     __shared__ uint32_t s_present[SRR][SRW];  // and the joints of that head that are asked for
-    typedef typename PoseBits<T>::type B;
+    typedef typename Bits<T>::type B;
     const int g = threadIdx.x / SRW, j = threadIdx.x % SRW, J = a.J, nb = a.n_bones;
     const size_t row = (size_t)blockIdx.x * SRR + g;
     const bool valid = row < (size_t)a.n_frames * a.pcap;     // every lane stays to the end: ballots and barriers
@@ -99,9 +87,9 @@ __global__ void __launch_bounds__(64) k_skel_refine(const DevCfg *__restrict__ c
     const int bf = a.frame ? a.frame[f] : f;
     const bool bad_frame = bf < 0 || bf >= a.batch_frames;
     int32_t t = -1;
-    if (valid && !bad_frame && p < min(max(a.n_persons[f], 0), a.pcap)) {
+    if (valid && !bad_frame && p < min(max(a.sel.n_persons[f], 0), a.pcap)) {
         t = a.tid[fp];
-        if (!a.joint_flags && !a.flags[fp]) t = -1;
+        if (!a.sel.joint_flags && !a.sel.flags[fp]) t = -1;
     }
     const bool known = t >= 0 && t < a.tid_cap;
 
@@ -113,7 +101,7 @@ __global__ void __launch_bounds__(64) k_skel_refine(const DevCfg *__restrict__ c
         const B *q = reinterpret_cast<const B *>(in) + 3 * j;
         in_bits[0] = q[0], in_bits[1] = q[1], in_bits[2] = q[2];
         X0 = (double)in[3 * j], X1 = (double)in[3 * j + 1], X2 = (double)in[3 * j + 2];
-        active = known && ((a.jmask >> j) & 1u) && (!a.joint_flags || a.flags[fp * J + j] != 0) && finite3(X0, X1, X2);
+        active = known && ((a.jmask >> j) & 1u) && (!a.sel.joint_flags || a.sel.flags[fp * J + j] != 0) && finite3(X0, X1, X2);
     }
     x[3 * j] = X0, x[3 * j + 1] = X1, x[3 * j + 2] = X2;
     const uint32_t act = (uint32_t)(__ballot(active) >> (SRW * g));
@@ -208,38 +196,18 @@ __global__ void __launch_bounds__(64) k_skel_refine(const DevCfg *__restrict__ c
             bool accept = false;
             double Y0 = X0, Y1 = X1, Y2 = X2;
             if (free_j && colour == col) {
-                double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0, C = 0.0;
+                Normal3 N;
+                double C = 0.0;
                 for (int c = 0; c < a.V; ++c) {
                     if (!((obs >> c) & 1u)) continue;
-                    const Proj pr = project(cfg, c, X0, X1, X2);
+                    const Proj pr = project(cfg->P[c], cfg->dist[c], cfg->K[c], X0, X1, X2);
                     const double *o = a.xy + ((size_t)heads[c] * J + j) * 2;
                     const double rx = pr.px - o[0], ry = pr.py - o[1];
                     const double e = sqrt(rx * rx + ry * ry);
-                    const double w = (a.huber <= 0.0 || e <= a.huber) ? 1.0 : a.huber / e;
                     C = C + rho(e, a.huber);
-                    const double *Tc = cfg->P[c];
-                    const float *K = cfg->K[c];
-                    const double kd0 = cfg->dist[c][0], kd1 = cfg->dist[c][1], kd2 = cfg->dist[c][4];
-                    const double fd = (kd0 + (2.0 * kd1) * pr.r) + ((3.0 * kd2) * pr.r) * pr.r;
                     double jx[3], jy[3];
-                    for (int k = 0; k < 3; ++k) {
-                        const double ak = (Tc[k] - pr.h0 * Tc[8 + k]) / pr.pc2, bk = (Tc[4 + k] - pr.h1 * Tc[8 + k]) / pr.pc2;
-                        const double qk = fd * (2.0 * (pr.h0 * ak + pr.h1 * bk));
-                        const double mk = ak * pr.f + pr.h0 * qk, nk = bk * pr.f + pr.h1 * qk;
-                        const double v0 = (double)K[0] * mk + (double)K[1] * nk, v1 = (double)K[3] * mk + (double)K[4] * nk;
-                        const double v2 = (double)K[6] * mk + (double)K[7] * nk;
-                        jx[k] = (v0 - pr.px * v2) / pr.u2;
-                        jy[k] = (v1 - pr.py * v2) / pr.u2;
-                    }
-                    A00 = A00 + w * (jx[0] * jx[0] + jy[0] * jy[0]);
-                    A01 = A01 + w * (jx[0] * jx[1] + jy[0] * jy[1]);
-                    A02 = A02 + w * (jx[0] * jx[2] + jy[0] * jy[2]);
-                    A11 = A11 + w * (jx[1] * jx[1] + jy[1] * jy[1]);
-                    A12 = A12 + w * (jx[1] * jx[2] + jy[1] * jy[2]);
-                    A22 = A22 + w * (jx[2] * jx[2] + jy[2] * jy[2]);
-                    g0 = g0 + w * (jx[0] * rx + jy[0] * ry);
-                    g1 = g1 + w * (jx[1] * rx + jy[1] * ry);
-                    g2 = g2 + w * (jx[2] * rx + jy[2] * ry);
+                    point_jacobian(cfg->P[c], cfg->dist[c], cfg->K[c], pr, jx, jy);
+                    N.add_pixel(huber_weight(e, a.huber), jx, jy, rx, ry);
                 }
                 if (with_bones)
                     for (uint32_t i = inc0; i < inc1; ++i) {
@@ -250,34 +218,13 @@ __global__ void __launch_bounds__(64) k_skel_refine(const DevCfg *__restrict__ c
                         const double q = bone_q(X0, X1, X2, x + 3 * (code & 255u), a.kappa, Ls[b], d, &l);
                         C = C + q * q;
                         if (!(l > 0.0)) continue;
-                        const double m0 = a.kappa * (d[0] / l), m1 = a.kappa * (d[1] / l), m2 = a.kappa * (d[2] / l);
-                        A00 = A00 + m0 * m0;
-                        A01 = A01 + m0 * m1;
-                        A02 = A02 + m0 * m2;
-                        A11 = A11 + m1 * m1;
-                        A12 = A12 + m1 * m2;
-                        A22 = A22 + m2 * m2;
-                        g0 = g0 + m0 * q;
-                        g1 = g1 + m1 * q;
-                        g2 = g2 + m2 * q;
+                        const double m[3] = {a.kappa * (d[0] / l), a.kappa * (d[1] / l), a.kappa * (d[2] / l)};
+                        N.add_bone(m, q);
                     }
-                // (A + lambda diag A) delta = -g, the LDL^T lines of mpe_refine_batch
-                const double M00 = A00 + lambda * A00, M11 = A11 + lambda * A11, M22 = A22 + lambda * A22;
-                const double D0 = M00;
-                const double L10 = A01 / D0, L20 = A02 / D0;
-                const double D1 = M11 - L10 * A01;
-                const double tt = A12 - L20 * A01;
-                const double L21 = tt / D1;
-                const double D2 = (M22 - L20 * A02) - L21 * tt;
-                const double z0 = -g0;
-                const double z1 = -g1 - L10 * z0;
-                const double z2 = (-g2 - L20 * z0) - L21 * z1;
-                const double e2 = z2 / D2;
-                const double e1 = z1 / D1 - L21 * e2;
-                const double e0 = (z0 / D0 - L10 * e1) - L20 * e2;
-                bool ok = D0 > 0.0 && D1 > 0.0 && D2 > 0.0 && finite3(e0, e1, e2);
+                double e[3];
+                bool ok = N.lm_step(lambda, e);
                 if (ok) {
-                    Y0 = X0 + e0, Y1 = X1 + e1, Y2 = X2 + e2;
+                    Y0 = X0 + e[0], Y1 = X1 + e[1], Y2 = X2 + e[2];
                     double Ct = pixel_cost(cfg, a, heads, j, obs, Y0, Y1, Y2, &ok);
                     if (with_bones)
                         for (uint32_t i = inc0; i < inc1; ++i) {
@@ -355,13 +302,13 @@ int skel_refine_tables(const int32_t *bones, int n_bones, int J, std::vector<uin
 hipError_t launch_skel_refine(hipStream_t s, const DevCfg *cfg, int V, mpe_skel_state *st, const mpe_batch &b, const mpe_body_refine_args &x) {
     const int J = st->J;
     SkelRefineK a{};
-    a.n_frames = x.n_frames; a.pcap = st->pcap; a.V = V; a.J = J; a.n_bones = st->n_bones; a.joint_flags = x.joint_flags;
+    a.n_frames = x.n_frames; a.pcap = st->pcap; a.V = V; a.J = J; a.n_bones = st->n_bones;
     a.tid_cap = st->tid_cap; a.sweeps = x.sweeps; a.n_colours = st->n_colours; a.batch_frames = b.n_frames;
     a.jmask = x.joint_mask & (J >= 32 ? 0xFFFFFFFFu : (1u << J) - 1u);
     a.kappa = x.bone_weight; a.huber = x.huber_px;
     a.sel = Selection{V, J, x.joint_flags, x.joint_mask, x.threshold, b.d_frame_head_off, b.d_joint_mask, b.d_vp, x.d_persons, x.d_n_persons, x.d_flags};
     a.xy = b.d_xy;
-    a.poses = x.d_poses; a.flags = x.d_flags; a.n_persons = x.d_n_persons; a.tid = x.d_track_id; a.frame = x.d_frame;
+    a.poses = x.d_poses; a.tid = x.d_track_id; a.frame = x.d_frame;
     a.poses_out = x.d_poses_out; a.status = x.d_status; a.n_views = x.d_n_views; a.n_bones_out = x.d_n_bones;
     a.cost = x.d_cost; a.err = x.d_err;
     a.bones = st->bones; a.len = st->len; a.tab = st->refine_tab;

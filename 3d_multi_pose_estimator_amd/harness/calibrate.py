@@ -25,7 +25,7 @@ import math
 import numpy as np
 
 from . import reprojection as R
-from .refine import camera_constants64
+from .refine import camera_constants64, huber_weight, jacobian_tail, project64, radial_slope, _rho
 
 SUMS = 28
 HELD, FEW_OBS, CONVERGED, STALLED, ACCEPTED, REJECTED = 1, 2, 4, 8, 16, 32
@@ -38,30 +38,15 @@ def project_camera(T, kd, K, X0, X1, X2, jacobian=False):
     with px, py, pc (three arrays) and, with jacobian, Jx / Jy: lists of six arrays, the derivatives of px / py by the
     perturbation xi = (w, tau) of the camera.  The header's lines."""
     with np.errstate(all='ignore'):
-        pc = [((T[i, 0] * X0 + T[i, 1] * X1) + T[i, 2] * X2) + T[i, 3] for i in range(3)]
-        h0 = pc[0] / pc[2]
-        h1 = pc[1] / pc[2]
-        r = h0 * h0 + h1 * h1
-        f = ((1.0 + kd[0] * r) + (kd[1] * r) * r) + ((kd[2] * r) * r) * r
-        d0 = h0 * f
-        d1 = h1 * f
-        u = [(K[i, 0] * d0 + K[i, 1] * d1) + K[i, 2] for i in range(3)]
-        px = u[0] / u[2]
-        py = u[1] / u[2]
-        out = {'px': px, 'py': py, 'pc': pc}
+        out = project64(T, kd, K, X0, X1, X2)
         if jacobian:
-            fd = (kd[0] + (2.0 * kd[1]) * r) + ((3.0 * kd[2]) * r) * r
+            pc, h0, h1 = out['pc'], out['h0'], out['h1']
+            fd = radial_slope(kd, out['r'])
             zero = np.zeros_like(h0)
             a = [1.0 / pc[2], zero, (-h0) / pc[2]]
             b = [zero, 1.0 / pc[2], (-h1) / pc[2]]
-            cx, cy = [], []
-            for k in range(3):
-                q = fd * (2.0 * (h0 * a[k] + h1 * b[k]))
-                m = a[k] * f + h0 * q
-                n = b[k] * f + h1 * q
-                v = [K[i, 0] * m + K[i, 1] * n for i in range(3)]
-                cx.append((v[0] - px * v[2]) / u[2])
-                cy.append((v[1] - py * v[2]) / u[2])
+            rows = [jacobian_tail(out, K, fd, a[k], b[k]) for k in range(3)]
+            cx, cy = [x for x, _ in rows], [y for _, y in rows]
             out['Jx'] = [cx[2] * pc[1] - cx[1] * pc[2], cx[0] * pc[2] - cx[2] * pc[0], cx[1] * pc[0] - cx[0] * pc[1], cx[0], cx[1], cx[2]]
             out['Jy'] = [cy[2] * pc[1] - cy[1] * pc[2], cy[0] * pc[2] - cy[2] * pc[0], cy[1] * pc[0] - cy[0] * pc[1], cy[0], cy[1], cy[2]]
     return out
@@ -104,11 +89,7 @@ def observation_terms(calib, E, pb, persons, n_persons, poses, flags, joint_mask
             rx = p['px'] - xy[:, :, c, :, 0]
             ry = p['py'] - xy[:, :, c, :, 1]
             e = np.sqrt(rx * rx + ry * ry)
-            if huber <= 0.0:
-                w, rho = np.ones_like(e), e * e
-            else:
-                w = np.where(e <= huber, 1.0, huber / e)
-                rho = np.where(e <= huber, e * e, (2.0 * huber) * e - huber * huber)
+            w, rho = huber_weight(e, huber), _rho(e, huber)
             Jx, Jy = p['Jx'], p['Jy']
             for q, (k, l) in enumerate(TRI):
                 terms[:, :, c, :, q] = w * (Jx[k] * Jx[l] + Jy[k] * Jy[l])

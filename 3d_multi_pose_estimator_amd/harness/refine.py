@@ -22,8 +22,9 @@ def camera_constants64(calib):
 
 
 def project64(T, kd, K, X0, X1, X2, jacobian=False):
-    """One camera (T [3,4], kd [3], K [3,3], float64), points X0 / X1 / X2 [...] float64 -> a dict with px, py, pc2 and,
-    with jacobian, jx / jy (lists of three arrays: the derivatives by X0, X1, X2).  The header's projection lines."""
+    """One camera (T [3,4], kd [3], K [3,3], float64), points X0 / X1 / X2 [...] float64 -> a dict with px, py, pc2 (and
+    the lines between: pc, h0, h1, r, f, u2) and, with jacobian, jx / jy (lists of three arrays: the derivatives by X0, X1,
+    X2).  The header's projection lines; csrc/project64.h has the same ones for the kernels."""
     with np.errstate(all='ignore'):
         pc = [((T[i, 0] * X0 + T[i, 1] * X1) + T[i, 2] * X2) + T[i, 3] for i in range(3)]
         h0 = pc[0] / pc[2]
@@ -35,20 +36,28 @@ def project64(T, kd, K, X0, X1, X2, jacobian=False):
         u = [(K[i, 0] * d0 + K[i, 1] * d1) + K[i, 2] for i in range(3)]
         px = u[0] / u[2]
         py = u[1] / u[2]
-        out = {'px': px, 'py': py, 'pc2': pc[2]}
+        out = {'px': px, 'py': py, 'pc2': pc[2], 'pc': pc, 'h0': h0, 'h1': h1, 'r': r, 'f': f, 'u2': u[2]}
         if jacobian:
-            fd = (kd[0] + (2.0 * kd[1]) * r) + ((3.0 * kd[2]) * r) * r
-            out['jx'], out['jy'] = [], []
-            for k in range(3):
-                a = (T[0, k] - h0 * T[2, k]) / pc[2]
-                b = (T[1, k] - h1 * T[2, k]) / pc[2]
-                q = fd * (2.0 * (h0 * a + h1 * b))
-                m = a * f + h0 * q
-                n = b * f + h1 * q
-                v = [K[i, 0] * m + K[i, 1] * n for i in range(3)]
-                out['jx'].append((v[0] - px * v[2]) / u[2])
-                out['jy'].append((v[1] - py * v[2]) / u[2])
+            fd = radial_slope(kd, r)
+            rows = [jacobian_tail(out, K, fd, (T[0, k] - h0 * T[2, k]) / pc[2], (T[1, k] - h1 * T[2, k]) / pc[2]) for k in range(3)]
+            out['jx'], out['jy'] = [x for x, _ in rows], [y for _, y in rows]
     return out
+
+
+def radial_slope(kd, r):
+    """d f / d r of the lens model"""
+    return (kd[0] + (2.0 * kd[1]) * r) + ((3.0 * kd[2]) * r) * r
+
+
+def jacobian_tail(p, K, fd, a, b):
+    """The tail of every Jacobian of (px, py).  p: project64's dict; (a, b): the derivative of (h0, h1) by one unknown;
+    fd = radial_slope -> (the derivative of px, of py) by that unknown."""
+    with np.errstate(all='ignore'):
+        q = fd * (2.0 * (p['h0'] * a + p['h1'] * b))
+        m = a * p['f'] + p['h0'] * q
+        n = b * p['f'] + p['h1'] * q
+        v = [K[i, 0] * m + K[i, 1] * n for i in range(3)]
+        return (v[0] - p['px'] * v[2]) / p['u2'], (v[1] - p['py'] * v[2]) / p['u2']
 
 
 def _rho(e, huber):
@@ -56,6 +65,37 @@ def _rho(e, huber):
         if huber <= 0.0:
             return e * e
         return np.where(e <= huber, e * e, (2.0 * huber) * e - huber * huber)
+
+
+def huber_weight(e, huber):
+    """the weight of a residual of length e in the normal equations; huber <= 0: 1"""
+    with np.errstate(all='ignore'):
+        return np.ones_like(e) if huber <= 0.0 else np.where(e <= huber, 1.0, huber / e)
+
+
+PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))          # the six entries of a symmetric 3 x 3 A, as the dicts below key them
+
+
+def lm_step3(A, g, lam):
+    """A {(k, l): array} over PAIRS, g [3] arrays, lam: (A + lam diag A) delta = -g, LDL^T written out -> (delta [..., 3],
+    ok: every pivot positive and delta finite)."""
+    with np.errstate(all='ignore'):
+        M00, M11, M22 = (A[k, k] + lam * A[k, k] for k in range(3))
+        D0 = M00
+        L10 = A[0, 1] / D0
+        L20 = A[0, 2] / D0
+        D1 = M11 - L10 * A[0, 1]
+        t = A[1, 2] - L20 * A[0, 1]
+        L21 = t / D1
+        D2 = (M22 - L20 * A[0, 2]) - L21 * t
+        z0 = -g[0]
+        z1 = -g[1] - L10 * z0
+        z2 = (-g[2] - L20 * z0) - L21 * z1
+        e2 = z2 / D2
+        e1 = z1 / D1 - L21 * e2
+        e0 = (z0 / D0 - L10 * e1) - L20 * e2
+        delta = np.stack([e0, e1, e2], axis=-1)
+        return delta, (D0 > 0.0) & (D1 > 0.0) & (D2 > 0.0) & np.isfinite(delta).all(axis=-1)
 
 
 def _cost(cams, X, xy, obs, huber):
@@ -109,35 +149,21 @@ def refine(calib, pb, persons, n_persons, poses, flags, joint_mask, threshold=0.
         for _ in range(int(max_iters)):
             if not active.any():
                 break
-            A = {kl: np.zeros(N) for kl in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))}
+            A = {kl: np.zeros(N) for kl in PAIRS}
             g = [np.zeros(N) for _ in range(3)]
             for c, (T, kd, K) in enumerate(cams):
                 p = project64(T, kd, K, X[:, 0], X[:, 1], X[:, 2], jacobian=True)
                 rx = p['px'] - xy[:, c, 0]
                 ry = p['py'] - xy[:, c, 1]
                 e = np.sqrt(rx * rx + ry * ry)
-                w = np.ones(N) if huber <= 0.0 else np.where(e <= huber, 1.0, huber / e)
+                w = huber_weight(e, huber)
                 jx, jy = p['jx'], p['jy']
                 for (k, l) in A:
                     A[k, l] = np.where(obs[:, c], A[k, l] + w * (jx[k] * jx[l] + jy[k] * jy[l]), A[k, l])
                 for k in range(3):
                     g[k] = np.where(obs[:, c], g[k] + w * (jx[k] * rx + jy[k] * ry), g[k])
-            M00, M11, M22 = (A[k, k] + lam * A[k, k] for k in range(3))
-            D0 = M00
-            L10 = A[0, 1] / D0
-            L20 = A[0, 2] / D0
-            D1 = M11 - L10 * A[0, 1]
-            t = A[1, 2] - L20 * A[0, 1]
-            L21 = t / D1
-            D2 = (M22 - L20 * A[0, 2]) - L21 * t
-            z0 = -g[0]
-            z1 = -g[1] - L10 * z0
-            z2 = (-g[2] - L20 * z0) - L21 * z1
-            e2 = z2 / D2
-            e1 = z1 / D1 - L21 * e2
-            e0 = (z0 / D0 - L10 * e1) - L20 * e2
-            delta = np.stack([e0, e1, e2], axis=1)
-            ok = active & (D0 > 0.0) & (D1 > 0.0) & (D2 > 0.0) & np.isfinite(delta).all(axis=1)
+            delta, ok = lm_step3(A, g, lam)
+            ok = active & ok
             Y = X + delta
             Ct, front = _cost(cams, Y, xy, obs, huber)
             accept = ok & front & (Ct < C)

@@ -44,7 +44,7 @@ import numpy as np
 
 from . import reprojection as R
 from . import skeleton as S
-from .refine import camera_constants64, project64, _rho
+from .refine import PAIRS, camera_constants64, huber_weight, lm_step3, project64, _rho
 
 FREE, MOVED, BAD_START, ONE_VIEW, BAD_FRAME = 1, 2, 4, 8, 16
 MAX_SWEEPS = 64
@@ -196,7 +196,7 @@ def refine_sequence(state, calib, pb, persons, n_persons, poses, flags, ids, mod
             for js in groups:
                 Y, o, z, fr = X[:, js], obs[:, js], xy[:, js], free[:, js]
                 m = len(js)
-                A = {kl: np.zeros((n, m)) for kl in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))}
+                A = {kl: np.zeros((n, m)) for kl in PAIRS}
                 g = [np.zeros((n, m)) for _ in range(3)]
                 C = np.zeros((n, m))
                 for c, (T, kd, K) in enumerate(cams):
@@ -204,7 +204,7 @@ def refine_sequence(state, calib, pb, persons, n_persons, poses, flags, ids, mod
                     rx = pr['px'] - z[..., c, 0]
                     ry = pr['py'] - z[..., c, 1]
                     e = np.sqrt(rx * rx + ry * ry)
-                    w = np.ones((n, m)) if huber <= 0.0 else np.where(e <= huber, 1.0, huber / e)
+                    w = huber_weight(e, huber)
                     jx, jy = pr['jx'], pr['jy']
                     oc = o[..., c]
                     C = np.where(oc, C + _rho(e, huber), C)
@@ -230,22 +230,8 @@ def refine_sequence(state, calib, pb, persons, n_persons, poses, flags, ids, mod
                     for k in range(3):
                         g[k] = np.where(on, g[k] + mk[k] * q, g[k])
                 lm = lam[:, js]
-                M00, M11, M22 = (A[k, k] + lm * A[k, k] for k in range(3))
-                D0 = M00
-                L10 = A[0, 1] / D0
-                L20 = A[0, 2] / D0
-                D1 = M11 - L10 * A[0, 1]
-                t = A[1, 2] - L20 * A[0, 1]
-                L21 = t / D1
-                D2 = (M22 - L20 * A[0, 2]) - L21 * t
-                z0 = -g[0]
-                z1 = -g[1] - L10 * z0
-                z2 = (-g[2] - L20 * z0) - L21 * z1
-                e2 = z2 / D2
-                e1 = z1 / D1 - L21 * e2
-                e0 = (z0 / D0 - L10 * e1) - L20 * e2
-                delta = np.stack([e0, e1, e2], axis=2)
-                ok = fr & (D0 > 0.0) & (D1 > 0.0) & (D2 > 0.0) & np.isfinite(delta).all(axis=2)
+                delta, ok = lm_step3(A, g, lm)
+                ok = fr & ok
                 trial = Y + delta
                 Ct, front = pixels(trial, o, z)
                 for on, N, L in held:

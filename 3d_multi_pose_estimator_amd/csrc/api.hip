@@ -160,6 +160,9 @@ int upload_linear(mpe_ctx *ctx, const float *w, const float *b, int out_dim, int
 
 int check_batch(mpe_ctx *ctx, const mpe_batch *b) {
     if (!ctx) return MPE_ERR_INVALID;
+    // every batch call starts here, and every batch call forgets the pairs mpe_match_batch left for mpe_mlp3d_batch: whatever this
+    // call is, the next mpe_mlp3d_batch is no longer "the call right after the matching of its batch" (pair_handoff.h)
+    ctx->handoff.forget();
     if (!b) return fail(ctx, MPE_ERR_INVALID, "batch is NULL");
     if (b->n_frames < 0 || b->n_heads < 0 || b->n_edge_nodes < 0) return fail(ctx, MPE_ERR_INVALID, "negative batch size");
     if (b->n_frames > ctx->cfg.max_frames || b->n_heads > ctx->cfg.max_heads ||
@@ -813,7 +816,7 @@ int copy_rows_in(mpe_ctx *ctx, hipStream_t s, float *dst, int ld_dst, const floa
 
 extern "C" {
 
-const char *mpe_version(void) { return "mpe-hip 0.2 (gfx950)"; }
+const char *mpe_version(void) { return "mpe-hip 0.3 (gfx950)"; }
 
 const char *mpe_last_error(const mpe_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
@@ -1237,32 +1240,24 @@ int mpe_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, float *d_sco
     }
     const int hmax = ctx->cfg.max_heads_per_frame;
     if ((rc = ensure_gat_workspace(ctx))) return rc;
-    for (int k = 0; k < 2; ++k)                               // whatever route this call takes: pairs solved for an older batch in these arrays are stale
-        if (ctx->pair_key[k] == b->d_xy) ctx->pair_key[k] = nullptr;
+    // (whatever route this call takes: check_batch has forgotten the pairs an earlier call solved)
     if (lat_gat_ok(ctx, b, false) && lat_tail_available(hmax, ctx->cl_keys_per_frame) && b->n_edge_nodes > 0) {
         // small batch: the last layer's scores and the clustering in ONE launch, and beside them every cross-camera pair of the batch
-        // solved for the row kernel of mpe_mlp3d_batch (which recognises the batch by the tag left here)
+        // solved for the row kernel of mpe_mlp3d_batch (which recognises the batch and the persons by the note left here)
         LatTail tail;
         if ((rc = run_gat_lat(ctx, s, b, scores, nullptr, &tail))) return rc;
         if (tail.deferred) {
             const int J = ctx->cfg.n_joints;
-            const int slot = ctx->pair_next;
+            const int slot = ctx->handoff.write_slot();
             const size_t need = (size_t)LAT_MAX_FRAMES * hmax * hmax * J * 3;
             // (the buffer is indexed by the batch's head number: a batch whose frames are within capacity has at most 16 hmax of them;
-            // anything else -- flagged on the device, rejected by Engine.check_capacity -- gets no pair solves and no tag)
+            // anything else -- flagged on the device, rejected by Engine.check_capacity -- gets no pair solves and no note)
             const bool pairs_ok = (size_t)b->n_heads <= (size_t)LAT_MAX_FRAMES * hmax;
             if (pairs_ok && !ctx->pair_pts[slot] && (rc = dev_alloc(ctx, &ctx->pair_pts[slot], need, false))) return rc;
-            for (int k = 0; k < 2; ++k)                       // one tag per input array at most: an older batch in the same arrays is gone
-                if (k == slot || ctx->pair_key[k] == b->d_xy) ctx->pair_key[k] = nullptr;
             HIPCHK(ctx, launch_lat_tail(s, ctx->d_cfg, *b, J, ctx->en_pair, ctx->en_frame, tail.ft2, tail.ld, ctx->a12, tail.alpha, tail.out_slope,
                                         tail.out_mode, ctx->node_off, scores, ctx->cfg.max_persons_per_frame, hmax, ctx->cl_keys_per_frame, d_persons,
                                         d_n_persons, pairs_ok ? ctx->pair_pts[slot] : nullptr));
-            if (pairs_ok) {
-                ctx->pair_key[slot] = b->d_xy;
-                ctx->pair_heads[slot] = b->n_heads;
-                ctx->pair_en[slot] = b->n_edge_nodes;
-                ctx->pair_next = slot ^ 1;
-            }
+            if (pairs_ok) ctx->handoff.note(mpe::pair_key(*b, d_persons, d_n_persons));      // (the next write goes to the other buffer)
             return MPE_OK;
         }
     } else if ((rc = run_gat(ctx, s, b, scores, nullptr))) {
@@ -1335,6 +1330,9 @@ int mpe_mlp_forward(mpe_ctx *ctx, void *stream, const float *d_x, int32_t ld_x, 
 
 int mpe_mlp3d_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const int32_t *d_persons,
                     const int32_t *d_n_persons, float *d_poses, uint8_t *d_valid) {
+    // the pairs mpe_match_batch left, if its note names exactly this batch and these persons: taken before check_batch forgets
+    // the note, as it does for every batch call -- a hand-off is used once, whatever becomes of this call
+    const int fetch = (ctx && b) ? ctx->handoff.take(mpe::pair_key(*b, d_persons, d_n_persons)) : -1;
     int rc = check_batch(ctx, b);
     if (rc) return rc;
     if (b->n_frames == 0) return MPE_OK;        // an empty batch has nothing to write (outputs may be NULL)
@@ -1350,11 +1348,9 @@ int mpe_mlp3d_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const int32_
     // column tiles at any batch size); small batches: the persons' prefix inside the row kernel as well
     const bool small = latency_path_on() && b->n_frames <= LAT_MAX_FRAMES;
     if (small) {
-        // the batch whose pairs mpe_match_batch left solved (same input arrays, same sizes)?  then the row kernel fetches them
-        const double *pairs = nullptr;
-        for (int k = 0; k < 2; ++k)
-            if (ctx->pair_key[k] && ctx->pair_key[k] == b->d_xy && ctx->pair_heads[k] == b->n_heads && ctx->pair_en[k] == b->n_edge_nodes)
-                pairs = ctx->pair_pts[k];
+        // the batch whose pairs the call before this one, mpe_match_batch, left solved (same arrays, generation and sizes, the
+        // persons it wrote)?  then the row kernel fetches them
+        const double *pairs = fetch >= 0 ? ctx->pair_pts[fetch] : nullptr;
         HIPCHK(ctx, launch_mlp_rows(s, ctx->d_cfg, ctx->cfg.n_cameras, ctx->cfg.n_joints, *b, d_persons, d_n_persons, nullptr, pcap, ctx->mlp_rows,
                                     ctx->mlp_ld_in, d_valid ? d_valid : ctx->valid_tmp, ctx->person_off, ctx->mlp_count, d_poses, n_out, pairs,
                                     ctx->cfg.max_heads_per_frame));

@@ -688,7 +688,11 @@ __global__ __launch_bounds__(64) void k_cluster_wave(const DevCfg *__restrict__ 
 // one wave; the rest of the chip is idle), every cross-camera skeleton pair of the batch for every joint: one DLT solve per
 // (edge-node, joint) with the arguments in camera order, as the row kernel's person_front would call it
 // (pose_estimator_dataset_from_json.py:63-101) -- which of them a person needs is only known after the clustering, that they
-// are all of this form is known before.  k_mlp_rows then fetches its pairs (pair_pts) instead of solving them: 21 -> 8 us.
+// are all of this form is known before.  k_mlp_rows then fetches its pairs (pair_pts) instead of solving them: 21 -> 8 us when this
+// was written; 17.5 -> 11 us on 1- and 8-frame batches of 5 x 4, re-measured in profiles/pair_handoff_timing.txt.
+// WHEN it fetches is host bookkeeping (pair_handoff.h): only mpe_mlp3d_batch as the context's next batch call after the
+// mpe_match_batch that launched this kernel, on the same batch (array pointers, generation, counts) and the persons written here;
+// once.  The buffer holds what the batch's arrays held at this launch and nothing tells it when they are rewritten.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct TailScores {                // the last layer's attention stage (AggArgs of that layer, the fields an N x 1 layer needs)
     const float *ft2;              // [n_nodes][ld]: column 0

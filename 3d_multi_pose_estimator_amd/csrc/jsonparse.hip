@@ -602,6 +602,7 @@ extern "C" int mpe_json_parse_device(mpe_ctx *ctx, void *stream, const char *d_t
     if (!ctx || !out || !d_totals || !d_scratch || !d_skeleton_index || n_entries < 0 || n_frames < 0 || head_cap < 0 ||
         skeletons_per_string_cap < 1)
         return MPE_ERR_INVALID;
+    ctx->handoff.forget();                    // a batch call like the others: this one REWRITES the arrays of `out` (pair_handoff.h)
     if (n_frames > 0 && (!d_frame_entry_off || !out->d_frame_head_off || !out->d_frame_en_off || !out->d_slot_cam || !out->d_slot_n))
         return MPE_ERR_INVALID;
     if (n_entries > 0 && (!d_text || !d_entries || !out->d_head_cam || !out->d_joint_mask || !out->d_tri_mask || !out->d_xy || !out->d_vp))

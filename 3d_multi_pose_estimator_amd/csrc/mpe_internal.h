@@ -7,6 +7,7 @@
 
 #include "../../include/mpe.h"
 #include "gemm_form.h"
+#include "pair_handoff.h"
 
 namespace mpe {
 
@@ -134,10 +135,10 @@ struct mpe_ctx {
     float *act[3] = {nullptr, nullptr, nullptr};   // [max_nodes][act_ld]
     float *a12 = nullptr;          // [max_nodes][2*16]
     // small batches: every cross-camera pair of a batch solved beside the clustering (cluster.hip: k_lat_tail) for the row kernel of the
-    // SAME batch to fetch: two buffers [heads][hmax][J][3] f64, each tagged with the batch it holds (the batch's d_xy pointer and sizes)
+    // SAME batch to fetch: two buffers [heads][hmax][J][3] f64 written in turn, and ONE note of the batch whose pairs the last
+    // mpe_match_batch solved -- kept until the next batch call, used once (pair_handoff.h has the rule)
     double *pair_pts[2] = {nullptr, nullptr};
-    const void *pair_key[2] = {nullptr, nullptr};
-    int pair_heads[2] = {0, 0}, pair_en[2] = {0, 0}, pair_next = 0;
+    mpe::PairHandoff handoff;
     unsigned short *gat_pl[2] = {nullptr, nullptr};   // small batches (lat.hip): activations between attention -> fc1 -> fc2 as three bf16 planes [3][lat_rows][act_ld]
     size_t gat_pl_plane = 0;       // plane stride in elements
     int lat_rows = 0;

@@ -31,7 +31,9 @@ struct PersonCtx {
 // s_und [V][J][2], s_pts [J][npairs][3], s_head[V] (global head index or -1)
 // pair_pts (small batches, cluster.hip: k_lat_tail): every cross-camera pair of the frame has ALREADY been solved, beside the
 // clustering -- [global head of the lower camera][frame-local head of the other][J][3] -- and a pair is fetched instead of solved
-// (the same function on the same arguments: the same bits).
+// (the same function on the same arguments: the same bits).  The caller passes pair_pts only for the batch and the persons of the
+// mpe_match_batch call right before it (pair_handoff.h: one note per context, forgotten by every batch call, taken once): pairs of
+// other contents at the same addresses would be read here without a sign -- every index stays inside the buffer.
 __device__ inline void person_front(const DevCfg *cfg, const PersonCtx &pc, const int32_t *s_head,
                                     const uint32_t *s_mask, const double *__restrict__ xy, double *s_und,
                                     double *s_pts, const double *__restrict__ pair_pts = nullptr, int pair_hmax = 0) {

@@ -56,6 +56,7 @@ class mpe_batch(C.Structure):
         ('d_slot_n', C.c_void_p), ('d_head_cam', C.c_void_p), ('d_joint_mask', C.c_void_p),
         ('d_tri_mask', C.c_void_p), ('d_xy', C.c_void_p), ('d_vp', C.c_void_p),
         ('d_en_pair', C.c_void_p),      # optional explicit edge-node list (process_training topology); NULL = implicit
+        ('generation', C.c_uint64),     # changes whenever the arrays are rewritten in place (packing.next_generation; mpe.h: mpe_mlp3d_batch)
     ]
 
 

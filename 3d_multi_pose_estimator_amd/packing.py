@@ -11,6 +11,7 @@ Ordering rules kept from the reference:
     (:590-591); ``skeleton_index`` remembers the position in the original list (:597-599);
   * joint key j is the COCO joint id string; values = [id, x, y, valid, prob].
 """
+import itertools
 import json
 
 import numpy as np
@@ -67,6 +68,16 @@ class PackedBatch:
 ARRAYS = (('frame_head_off', np.int32), ('frame_en_off', np.int32), ('slot_cam', np.int32), ('slot_n', np.int32),
           ('head_cam', np.int32), ('joint_mask', np.uint32), ('tri_mask', np.uint32), ('xy', np.float64),
           ('vp', np.float32))
+
+
+_generations = itertools.count(1)
+
+
+def next_generation():
+    """A number no mpe_batch of this process has carried yet (mpe_batch::generation): taken by every new batch struct and again
+    whenever its arrays are rewritten in place (DeviceBatch.rebind / upload), so that nothing the library computed from the
+    old contents is taken for the new ones' (include/mpe.h: the caller's rule at mpe_mlp3d_batch)."""
+    return next(_generations)
 
 
 class BatchArena:
@@ -282,6 +293,7 @@ class ParsedOnDevice:
         s.n_frames, s.n_heads, s.n_edge_nodes = self.n_frames, self.n_heads, self.n_edge_nodes
         for name, _ in ARRAYS:
             setattr(s, 'd_' + name, C.c_void_p(arena.ptr(name)))
+        s.generation = next_generation()      # the arena was just parsed into: another batch at the same addresses
         self.struct = s
 
     def max_heads_per_frame(self):
@@ -499,19 +511,23 @@ class DeviceBatch:
                 raise ValueError('arena-backed batches carry the implicit topology only')
             for name, _ in ARRAYS:
                 setattr(s, 'd_' + name, C.c_void_p(arena.ptr(name)))
+        s.generation = next_generation()
         self.struct = s
 
     def rebind(self, pb):
-        """Capacity arenas: the same device buffer now holds another batch (sizes only change)."""
+        """Capacity arenas: the same device buffer now holds another batch (sizes only change).  Whoever copies into a batch's
+        buffer by hand calls this (before or after the copy, before the next engine call): the batch takes a new generation."""
         self.host = pb
         self.struct.n_frames, self.struct.n_heads, self.struct.n_edge_nodes = pb.n_frames, pb.n_heads, pb.n_edge_nodes
+        self.struct.generation = next_generation()
         return self
 
     def upload(self, pinned):
         """One H2D copy of the whole batch from a pinned BatchArena of the same layout, on the
-        current stream."""
+        current stream.  New contents at the same addresses: a new generation."""
         assert self.arena is not None and pinned.nbytes == self.arena.nbytes
         self.arena.buf.copy_(pinned.buf, non_blocking=True)
+        self.struct.generation = next_generation()
 
     @property
     def n_frames(self):

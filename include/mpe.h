@@ -113,6 +113,11 @@ typedef struct {
      * truncated; raise max_heads_per_frame to make room.  Available on contexts with
      * max_heads_per_frame <= 1024 whose per-frame node ids fit 16 bits (MPE_ERR_UNSUPPORTED otherwise). */
     const int32_t *d_en_pair;
+    /* What the caller changes (to any other value) whenever it REWRITES the contents of the arrays above in place: same
+     * addresses, another batch.  The library cannot see such a rewrite; it compares this number where it keeps something it
+     * computed from the arrays from one call to the next (today: mpe_mlp3d_batch, which has the rule).  0 is a value like
+     * any other; a host that never reuses an address between mpe_match_batch and mpe_mlp3d_batch may leave it alone. */
+    uint64_t generation;
 } mpe_batch;
 
 /* ---- environment switches of the library (diagnostics; none is needed in production) -------------------------------------------
@@ -146,7 +151,7 @@ typedef struct {
 int mpe_create(const mpe_config *cfg, mpe_ctx **out);
 void mpe_destroy(mpe_ctx *ctx);
 const char *mpe_last_error(const mpe_ctx *ctx);
-const char *mpe_version(void);           /* "mpe-hip 0.2 ...": 0.2 = mpe_config.median_window is a double (the layout of 0.1 had a float) */
+const char *mpe_version(void);           /* "mpe-hip 0.3 ...": 0.2 = mpe_config.median_window is a double (the layout of 0.1 had a float); 0.3 = mpe_batch ends with `generation` */
 
 /* ---- weights (host pointers, copied once; ctx owns padded device copies) ---------------
  * GAT2 state-dict tensors of layer l (gat2.py:18-48): fc1.weight [in][in], fc1.bias [in],
@@ -203,10 +208,17 @@ int mpe_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b,
  * incl. get_3D_from_triangulation :63-101) + PoseEstimatorMLP + x10 decode
  * (metrics_from_model.py:243-294).
  *   d_poses [n_frames][Pcap][J][3] f32 metres, d_valid [n_frames][Pcap] 1 = person row kept
- * Small batches (<= 16 frames): when mpe_match_batch has just run on the SAME batch arrays (same d_xy pointer, same head and edge-node
- * counts), it has already solved every cross-camera skeleton pair of the batch beside its clustering launch, and the row kernel here
- * fetches them instead of solving (same function, same arguments: same bits).  The arrays must not change in between -- which the
- * call order of the pipeline implies anyway. */
+ * Small batches (<= 16 frames): mpe_match_batch has already solved every cross-camera skeleton pair of its batch beside its clustering
+ * launch, and the row kernel here fetches them instead of solving (same function, same arguments: same bits) -- in ONE case only: this
+ * call is the context's first batch call after that mpe_match_batch, and it is handed the same batch (every array pointer, the
+ * generation and the three counts equal) and the d_persons / d_n_persons arrays that call wrote.  The hand-off is used once: any batch
+ * entry point of the context (every function that takes an mpe_batch, this one included) ends it, and everything else solves its pairs
+ * itself.  Results never depend on which of the two happens.
+ * THE CALLER'S RULE.  One thing the library cannot see: new contents written into the same arrays between the two calls (a copy into
+ * a reused arena, a kernel of the caller's) with equal counts, and persons at the same address.  A caller that rewrites a batch's
+ * arrays between mpe_match_batch and mpe_mlp3d_batch -- instead of matching the new contents first, as the pipeline's call order does --
+ * must change mpe_batch::generation with the rewrite.  (Python: DeviceBatch.upload / rebind and every new DeviceBatch / ParsedOnDevice
+ * take a fresh generation; code that copies into a batch's buffer by hand calls rebind.) */
 int mpe_mlp3d_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b,
                     const int32_t *d_persons, const int32_t *d_n_persons,
                     float *d_poses, uint8_t *d_valid);

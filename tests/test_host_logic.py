@@ -1127,3 +1127,47 @@ def test_native_packer_accepts_the_json_dialect_of_python(calib):
         assert (nf, ne) == (1, 2)
     finally:
         ix.close()
+
+
+def test_pair_handoff_rule_under_the_host_sanitizers(tmp_path):
+    """csrc/pair_handoff.h -- which batch the pair solves of mpe_match_batch belong to and when mpe_mlp3d_batch may fetch them, host
+    code that touches no device -- in a stand-alone program (tests/native/pair_handoff_test.cpp) built with
+    -fsanitize=address,undefined and run as a child: the scenarios of tests/test_gpu_history.py as sequences of calls, uploads and
+    addresses, each with its answer (fetch / solve), and no fetch of pairs solved for other contents anywhere."""
+    import shutil
+    import subprocess
+    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
+    assert cxx, 'no host C++ compiler'
+    exe = str(tmp_path / 'pair_handoff_test')
+    subprocess.run([cxx, '-O1', '-g', '-std=c++17', '-Wall', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                    '-I', os.path.join(ROOT, '3d_multi_pose_estimator_amd', 'csrc'), os.path.join(ROOT, 'tests', 'native', 'pair_handoff_test.cpp'),
+                    '-o', exe], check=True, capture_output=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and re.fullmatch(r'ok \d+\n', r.stdout), r.stdout + r.stderr
+
+
+def test_every_rewrite_of_a_batch_takes_a_new_generation():
+    """mpe_batch::generation (include/mpe.h, the caller's rule at mpe_mlp3d_batch) as the package keeps it: a number per batch struct
+    that no other struct of the process carries, and a new one from DeviceBatch.rebind and DeviceBatch.upload -- the two ways new
+    contents reach a batch's arrays at the same addresses.  The field lies where the header puts it (the native program asserts the
+    same two numbers of the C struct)."""
+    packing, L = pkg('packing'), pkg('lib')
+    assert L.mpe_batch.generation.offset == 96 and ctypes.sizeof(L.mpe_batch) == 104
+    P = pkg('parameters').parameters
+    arr, frames = load_case(CASES[1])
+    pb = packing.pack_frames([oracle().processed_input(f) for f in frames[:2]], P)
+    host = packing.BatchArena(pb, 'host').fill(pb)
+    dbs = [packing.DeviceBatch(pb, 'cpu', arena=packing.BatchArena(pb, 'host')) for _ in range(2)] + [packing.DeviceBatch(pb, 'cpu')]
+    seen = [db.struct.generation for db in dbs]
+    assert min(seen) > 0 and len(set(seen)) == 3
+    db = dbs[0]
+    db.upload(host)
+    seen.append(db.struct.generation)
+    assert db.rebind(pb) is db
+    seen.append(db.struct.generation)
+    db.upload(host)
+    seen.append(db.struct.generation)
+    assert len(set(seen)) == 6 and seen == sorted(seen)
+    assert dbs[1].struct.generation == seen[1]            # (another batch's upload is not this batch's business)
+    pod = packing.ParsedOnDevice(packing.CapacityArena(pb.V, pb.J, 2, pb.n_heads, 'host'), pb.V, pb.J, 2, pb.n_heads, pb.n_edge_nodes, 20)
+    assert pod.struct.generation > seen[-1]

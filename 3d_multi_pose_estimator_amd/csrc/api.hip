@@ -396,6 +396,9 @@ int ensure_gat_workspace(mpe_ctx *ctx) {
         if (l > 0 && g.in_dim != ctx->gat[l - 1].heads * ctx->gat[l - 1].out_dim)
             return fail(ctx, MPE_ERR_INVALID, "GAT layer %d input width mismatch", l);
         if (g.heads > 16) return fail(ctx, MPE_ERR_INVALID, "at most 16 attention heads supported");
+        // the last layer's attention stage writes one score per node (agg_scores_out: row stride 1, column 0 only)
+        if (l == ctx->gat_layers - 1 && (g.heads != 1 || g.out_dim != 1))
+            return fail(ctx, MPE_ERR_INVALID, "the last GAT layer must have 1 head x 1 output (it has %d x %d)", g.heads, g.out_dim);
         if (l > 0) widest = widest > g.in_dim ? widest : g.in_dim;
         widest = widest > g.heads * g.out_dim ? widest : g.heads * g.out_dim;
     }

@@ -70,7 +70,7 @@ def gat_layer_dims(num_feats, hidden=None, heads=None, n_classes=1):
     return dims
 
 
-def gat_state_dict(seed, num_feats, hidden=None, heads=None, logit_gain=1.0, logit_shift=0.0):
+def gat_state_dict(seed, num_feats, hidden=None, heads=None, logit_gain=1.0, logit_shift=0.0, attn_gain=1.0):
     """Deterministic GAT2 weights under the reference's state-dict names
     (``layers.{l}.{attn_l,attn_r,fc1.weight,fc1.bias,fc2.weight,fc2.bias}``).
 
@@ -79,9 +79,14 @@ def gat_state_dict(seed, num_feats, hidden=None, heads=None, logit_gain=1.0, log
     sigmoid outputs spread over (0,1) instead of sitting in a narrow band (needed to
     keep sorted-score gaps far above fp32 reordering noise in the parity tests);
     `logit_shift` is added to the last layer's fc2 bias before the gain (centres the logits).
+    `attn_gain` multiplies attn_l / attn_r: it spreads the attention logits, so that the softmax over a node's
+    in-edges is far from uniform (1.0 leaves every bit as it is).  One number for every layer, or one per layer.
     """
     sd = {}
     dims = gat_layer_dims(num_feats, hidden, heads)
+    gains = [float(attn_gain)] * len(dims) if np.isscalar(attn_gain) else [float(g) for g in attn_gain]
+    if len(gains) != len(dims):
+        raise ValueError('attn_gain: one number, or one per layer (%d)' % len(dims))
     for l, (din, nh, dout) in enumerate(dims):
         s = 1000 * (l + 1)
         std1 = 1.414 * np.sqrt(2.0 / (din + din))
@@ -90,6 +95,9 @@ def gat_state_dict(seed, num_feats, hidden=None, heads=None, logit_gain=1.0, log
         g2 = logit_gain if l == len(dims) - 1 else 1.0
         sd['layers.%d.attn_l' % l] = hash_symmetric(seed, s + 1, (nh, dout, 1), np.sqrt(3.0) * stda)
         sd['layers.%d.attn_r' % l] = hash_symmetric(seed, s + 2, (nh, dout, 1), np.sqrt(3.0) * stda)
+        if gains[l] != 1.0:
+            for k in ('attn_l', 'attn_r'):
+                sd['layers.%d.%s' % (l, k)] = (sd['layers.%d.%s' % (l, k)] * np.float32(gains[l])).astype(np.float32)
         sd['layers.%d.fc1.weight' % l] = hash_symmetric(seed, s + 3, (din, din), np.sqrt(3.0) * std1)
         sd['layers.%d.fc1.bias' % l] = hash_symmetric(seed, s + 4, (din,), 1.0 / np.sqrt(din))
         sd['layers.%d.fc2.weight' % l] = hash_symmetric(seed, s + 5, (nh * dout, din), np.sqrt(3.0) * std2 * g2)
@@ -103,8 +111,9 @@ def gat_state_dict(seed, num_feats, hidden=None, heads=None, logit_gain=1.0, log
 def gat_params(num_feats, hidden=None, heads=None):
     """Contents of ``skeleton_matching.prms`` (reference train_skeleton_matching.py:231-246)
     minus the pickled activation modules (given here by slope / name)."""
-    return {'gnn_layers': GAT_LAYERS, 'num_feats': num_feats, 'n_classes': 1,
-            'num_hidden': list(GAT_HIDDEN if hidden is None else hidden),
+    hidden = list(GAT_HIDDEN if hidden is None else hidden)
+    return {'gnn_layers': len(hidden) + 1, 'num_feats': num_feats, 'n_classes': 1,
+            'num_hidden': hidden,
             'heads': list(GAT_HEADS if heads is None else heads),
             'nonlinearity': 0.01, 'final_activation': 'sigmoid',
             'in_drop': 0.0, 'attn_drop': 0.0, 'alpha': GAT_ALPHA, 'residual': False}

@@ -155,7 +155,10 @@ const char *mpe_version(void);           /* "mpe-hip 0.3 ...": 0.2 = mpe_config.
 
 /* ---- weights (host pointers, copied once; ctx owns padded device copies) ---------------
  * GAT2 state-dict tensors of layer l (gat2.py:18-48): fc1.weight [in][in], fc1.bias [in],
- * fc2.weight [heads*out][in], fc2.bias [heads*out], attn_l / attn_r [heads][out]. */
+ * fc2.weight [heads*out][in], fc2.bias [heads*out], attn_l / attn_r [heads][out].
+ * Limits: 2 <= n_layers <= MPE_MAX_GAT_LAYERS (mpe_set_gat_params); any in_dim / out_dim, at most 16 attention heads per layer;
+ * the last layer is 1 head x 1 output (n_classes = 1: one score per node).  The last two are checked at the first batch call,
+ * before anything is allocated or launched: MPE_ERR_INVALID.  (tests/test_gpu_gat_archs.py runs other shapes than the deployed one.) */
 int mpe_set_gat_params(mpe_ctx *ctx, int32_t n_layers, float alpha, float hidden_slope);
 int mpe_set_gat_layer(mpe_ctx *ctx, int32_t layer, int32_t in_dim, int32_t heads, int32_t out_dim,
                       const float *fc1_w, const float *fc1_b, const float *fc2_w, const float *fc2_b,

@@ -2350,3 +2350,147 @@ int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_ca
 }
 
 }  // extern "C"
+
+// ---- time lags (lag.hip sums on the device; the pick below is host work, once per pass) ----
+#include "lag_pick.h"
+
+namespace {
+
+struct LagSums {
+    std::vector<double> cost;
+    std::vector<int64_t> ctr;                        // n_obs [V][K] | n_skipped [V][K] | n_support [V] | n_unsupported [V]
+};
+
+int lag_fetch(mpe_ctx *ctx, hipStream_t s, mpe_lag_state *st, LagSums *h) {
+    const size_t vk = (size_t)st->V * st->K;
+    h->cost.resize(vk);
+    h->ctr.resize(lag_counter_words(st->V, st->K));
+    HIPCHK(ctx, hipMemcpyAsync(h->cost.data(), st->cost, vk * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h->ctr.data(), st->ctr, h->ctr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return MPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpe_lag_destroy(mpe_ctx *ctx, mpe_lag_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    dev_free(ctx, st->cost);
+    dev_free(ctx, st->ctr);
+    dev_free(ctx, st->S);
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_lag_create(mpe_ctx *ctx, const mpe_lag_config *cfg, mpe_lag_state **out) {
+    return create_state(ctx, "mpe_lag_create", out, mpe_lag_destroy, [&](mpe_lag_state *st) {
+        if (!cfg) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_create: NULL argument");
+        if (cfg->window < 0 || cfg->window > MPE_LAG_MAX_WINDOW || cfg->sub < 1 || cfg->sub > MPE_LAG_MAX_SUB)
+            return fail(ctx, MPE_ERR_INVALID, "mpe_lag_create: window %d must be within 0 .. %d and sub %d within 1 .. %d", cfg->window,
+                        MPE_LAG_MAX_WINDOW, cfg->sub, MPE_LAG_MAX_SUB);
+        if (cfg->n_joints != ctx->cfg.n_joints)
+            return fail(ctx, MPE_ERR_INVALID, "mpe_lag_create: %d joints, the context has %d", cfg->n_joints, ctx->cfg.n_joints);
+        if (cfg->pcap < 1 || cfg->max_frames < 1 || (cfg->pose_f64 & ~1) || (cfg->joint_flags & ~1))
+            return fail(ctx, MPE_ERR_INVALID, "mpe_lag_create: pcap %d and max_frames %d must be at least 1, pose_f64 %d and joint_flags %d 0 or 1",
+                        cfg->pcap, cfg->max_frames, cfg->pose_f64, cfg->joint_flags);
+        if (cfg->pcap > MPE_TRACK_MAX_PERSONS || cfg->max_frames > (1 << 23))
+            return fail(ctx, MPE_ERR_CAPACITY, "mpe_lag_create: pcap %d over %d or max_frames %d over 2^23", cfg->pcap, MPE_TRACK_MAX_PERSONS,
+                        cfg->max_frames);
+        st->V = ctx->cfg.n_cameras;
+        st->W = cfg->window;
+        st->sub = cfg->sub;
+        st->K = 2 * cfg->window * cfg->sub + 1;
+        st->pcap = cfg->pcap;
+        st->J = cfg->n_joints;
+        st->pose_f64 = cfg->pose_f64;
+        st->joint_flags = cfg->joint_flags;
+        st->max_frames = cfg->max_frames;
+        const size_t vk = (size_t)st->V * st->K;
+        int rc = dev_alloc(ctx, &st->cost, vk);
+        if (!rc) rc = dev_alloc(ctx, &st->ctr, lag_counter_words(st->V, st->K));
+        if (!rc) rc = dev_alloc(ctx, &st->S, (size_t)st->max_frames * vk, false);
+        return rc;
+    });
+}
+
+int mpe_lag_reset(mpe_ctx *ctx, void *stream, mpe_lag_state *st) { return reset_state(ctx, "mpe_lag_reset", stream, st, launch_lag_reset); }
+
+int mpe_lag_launches(mpe_ctx *ctx, const mpe_lag_state *st, int64_t *n) { return state_launches(ctx, "mpe_lag_launches", st, n); }
+
+int mpe_lag_batch(mpe_ctx *ctx, void *stream, mpe_lag_state *st, const mpe_batch *b, const mpe_lag_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_frames != b->n_frames)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: n_frames %d, the batch has %d frames", a->n_frames, b->n_frames);
+    if (a->n_joints != ctx->cfg.n_joints)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: %d joints, the context has %d", a->n_joints, ctx->cfg.n_joints);
+    bool run;
+    rc = check_pose_rows(ctx, "mpe_lag_batch", st, a, &run);
+    if (rc) return rc;
+    if (a->joint_flags != st->joint_flags)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: joint_flags %d, the state was made for %d", a->joint_flags, st->joint_flags);
+    if (st->V != ctx->cfg.n_cameras) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: the state belongs to another context");
+    if (a->frame_start < 0 || a->n_table < 0 || (int64_t)a->frame_start + a->n_frames > a->n_table)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: frame_start %d + n_frames %d must lie within the table's %d frames", a->frame_start,
+                    a->n_frames, a->n_table);
+    if (a->n_frames > st->max_frames)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: %d frames, max_frames of the state is %d", a->n_frames, st->max_frames);
+    if (!(a->huber_px >= 0.0)) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: huber_px %g must not be negative", a->huber_px);
+    if (!run) return MPE_OK;
+    if (!a->d_persons || !a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_tid) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_batch: NULL argument");
+    HIPCHK(ctx, launch_lag(static_cast<hipStream_t>(stream), ctx->d_cfg, st, *b, *a));
+    return MPE_OK;
+}
+
+int mpe_lag_read(mpe_ctx *ctx, void *stream, mpe_lag_state *st, double *cost, int64_t *n_obs, int64_t *n_skipped, int64_t *n_support,
+                 int64_t *n_unsupported) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_read: NULL state");
+    DeviceGuard dg(ctx);
+    LagSums h;
+    const int rc = lag_fetch(ctx, static_cast<hipStream_t>(stream), st, &h);
+    if (rc) return rc;
+    const size_t vk = (size_t)st->V * st->K, v = (size_t)st->V;
+    if (cost) std::memcpy(cost, h.cost.data(), vk * sizeof(double));
+    if (n_obs) std::memcpy(n_obs, h.ctr.data(), vk * sizeof(int64_t));
+    if (n_skipped) std::memcpy(n_skipped, h.ctr.data() + vk, vk * sizeof(int64_t));
+    if (n_support) std::memcpy(n_support, h.ctr.data() + 2 * vk, v * sizeof(int64_t));
+    if (n_unsupported) std::memcpy(n_unsupported, h.ctr.data() + 2 * vk + v, v * sizeof(int64_t));
+    return MPE_OK;
+}
+
+int mpe_lag_estimate(mpe_ctx *ctx, void *stream, mpe_lag_state *st, int32_t min_obs, mpe_lag_report *report) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !report) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_estimate: NULL argument");
+    if (min_obs < 1) return fail(ctx, MPE_ERR_INVALID, "mpe_lag_estimate: min_obs %lld is below 1", (long long)min_obs);
+    DeviceGuard dg(ctx);
+    LagSums h;
+    const int rc = lag_fetch(ctx, static_cast<hipStream_t>(stream), st, &h);
+    if (rc) return rc;
+    const size_t vk = (size_t)st->V * st->K;
+    std::memset(report, 0, sizeof *report);
+    report->n_cameras = st->V;
+    report->n_grid = st->K;
+    for (int c = 0; c < st->V; ++c) {
+        const lag_pick_result p = lag_pick(h.cost.data() + (size_t)c * st->K, h.ctr.data() + (size_t)c * st->K, st->W, st->sub, min_obs);
+        mpe_lag_cam_report &r = report->cam[c];
+        r.status = p.status;
+        r.k_best = p.k_best;
+        r.lag_grid = p.lag_grid;
+        r.lag_refined = p.lag_refined;
+        r.cost_best = p.cost_best;
+        r.cost_zero = p.cost_zero;
+        r.n_obs = p.n_obs;
+        r.n_support = h.ctr[2 * vk + c];
+        r.n_unsupported = h.ctr[2 * vk + st->V + c];
+    }
+    return MPE_OK;
+}
+
+}  // extern "C"

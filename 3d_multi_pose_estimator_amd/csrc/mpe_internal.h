@@ -273,6 +273,16 @@ struct mpe_calib_state {
     mpe_calib_host *host = nullptr;
 };
 
+// lag.hip: what mpe_lag_batch accumulates and mpe_lag_read / mpe_lag_estimate read.  The pick of the least entry is host
+// work (api.hip, csrc/lag_pick.h).
+struct mpe_lag_state {
+    int V = 0, K = 0, W = 0, sub = 0, pcap = 0, J = 0, pose_f64 = 0, joint_flags = 0, max_frames = 0;
+    int64_t launches = 0;           // kernels enqueued since mpe_lag_create
+    double *cost = nullptr;         // [V][K] sums of the pass so far
+    unsigned long long *ctr = nullptr;   // n_obs [V][K] | n_skipped [V][K] | n_support [V] | n_unsupported [V]
+    double *S = nullptr;            // scratch [max_frames][V][K]: the per-frame partials of a call
+};
+
 namespace mpe {
 
 // gemm.hip
@@ -454,6 +464,10 @@ hipError_t launch_consolidate(hipStream_t s, const DevCfg *cfg, int V, int hmax,
 size_t calib_workspace_doubles(int max_frames, int V);
 hipError_t launch_calib(hipStream_t s, const DevCfg *cfg, int V, mpe_calib_state *st, const mpe_batch &b, const mpe_calib_args &a);
 hipError_t launch_calib_clear(hipStream_t s, mpe_calib_state *st, int V);
+// lag.hip
+size_t lag_counter_words(int V, int K);
+hipError_t launch_lag(hipStream_t s, const DevCfg *cfg, mpe_lag_state *st, const mpe_batch &b, const mpe_lag_args &a);
+hipError_t launch_lag_reset(hipStream_t s, mpe_lag_state *st);
 // geom.hip: en_pair = the context's pair table (launch_topology); ray_table only when geom_needs_table()
 constexpr size_t GEOM_LDS_BYTES = 48 * 1024;     // head records of a frame staged in LDS up to this (three 256-thread workgroups per CU's 160 KiB)
 bool geom_needs_table(int max_heads_per_frame, int J);

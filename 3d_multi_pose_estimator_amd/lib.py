@@ -205,6 +205,29 @@ class mpe_calib_report(C.Structure):
     _fields_ = [('n_cameras', C.c_int32), ('all_done', C.c_int32), ('cam', mpe_calib_cam_report * MPE_MAX_CAMERAS)]
 
 
+class mpe_lag_config(C.Structure):
+    _fields_ = [('pcap', C.c_int32), ('n_joints', C.c_int32), ('window', C.c_int32), ('sub', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('max_frames', C.c_int32), ('reserved', C.c_int32)]
+
+
+class mpe_lag_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('frame_start', C.c_int32), ('n_table', C.c_int32), ('joint_mask', C.c_uint32),
+                ('threshold', C.c_float), ('reserved', C.c_int32), ('huber_px', C.c_double),
+                ('d_persons', C.c_void_p), ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p),
+                ('d_tid', C.c_void_p)]
+
+
+class mpe_lag_cam_report(C.Structure):
+    _fields_ = [('status', C.c_int32), ('k_best', C.c_int32), ('lag_grid', C.c_double), ('lag_refined', C.c_double),
+                ('cost_best', C.c_double), ('cost_zero', C.c_double), ('n_obs', C.c_int64), ('n_support', C.c_int64),
+                ('n_unsupported', C.c_int64)]
+
+
+class mpe_lag_report(C.Structure):
+    _fields_ = [('n_cameras', C.c_int32), ('n_grid', C.c_int32), ('cam', mpe_lag_cam_report * MPE_MAX_CAMERAS)]
+
+
 class mpe_geom_args(C.Structure):
     _fields_ = [('sigma_m', C.c_double), ('clip_m', C.c_double), ('min_joints', C.c_int32), ('joint_mask', C.c_uint32),
                 ('min_conf', C.c_float), ('d_scores', C.c_void_p), ('d_n_votes', C.c_void_p), ('d_mean', C.c_void_p)]
@@ -288,6 +311,10 @@ MPE_CONSOLIDATE_RAY_DOUBLES = 3520
 # per-camera status bits of mpe_calib_step and the sums a camera accumulates
 MPE_CALIB_HELD, MPE_CALIB_FEW_OBS, MPE_CALIB_CONVERGED, MPE_CALIB_STALLED, MPE_CALIB_ACCEPTED, MPE_CALIB_REJECTED = 1, 2, 4, 8, 16, 32
 MPE_CALIB_SUMS = 28
+
+# per-camera status bits of mpe_lag_estimate and the caps of mpe_lag_create
+MPE_LAG_FEW_OBS, MPE_LAG_EDGE, MPE_LAG_FLAT = 1, 2, 4
+MPE_LAG_MAX_WINDOW, MPE_LAG_MAX_SUB = 8, 8
 
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
@@ -381,6 +408,14 @@ SYMBOLS = {
     'mpe_calib_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'mpe_calib_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_calib_step_args), C.POINTER(mpe_calib_report)]),
     'mpe_calib_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_lag_create': (C.c_int, [C.c_void_p, C.POINTER(mpe_lag_config), C.POINTER(C.c_void_p)]),
+    'mpe_lag_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_lag_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_lag_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_lag_args)]),
+    'mpe_lag_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_lag_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                               C.POINTER(C.c_int64)]),
+    'mpe_lag_estimate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(mpe_lag_report)]),
     'mpe_geom_scores_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args)]),
     'mpe_geom_match_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args), C.c_void_p, C.c_void_p]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),

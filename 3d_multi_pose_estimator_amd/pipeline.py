@@ -1297,6 +1297,16 @@ class Engine:
         calibration is never modified: Calibrator.calibration() gives the one to build the next engine from."""
         return Calibrator(self, kind, huber_px, min_obs, hold)
 
+    def lag_estimator(self, kind, window=4, sub=4, huber_px=0.0, pcap=None, max_frames=None):
+        """A LagEstimator for a table of tracked poses of `kind` ('est': f32 poses with per-row flags, 'triang': f64 poses
+        with per-joint flags, as the calibrator takes them): how many frames every camera runs ahead of or behind the
+        poses of the recording, on a grid of lags within +- `window` frames with `sub` entries per frame (mpe_lag_*;
+        include/mpe.h has the rule, harness/lag.py states it in numpy).  huber_px > 0 bounds the pull of an outlying
+        detection.  pcap: rows per frame (default: the engine's Pcap); max_frames: frames per accumulate() (default: the
+        engine's)."""
+        return LagEstimator(self, kind, window, sub, huber_px, self.pcap if pcap is None else int(pcap),
+                            self.max_frames if max_frames is None else int(max_frames))
+
     def residual_stats(self, res_list):
         """Per-camera statistics of one or more residual tensors [..., V, J] f64 on the device (mpe_residual_stats): the
         exact middle elements by radix select, a sum reduced in a fixed order.  -> dict of numpy arrays over the cameras:
@@ -1681,6 +1691,90 @@ class Calibrator(_DeviceState):
 
     def reset(self):
         """Start afresh from the engine's own extrinsics."""
+        self._open()
+        super().reset()
+
+
+class LagEstimator(_DeviceState):
+    """Engine.lag_estimator's object: per camera the cost of every grid lag and the counts on the device.  A pass is
+    accumulate() over every batch of the recording with the same table, in any chunking (the sums are the same bits), then
+    estimate().  accumulate() stays on the current stream and neither synchronises nor reads back; read() and estimate()
+    synchronise."""
+    _prefix, _noun = 'mpe_lag', 'lag estimator'
+
+    def __init__(self, eng, kind, window, sub, huber_px, pcap, max_frames):
+        if kind not in ('est', 'triang'):
+            raise ValueError('kind must be est or triang')
+        if not 0 <= int(window) <= L.MPE_LAG_MAX_WINDOW or not 1 <= int(sub) <= L.MPE_LAG_MAX_SUB:
+            raise ValueError('window must be within 0 .. %d and sub within 1 .. %d' % (L.MPE_LAG_MAX_WINDOW, L.MPE_LAG_MAX_SUB))
+        if not huber_px >= 0.0:
+            raise ValueError('huber_px must be >= 0')
+        if int(max_frames) < 1:
+            raise ValueError('max_frames must be at least 1')
+        self.kind, self.window, self.sub, self.huber_px = kind, int(window), int(sub), float(huber_px)
+        self.pcap, self.max_frames = int(pcap), int(max_frames)
+        self.K = 2 * self.window * self.sub + 1
+        self._keep = None
+        cfg = L.mpe_lag_config()
+        cfg.pcap, cfg.n_joints, cfg.window, cfg.sub = self.pcap, eng.J, self.window, self.sub
+        cfg.pose_f64 = cfg.joint_flags = int(kind == 'triang')
+        cfg.max_frames = self.max_frames
+        self._create(eng, C.byref(cfg))
+
+    def accumulate(self, db, frame_start, persons, table_poses, table_flags, table_n_persons, table_ids, joint_mask=None, threshold=0.5):
+        """The observations of one batch added to the pass: db holds the detections of the table frames frame_start ..
+        frame_start + db.n_frames - 1, persons [B,Pcap,V] i32 their rows; the table (poses, flags, n_persons, ids of the
+        whole sequence, as the sequence stages take them) is the same at every call of a pass."""
+        self._open()
+        eng, tri = self.eng, self.kind == 'triang'
+        B = db.n_frames
+        n_table = _check_pose_rows(eng.J, self.pcap, tri, tri, table_poses, table_flags, table_n_persons, table_ids, device=eng.device)
+        if persons.dtype != torch.int32 or tuple(persons.shape) != (B, self.pcap, eng.V) or not persons.is_contiguous():
+            raise ValueError('persons must be int32 [%d,%d,%d], contiguous' % (B, self.pcap, eng.V))
+        if joint_mask is None:
+            joint_mask = (1 << eng.J) - 1 if tri else sum(1 << j for j in eng.params.used_joints)
+        a = L.mpe_lag_args()
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, self.pcap, eng.J, int(tri), int(tri)
+        a.frame_start, a.n_table, a.joint_mask, a.threshold, a.huber_px = int(frame_start), n_table, int(joint_mask), float(threshold), self.huber_px
+        a.d_persons, a.d_poses, a.d_flags = persons.data_ptr(), table_poses.data_ptr(), table_flags.data_ptr()
+        a.d_n_persons, a.d_tid = table_n_persons.data_ptr(), table_ids.data_ptr()
+        eng._chk(eng.lib.mpe_lag_batch(eng.ctx, eng._stream(), self.state, C.byref(db.struct), C.byref(a)))
+        self._keep = (db, persons, table_poses, table_flags, table_n_persons, table_ids)      # alive until the caller has synchronised
+
+    def read(self):
+        """The sums of the pass so far (synchronises) -> {'cost' [V,K] f64, 'n_obs' [V,K], 'n_skipped' [V,K], 'n_support'
+        [V], 'n_unsupported' [V] i64}."""
+        self._open()
+        eng = self.eng
+        out = {'cost': np.zeros((eng.V, self.K)), 'n_obs': np.zeros((eng.V, self.K), np.int64), 'n_skipped': np.zeros((eng.V, self.K), np.int64),
+               'n_support': np.zeros(eng.V, np.int64), 'n_unsupported': np.zeros(eng.V, np.int64)}
+        i64p = C.POINTER(C.c_int64)
+        eng._chk(eng.lib.mpe_lag_read(eng.ctx, eng._stream(), self.state, out['cost'].ctypes.data_as(L.c_f64p),
+                                      *(out[k].ctypes.data_as(i64p) for k in ('n_obs', 'n_skipped', 'n_support', 'n_unsupported'))))
+        self._keep = None
+        return out
+
+    def estimate(self, min_obs=50):
+        """The lag of every camera from the sums of the pass so far (mpe_lag_estimate; synchronises) -> {'status'
+        (MPE_LAG_* bits), 'k_best' i32, 'lag_grid', 'lag_refined', 'cost_best', 'cost_zero' f64, 'n_obs', 'n_support',
+        'n_unsupported' i64} as arrays over the cameras."""
+        self._open()
+        eng = self.eng
+        rep = L.mpe_lag_report()
+        eng._chk(eng.lib.mpe_lag_estimate(eng.ctx, eng._stream(), self.state, int(min_obs), C.byref(rep)))
+        self._keep = None
+        cams = [rep.cam[c] for c in range(rep.n_cameras)]
+        out = {k: np.array([getattr(c, k) for c in cams], np.int32) for k in ('status', 'k_best')}
+        out.update({k: np.array([getattr(c, k) for c in cams], np.float64) for k in ('lag_grid', 'lag_refined', 'cost_best', 'cost_zero')})
+        out.update({k: np.array([getattr(c, k) for c in cams], np.int64) for k in ('n_obs', 'n_support', 'n_unsupported')})
+        return out
+
+    def launches(self):
+        self._open()
+        return super().launches()
+
+    def reset(self):
+        """The sums and the counts back to zero: a new pass (ordered on the current stream)."""
         self._open()
         super().reset()
 

@@ -320,6 +320,54 @@ def make_frames(calib, n, spec=None, seed=1234, start=0):
     return frames, gts
 
 
+def walking_bodies(n_bodies, times, seed=1234, step=0.03, weave=0.0, n_joints=18):
+    """Bodies on seeded smooth walks at the given times (frames, any real numbers) -> [len(times), P, J, 3] world metres.
+    A body is a fixed cloud of joints around a root that walks `step` metres per frame along a seeded heading; weave > 0
+    adds a sideways sine of that amplitude (metres, period about 20 frames).  Starts, velocities and joint offsets are
+    multiples of 2^-10, 2^-8 and 2^-10: with weave = 0 a body's position at any multiple of 1/8 frame is exact in float64,
+    and so is the linear interpolation between two frames -- a straight walk has no rounding of its own."""
+    P, J = int(n_bodies), int(n_joints)
+    u = hash_uniform(seed, 7001, P * 5).reshape(P, 5)
+    start = np.stack([u[:, 0] * 1.2 - 0.6, -(0.8 + 0.4 * u[:, 1]), u[:, 2] * 1.2 - 0.6], axis=1)
+    start = np.round(start * 1024.0) / 1024.0
+    ang = 2.0 * np.pi * u[:, 3]
+    vel = np.stack([np.cos(ang), np.zeros(P), np.sin(ang)], axis=1) * step
+    vel = np.round(vel * 256.0) / 256.0
+    side = np.stack([-np.sin(ang), np.zeros(P), np.cos(ang)], axis=1)
+    g = _normal(hash_uniform(seed, 7002, P * J * 3), hash_uniform(seed, 7003, P * J * 3)).reshape(P, J, 3)
+    cloud = np.round(0.25 * g * 1024.0) / 1024.0
+    t = np.asarray(times, np.float64).reshape(-1)
+    root = start[None] + vel[None] * t[:, None, None]                                   # [T, P, 3]
+    if weave:
+        root = root + weave * np.sin(0.3 * t[:, None, None] + 2.0 * np.pi * u[None, :, 4, None]) * side[None]
+    return root[:, :, None, :] + cloud[None]
+
+
+def lagged_recording(calib, n_frames, lags, n_bodies=2, seed=1234, step=0.03, weave=0.0, orders=None):
+    """A recording whose cameras do not see the same instant: camera c's entry of frame f is frame_from_bodies of the
+    walking bodies at time f + lags[c] (lags: a list over params.used_cameras_skeleton_matching or {camera: frames}; a
+    camera that is not named has lag 0).  orders: {camera: the order of the persons in its skeleton lists}.
+    -> (frames, owners [{camera: person of every skeleton}], bodies [n_frames,P,J,3] at the integer frames,
+    {camera: its bodies [n_frames,P,J,3]})."""
+    params = calib.params
+    if not isinstance(lags, dict):
+        lags = dict(zip(params.used_cameras_skeleton_matching, lags))
+    J = len(params.joint_list)
+    frames_t = np.arange(n_frames, dtype=np.float64)
+    bodies = walking_bodies(n_bodies, frames_t, seed, step, weave, J)
+    at = {lag: walking_bodies(n_bodies, frames_t + lag, seed, step, weave, J) for lag in set(float(lags.get(cam, 0.0)) for cam in params.camera_names)}
+    seen = {cam: at[float(lags.get(cam, 0.0))] for cam in params.camera_names}
+    frames, owners = [], []
+    for f in range(n_frames):
+        frame, owner = {}, {}
+        made = {lag: frame_from_bodies(calib, f, b[f], orders) for lag, b in at.items()}      # cameras of one lag share a call
+        for cam in params.camera_names:
+            frame[cam], owner[cam] = (part[cam] for part in made[float(lags.get(cam, 0.0))])
+        frames.append(frame)
+        owners.append(owner)
+    return frames, owners, bodies, seen
+
+
 def decoder_mlp_state_dict(n_cameras, n_joints=18, npj=14, noise_seed=None, noise_bound=0.0, mean_of=range(5, 18)):
     """Hand-built PoseEstimatorMLP weights (reference utils/mlp.py:8-28 shapes and key names) that
     make the network a DECODER of its own input row: output joint j = the triangulated point the

@@ -513,6 +513,113 @@ int mpe_calib_read(mpe_ctx *ctx, void *stream, mpe_calib_state *st, double *sums
 int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_calib_step_args *a, mpe_calib_report *report);
 int mpe_calib_launches(mpe_ctx *ctx, const mpe_calib_state *st, int64_t *n);
 
+/* Time lags: how many frames each camera runs ahead of or behind the poses of a recording, estimated from the recording
+ * itself -- the time half of the rig adjustment of which mpe_calib_* is the space half.  The 3D poses of the whole
+ * sequence, with track ids, are a table; every detection of a camera is compared with the projection of its track's pose
+ * at the table frames f + lag for a grid of lags, linearly interpolated between frames, and the reprojection cost of every
+ * grid entry is summed per camera.  The entry of least mean cost, refined by a parabola through its neighbours, is the
+ * camera's lag relative to the poses' own time (the common shift of all cameras cannot be seen from poses the cameras made
+ * themselves).  All binary64, every operation named below rounded on its own (nothing fused), quotients and roots
+ * correctly rounded; harness/lag.py states the same in numpy: the sums agree bit for bit, and so does the estimate.
+ * Configuration, fixed at create: pcap, n_joints (the context's), window W in 0 .. MPE_LAG_MAX_WINDOW, sub in 1 ..
+ *   MPE_LAG_MAX_SUB, pose_f64, joint_flags, max_frames (frames per call, at most: the workspace of the per-frame partials).
+ *   The grid has K = 2*W*sub + 1 entries, i = 0 .. K-1:
+ *   k = i - W*sub ; s = floor(k / sub) (towards -inf) ; r = k - s*sub ; alpha = (double)r / (double)sub
+ *   and the lag of entry i is (double)k / (double)sub frames.  Sign: a camera with lag > 0 shows, in its picture of frame f,
+ *   the world at time f + lag.
+ * The table, given at every call (no frame is carried from call to call, which is what makes the sums independent of the
+ *   chunking): d_poses [n_table][pcap][J][3], d_flags, d_n_persons [n_table], d_tid [n_table][pcap], rows as every sequence
+ *   stage reads them.  A call takes a batch -- the detections of the table frames frame_start .. frame_start + n_frames - 1
+ *   --, d_persons [n_frames][pcap][V] for those frames, joint_mask, threshold and huber_px.
+ * Row of a track.  For t >= 0 and a table frame g, the row of (g, t) is the lowest p below the rows of frame g (n_persons
+ *   held within 0 .. pcap) with tid[g][p] == t and, with per-row flags, the flag set; there is none when g is outside
+ *   0 .. n_table - 1.
+ * Observation (f, p, c, j), f a table frame of the call: where mpe_reproject_batch would count d_res[f][p][c][j] given the
+ *   batch, these persons, the table's n_persons and flags of frame f and the same mask and threshold.  It is supported when
+ *   t = tid[f][p] >= 0 and for every g in f-W .. f+W the row of (g, t) exists, joint j of it is flagged and its three
+ *   coordinates are finite (f-W .. f+W is exactly what the grid touches: its last entry has r = 0).  Supported observations
+ *   count in n_support[c], the others in n_unsupported[c]; the support is the same for every k, so the K costs of a camera
+ *   are sums over the same observations.
+ * Term, per supported observation and k:
+ *   X_a = joint j of the row of (f+s, t), widened to f64
+ *   r = 0: X = X_a.  Otherwise X_b = joint j of the row of (f+s+1, t) and X_i = X_a,i + alpha*(X_b,i - X_a,i)
+ *   X projected with camera c of the context (cfg.P, kd, K and the projection lines of mpe_refine_batch)
+ *   if pc_2 > 0 does not hold, or px or py is not finite: n_skipped[c][k] += 1, nothing is summed
+ *   otherwise rx = px - x ; ry = py - y ; e = sqrt(rx*rx + ry*ry) ; the term is rho(e) as for mpe_refine_batch (Huber;
+ *   huber_px = 0: the plain square) and n_obs[c][k] += 1.
+ * Order.  Per frame, S_f[c][k] is the left fold from 0.0 of the terms over p increasing, then j increasing.  A call takes
+ *   cost[c][k] = cost[c][k] + S_f[c][k] for its frames in increasing f -- every frame, whether its partial is zero or not --
+ *   and calls count in the order made: with the same table the sums do not depend on how a recording is cut into batches,
+ *   bit for bit.
+ * mpe_lag_batch: two launches whatever the frame count, ordered on `stream`; neither synchronises nor allocates; n_frames
+ *   == 0 does nothing.  MPE_ERR_INVALID: n_frames other than the batch's, n_joints other than the context's, pcap, pose_f64
+ *   or joint_flags other than the state's, frame_start < 0, frame_start + n_frames > n_table, n_frames > max_frames, a
+ *   negative (or NaN) huber_px, a NULL array.  mpe_lag_create: MPE_ERR_INVALID for a window or sub out of range, pcap < 1,
+ *   max_frames < 1, n_joints other than the context's; MPE_ERR_CAPACITY for pcap > MPE_TRACK_MAX_PERSONS.
+ * mpe_lag_reset zeroes the sums and the counts (stream-ordered memsets).  mpe_lag_read synchronises `stream` and returns
+ *   cost [V][K], n_obs [V][K], n_skipped [V][K], n_support [V], n_unsupported [V] (any may be NULL).
+ * mpe_lag_estimate does the same read, then per camera (csrc/lag_pick.h):
+ *   entry i is valid when n_obs[c][i] >= min_obs (min_obs >= 1, else MPE_ERR_INVALID) ; m_i = cost / (double)n_obs
+ *   no valid entry: MPE_LAG_FEW_OBS, k_best = 0, both lags 0, both costs NaN
+ *   i* = the lowest index of the least m_i among the valid entries (a NaN is never least; with nothing but NaN the lowest
+ *   valid index)
+ *   i* = 0, i* = K-1 or an invalid neighbour: MPE_LAG_EDGE, refined = grid
+ *   otherwise den = (m_{i*-1} - m_{i*}) + (m_{i*+1} - m_{i*}) ; den > 0: off = (0.5*(m_{i*-1} - m_{i*+1})) / den, held within
+ *   -0.5 .. 0.5 ; else, or when off is a NaN, off = 0 and MPE_LAG_FLAT
+ *   k* = i* - W*sub ; lag_grid = (double)k* / (double)sub ; lag_refined = ((double)k* + off) / (double)sub
+ *   cost_best = m_{i*} ; cost_zero = m at k = 0, NaN when that entry is invalid ; n_obs = that of i*.
+ * One state serves one thread and one stream of work at a time. */
+typedef struct mpe_lag_state mpe_lag_state;
+enum {
+    MPE_LAG_FEW_OBS = 1,
+    MPE_LAG_EDGE = 2,
+    MPE_LAG_FLAT = 4
+};
+#define MPE_LAG_MAX_WINDOW 8
+#define MPE_LAG_MAX_SUB 8
+#define MPE_LAG_MAX_GRID (2 * MPE_LAG_MAX_WINDOW * MPE_LAG_MAX_SUB + 1)
+typedef struct {
+    int32_t pcap, n_joints;
+    int32_t window, sub;           /* W and the grid entries per frame                               */
+    int32_t pose_f64;              /* 0: table poses f32; 1: f64                                     */
+    int32_t joint_flags;           /* 0: table flags [n_table][pcap] u8; 1: [n_table][pcap][J]       */
+    int32_t max_frames;            /* frames per mpe_lag_batch, at most                              */
+    int32_t reserved;
+} mpe_lag_config;
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64, joint_flags; /* as the state was made                                          */
+    int32_t frame_start, n_table;  /* the call's frames are frame_start .. + n_frames - 1 of n_table */
+    uint32_t joint_mask;           /* bit j: joint j is observed                                     */
+    float threshold;               /* 0.5, as for mpe_reproject_batch                                */
+    int32_t reserved;
+    double huber_px;               /* pixels, >= 0; 0: the plain square                              */
+    const int32_t *d_persons;      /* [n_frames][pcap][V], of the call's frames                      */
+    const void *d_poses;           /* [n_table][pcap][J][3]                                          */
+    const uint8_t *d_flags;        /* [n_table][pcap] or [n_table][pcap][J]                          */
+    const int32_t *d_n_persons;    /* [n_table]                                                      */
+    const int32_t *d_tid;          /* [n_table][pcap]                                                */
+} mpe_lag_args;
+typedef struct {
+    int32_t status, k_best;        /* MPE_LAG_* bits; k* (signed, in grid steps)                     */
+    double lag_grid, lag_refined;  /* frames                                                         */
+    double cost_best, cost_zero;   /* mean cost per observation, px^2 (Huber: its units)             */
+    int64_t n_obs;                 /* of entry i*                                                    */
+    int64_t n_support, n_unsupported;
+} mpe_lag_cam_report;
+typedef struct {
+    int32_t n_cameras, n_grid;
+    mpe_lag_cam_report cam[MPE_MAX_CAMERAS];
+} mpe_lag_report;
+int mpe_lag_create(mpe_ctx *ctx, const mpe_lag_config *cfg, mpe_lag_state **out);
+int mpe_lag_reset(mpe_ctx *ctx, void *stream, mpe_lag_state *st);
+int mpe_lag_destroy(mpe_ctx *ctx, mpe_lag_state *st);
+int mpe_lag_batch(mpe_ctx *ctx, void *stream, mpe_lag_state *st, const mpe_batch *b, const mpe_lag_args *a);
+int mpe_lag_launches(mpe_ctx *ctx, const mpe_lag_state *st, int64_t *n);
+int mpe_lag_read(mpe_ctx *ctx, void *stream, mpe_lag_state *st, double *cost, int64_t *n_obs, int64_t *n_skipped, int64_t *n_support,
+                 int64_t *n_unsupported);
+int mpe_lag_estimate(mpe_ctx *ctx, void *stream, mpe_lag_state *st, int32_t min_obs, mpe_lag_report *report);
+
 /* Geometric cross-view matching: a score per edge-node (h1,h2) that needs the calibration only -- how closely the
  * back-projected rays of the two 2D skeletons meet in space (the standard multi-view baseline; no GAT, no MLP weights).
  * All binary64, every operation named below rounded on its own (nothing fused), quotients and roots correctly rounded;

@@ -2493,4 +2493,40 @@ int mpe_lag_estimate(mpe_ctx *ctx, void *stream, mpe_lag_state *st, int32_t min_
     return MPE_OK;
 }
 
+// ---- time-aware refinement (refine_timed.hip): mpe_refine_batch's checks, mpe_lag_batch's on the table, and the lags ----
+int mpe_refine_timed_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_refine_timed_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_refine_timed_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_refine_timed_batch", b, a, &run);
+    if (rc) return rc;
+    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "mpe_refine_timed_batch: %d frames over 2^23 per call", a->n_frames);
+    if (a->max_iters < 1 || a->max_iters > MPE_REFINE_MAX_ITERS)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_timed_batch: max_iters %d outside 1..%d", a->max_iters, MPE_REFINE_MAX_ITERS);
+    if (!(a->step_tol >= 0.0) || !(a->huber_px >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_timed_batch: step_tol %g and huber_px %g must not be negative", a->step_tol, a->huber_px);
+    if (a->frame_start < 0 || a->n_table < 0 || (int64_t)a->frame_start + a->n_frames > a->n_table)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_timed_batch: frame_start %d + n_frames %d must lie within the table's %d frames",
+                    a->frame_start, a->n_frames, a->n_table);
+    for (int c = 0; c < ctx->cfg.n_cameras; ++c)
+        if (!(fabs(a->lag[c]) <= (double)MPE_LAG_MAX_WINDOW))          // a NaN fails the comparison, an infinity exceeds it
+            return fail(ctx, MPE_ERR_INVALID, "mpe_refine_timed_batch: lag %g of camera %d must be finite and within %d frames", a->lag[c], c,
+                        MPE_LAG_MAX_WINDOW);
+    if (!run) return MPE_OK;
+    if (!a->d_persons || !a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_tid || !a->d_poses_out || !a->d_status || !a->d_cost0 ||
+        !a->d_cost1 || !a->d_iters || !a->d_n_views || !a->d_n_timed)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_timed_batch: NULL argument");
+    const size_t joint_bytes = (size_t)a->pcap * a->n_joints * 3 * (a->pose_f64 ? sizeof(double) : sizeof(float));
+    const uintptr_t tab0 = reinterpret_cast<uintptr_t>(a->d_poses), tab1 = tab0 + (size_t)a->n_table * joint_bytes;
+    const uintptr_t out0 = reinterpret_cast<uintptr_t>(a->d_poses_out), out1 = out0 + (size_t)a->n_frames * joint_bytes;
+    if (out0 < tab1 && tab0 < out1)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_refine_timed_batch: d_poses_out overlaps the table (other frames read their neighbours from it)");
+    if ((int64_t)a->n_frames * a->pcap > 0x7FFFFFFFLL)             // one workgroup per 1 .. 8 rows, no stride loop
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_refine_timed_batch: %d frames of %d rows are more workgroups than a launch takes", a->n_frames, a->pcap);
+    HIPCHK(ctx, launch_refine_timed(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
+    return MPE_OK;
+}
+
 }  // extern "C"

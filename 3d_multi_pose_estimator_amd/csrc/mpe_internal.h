@@ -468,6 +468,9 @@ hipError_t launch_calib_clear(hipStream_t s, mpe_calib_state *st, int V);
 size_t lag_counter_words(int V, int K);
 hipError_t launch_lag(hipStream_t s, const DevCfg *cfg, mpe_lag_state *st, const mpe_batch &b, const mpe_lag_args &a);
 hipError_t launch_lag_reset(hipStream_t s, mpe_lag_state *st);
+
+// refine_timed.hip
+hipError_t launch_refine_timed(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_refine_timed_args &a);
 // geom.hip: en_pair = the context's pair table (launch_topology); ray_table only when geom_needs_table()
 constexpr size_t GEOM_LDS_BYTES = 48 * 1024;     // head records of a frame staged in LDS up to this (three 256-thread workgroups per CU's 160 KiB)
 bool geom_needs_table(int max_heads_per_frame, int J);

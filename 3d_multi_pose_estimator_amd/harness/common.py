@@ -619,6 +619,35 @@ def evaluate_on_device(work, infer, mode, T_i1, batch=256, device_gt=None, T_d_f
     return metrics, n_data, n_results
 
 
+def add_lags_option(p):
+    """--lags of metrics_from_model and metrics_from_triangulation (harness/lag.py has a --lags of its own) -> p"""
+    p.add_argument('--lags', dest='lags_file', type=str, default=None, metavar='lags.json',
+                   help='needs --track; the file harness.lag --correct N --out wrote.  Where --refine runs, the time-aware refinement runs in '
+                        'its place (mpe_refine_timed_batch with --refine\'s iterations, 10 without, and Huber option): every camera looks at a '
+                        'joint where the joint\'s track says it was at that camera\'s time.  The tracks are those of the --batch chunk, so a '
+                        'chunk\'s first and last ceil(|lag|) frames stay untimed; one further line reports the cameras with a lag, the joints '
+                        'timed and the mean cost before and after')
+    return p
+
+
+def load_lags(path, names):
+    """lags.json as harness.lag --out writes it ({'lags': {camera: frames}}; a bare {camera: frames} or a list over `names`
+    is taken, too) -> [lag of every camera in `names`], 0.0 for a camera the file does not name."""
+    import json
+    with open(path) as fh:
+        doc = json.load(fh)
+    if isinstance(doc, dict) and 'lags' in doc:
+        doc = doc['lags']
+    if isinstance(doc, dict):
+        unknown = [c for c in doc if c not in names]
+        if unknown:
+            raise ValueError('--lags: %s names cameras the rig does not use: %s' % (path, ', '.join(unknown)))
+        return [float(doc.get(c, 0.0)) for c in names]
+    if not isinstance(doc, list) or len(doc) != len(names):
+        raise ValueError('--lags: %s must hold one lag for each of the %d cameras' % (path, len(names)))
+    return [float(x) for x in doc]
+
+
 def max_skeletons_per_camera(work):
     """Largest skeleton list of any camera in the selected frames: sizes the engine's per-frame
     capacity (the reference has no such limit; its graphs simply grow)."""
@@ -656,6 +685,11 @@ def run(args, mode):
             raise ValueError('--relink: %s' % e)
     if smooth or track_score or bones or bones_refine or relink:
         args.track = True
+    lags = None
+    if getattr(args, 'lags_file', None):
+        if not getattr(args, 'track', False):
+            raise ValueError('--lags needs --track: the offsets of a joint come from its track')
+        lags = load_lags(args.lags_file, list(parameters.used_cameras_skeleton_matching))
     if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
         args.device_metrics = True
     src = [] if device_gt else None
@@ -672,7 +706,8 @@ def run(args, mode):
     tracker = summary = smoother = smoothed = gt_tracker = scorer = skeleton = boned = relinker = relinked = None
     last = {}                                                # what the track score of a batch needs from infer_device
     refined = []
-    regrouped = []                                           # --regroup: per round, the counts of every batch
+    timed = []                                               # --lags: the time-aware refinement's outputs of every batch
+    regrouped = []                                         # --regroup: per round, the counts of every batch
     consolidated = []                                        # --merge / --found: the same of the consolidation
     used_mask = sum(1 << int(j) for j in parameters.used_joints)     # the joints both 3D stages of this script fill in
     if getattr(args, 'track', False):
@@ -761,19 +796,29 @@ def run(args, mode):
         persons, n_persons, poses, flags = repair_stage(eng, args, db, persons, n_persons, poses, flags, mode, regrouped, consolidated,
                                                         lambda rows, n: eng.mlp3d(db, rows, n) if mode == 'mlp' else eng.triangulate(db, rows, n),
                                                         used_mask)
-        if refine:
+        tr = None
+        if tracker is not None:
+            # the frames that are evaluated (a cross-camera pair, as Engine.evaluate's skip rule has it), in order
+            keep = torch.from_numpy(np.flatnonzero(np.diff(np.asarray(db.host.frame_en_off[:db.n_frames + 1])) != 0)).to(poses.device)
+        if lags is not None:
+            # --lags: track first (the unrefined poses), then the time-aware refinement against the chunk's own frames as the table;
+            # a frame that is not evaluated is a time step without ids
+            tr = track(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
+            ids = torch.full(tuple(poses.shape[:2]), -1, dtype=torch.int32, device=poses.device).index_copy_(0, keep, tr['ids'])
+            ref = eng.refine_timed(db, 0, persons, poses, flags, n_persons, ids, 'est' if mode == 'mlp' else 'triang', lags,
+                                   max_iters=refine or 10, huber_px=args.refine_huber)
+            poses = ref['poses']
+            timed.append({k: ref[k].cpu().numpy() for k in ('status', 'cost0', 'cost1', 'n_timed')})
+        elif refine:
             ref = eng.refine(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', max_iters=refine,
                              huber_px=args.refine_huber, out=poses)
             refined.append({k: ref[k].cpu().numpy() for k in ('status', 'cost0', 'cost1')})
         torch.cuda.synchronize()
         t2 = time.time()
-        if tracker is not None:
-            # the frames that are evaluated (a cross-camera pair, as Engine.evaluate's skip rule has it), in order
-            keep = torch.from_numpy(np.flatnonzero(np.diff(np.asarray(db.host.frame_en_off[:db.n_frames + 1])) != 0)).to(poses.device)
         if smoother is not None or skeleton is not None:
             # track, then smooth, then bones, then scoring: the fitted poses of the tracked frames take the place of the raw ones
             p_in, f_in, n_in = poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep)
-            tr = track(p_in, f_in, n_in)
+            tr = tr if tr is not None else track(p_in, f_in, n_in)
             p_cur, f_cur = p_in, f_in
             if smoother is not None:
                 sm = smoother.update(p_in, f_in, n_in, tr['ids'])
@@ -805,7 +850,7 @@ def run(args, mode):
             if skeleton is not None:
                 boned.add(p_sk.cpu().numpy(), {k: v.cpu().numpy() for k, v in sk.items()})
         elif tracker is not None:
-            tr = track(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
+            tr = tr if tr is not None else track(poses.index_select(0, keep), flags.index_select(0, keep), n_persons.index_select(0, keep))
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
         if scorer is not None:
             last.update(flags=flags, n_persons=n_persons, ids=tr['ids'])
@@ -867,7 +912,12 @@ def run(args, mode):
         out['regroup'] = report_regroup(args, regrouped)
     if getattr(args, 'merge', 0.0) or getattr(args, 'found', 0.0):
         out['consolidate'] = report_consolidate(args, consolidated)
-    if refine:
+    if lags is not None:
+        from .refine_timed import summary as timed_summary
+        out['refine_timed'] = r = timed_summary(timed, lags)
+        print('Refined in time (%d cameras with a lag, at most %d iterations, Huber %g px): %d joints solved, %d timed, mean cost %.6g -> %.6g px^2'
+              % (r['cameras_lagged'], refine or 10, args.refine_huber, r['solved'], r['joints_timed'], r['mean_cost0'], r['mean_cost1']))
+    elif refine:
         from .refine import summary as refine_summary
         out['refine'] = r = refine_summary(refined)
         print('Refined (at most %d iterations, Huber %g px): %d joints solved, %.1f %% moved, mean cost %.6g -> %.6g px^2'

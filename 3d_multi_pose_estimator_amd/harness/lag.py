@@ -10,7 +10,7 @@ are IEEE doubles), in the header's order.  The observations of a camera are the 
 As a script:
 
     python -m 3d_multi_pose_estimator_amd.harness.lag --testfiles F.json --tmdir DIR --matcher geometric \
-        --window 4 --sub 4 --rounds 3 [--lag-huber PX] [--hold NAME] [--refine ITERS] [--track-gate M --track-gap N] [--out lags.json]
+        --window 4 --sub 4 --rounds 3 [--lag-huber PX] [--hold NAME] [--refine ITERS] [--track-gate M --track-gap N] [--correct N --correct-inner M] [--out lags.json]
 
 A round matches, triangulates, (with --refine) refines and tracks every batch, makes the table from the kept poses and ids on
 the device, takes one pass over the kept batches and estimates.  Per camera it prints the observations supported, the mean
@@ -18,7 +18,12 @@ cost at zero lag and at the best entry as RMS pixels, the grid and the refined l
 default: the common shift of all cameras is not observable from poses the cameras made themselves) and the total integer
 shift applied so far.  The integer parts, rounded relative to the held camera, are then applied with `retime_frames` and the
 recording is packed again; the script stops early when a round applies nothing.  The fractional remainder is relative to
-the poses' own time and biased towards zero: it is reported, not corrected.
+the poses' own time and biased towards zero.  --correct N [--correct-inner M] corrects it in the poses: N times, the lags
+relative to the held camera go to M rounds of the time-aware refinement over all batches (harness/refine_timed.py,
+Engine.refine_timed; the first round reads the round's uncorrected tracked poses, each later one the output of the one
+before), one more pass of the estimator runs against the corrected table, and per camera the lag and the RMS pixels at the
+best entry before and after are printed, with the joints timed.  --out then also holds 'lags': the whole lag of every
+camera (integer shift plus remainder), what --lags of the metrics scripts takes.
 --synthetic N --lags 0,2,-1,0,1 runs on generated frames (bodies on seeded smooth walks, every camera's column projected
 from the bodies at its own time) and also prints the true lags.
 """
@@ -258,6 +263,47 @@ def relative_shifts(lags, hold):
     return [int(math.floor(abs(x) + 0.5)) * (1 if x >= 0 else -1) for x in rel]
 
 
+def correct_rounds(eng, calib, args, names, h, kept, packed, table, rep, estimate):
+    """--correct: N alternations of (the lags relative to the held camera; M rounds of the time-aware refinement over all
+    batches, the first reading the round's uncorrected tracked poses and each later one the output of the one before -- the
+    frames whose neighbours are missing stay as they were, and what they spoil reaches M * ceil(max |lag|) frames at most;
+    one pass of the estimator against the corrected table).  -> one dict per alternation; 'report' is its estimate."""
+    import torch
+
+    from .refine_timed import refine_timed
+    out = []
+    iters = args.refine if args.refine else 10
+    for n in range(args.correct):
+        lags = [float(rep['lag_refined'][c] - rep['lag_refined'][h]) for c in range(len(names))]
+        lags = [max(-float(MAX_WINDOW), min(float(MAX_WINDOW), x)) for x in lags]
+        corrected, timed = table, 0
+        for m in range(max(1, args.correct_inner)):
+            if args.host_statement:
+                host = [t.cpu().numpy() for t in corrected]
+                res = [refine_timed(calib, pb, at, persons.cpu().numpy(), *host, lags, (1 << eng.J) - 1, max_iters=iters, huber_px=args.refine_huber)
+                       for (db, at, persons, _, _, _, _), pb in zip(kept, packed)]
+                poses = torch.from_numpy(np.concatenate([r['poses'] for r in res])).to(table[0].device)
+                timed = int(sum(int((r['n_timed'] > 0).sum()) for r in res))
+            else:
+                res = [eng.refine_timed(db, at, persons, *corrected, 'triang', lags, max_iters=iters, huber_px=args.refine_huber)
+                       for db, at, persons, _, _, _, _ in kept]
+                poses = torch.cat([r['poses'] for r in res])
+                timed = int(sum(int((r['n_timed'] > 0).sum()) for r in res))
+            corrected = [poses.contiguous()] + list(table[1:])
+        after = estimate(kept, packed, corrected)
+        with np.errstate(all='ignore'):
+            rms_b, rms_a = np.sqrt(rep['cost_best']), np.sqrt(after['cost_best'])
+        rel_a = [float(after['lag_refined'][c] - after['lag_refined'][h]) for c in range(len(names))]
+        for c, name in enumerate(names):
+            print('correction %d camera %s: lag %+.4f frames before, %+.4f after; RMS %.4f px at the best entry before, %.4f after%s'
+                  % (n + 1, name, lags[c], rel_a[c], rms_b[c], rms_a[c], ' (status %d)' % after['status'][c] if after['status'][c] else ''))
+        print('correction %d: %d joints timed in the last of %d rounds' % (n + 1, timed, max(1, args.correct_inner)))
+        out.append({'lag_before': lags, 'lag_after': rel_a, 'rms_before': rms_b.tolist(), 'rms_after': rms_a.tolist(), 'joints_timed': timed,
+                    'report': after})
+        rep = after
+    return out
+
+
 def build_own_parser():
     from .common import build_parser
     p = build_parser('Estimate per-camera time lags from the poses of a recording and re-pair the cameras by their integer parts')
@@ -272,6 +318,10 @@ def build_own_parser():
     p.add_argument('--lag-seed', type=int, default=1234, help='--synthetic: the seed of the walks')
     p.add_argument('--weave', type=float, default=0.0, metavar='M', help='--synthetic: the bodies weave sideways by this much, metres')
     p.add_argument('--host-statement', action='store_true', help='take the passes through the numpy statement instead of the device')
+    p.add_argument('--correct', type=int, default=0, metavar='N', help='after the integer rounds: N alternations of the time-aware refinement '
+                   '(the sub-frame lags corrected in the poses) with the estimate (0: the lags are reported only)')
+    p.add_argument('--correct-inner', type=int, default=2, metavar='M', help='--correct: rounds of the time-aware refinement per alternation, '
+                   'each reading its offsets from the poses of the one before')
     return p
 
 
@@ -315,7 +365,9 @@ def run(args):
         report['true_lags'] = true_lags
         print('true lags (frames): ' + ', '.join('%s %+g' % (n, x) for n, x in zip(names, true_lags)))
     current = frames
-    for rnd in range(max(1, args.rounds)):
+
+    def stage(current):
+        """match, triangulate, (refine,) track every batch -> the kept batches, the packed ones and the table."""
         kept, packed = [], []
         tracker.reset()
         for at in range(0, len(current), args.batch):
@@ -331,17 +383,25 @@ def run(args):
             packed.append(pb)
         eng.sync_status()
         table = [torch.cat([b[i] for b in kept]).contiguous() for i in (4, 5, 3, 6)]          # poses, flags, n_persons, ids
+        return kept, packed, table
+
+    def estimate(kept, packed, table):
+        """one pass over the kept batches against `table` and the estimate"""
         if args.host_statement:
             sums = None
             host = [t.cpu().numpy() for t in table]
             for (db, at, persons, _, _, _, _), pb in zip(kept, packed):
                 sums = lag_pass_host(calib, pb, at, persons.cpu().numpy(), *host, args.window, args.sub, args.lag_huber, sums=sums)
-            rep = lag_estimate_host(sums, args.window, args.sub, args.min_obs)
-        else:
-            est.reset()
-            for db, at, persons, _, _, _, _ in kept:
-                est.accumulate(db, at, persons, *table)
-            rep = est.estimate(args.min_obs)
+            return lag_estimate_host(sums, args.window, args.sub, args.min_obs)
+        est.reset()
+        for db, at, persons, _, _, _, _ in kept:
+            est.accumulate(db, at, persons, *table)
+        return est.estimate(args.min_obs)
+
+    settled = False
+    for rnd in range(max(1, args.rounds)):
+        kept, packed, table = stage(current)
+        rep = estimate(kept, packed, table)
         shifts = relative_shifts(rep['lag_refined'], h)
         total = [a + b for a, b in zip(total, shifts)]
         with np.errstate(all='ignore'):
@@ -355,12 +415,23 @@ def run(args):
                                  'n_support': rep['n_support'].tolist(), 'rms_zero': rms0.tolist(), 'rms_best': rms1.tolist(),
                                  'applied': shifts, 'total_shift': list(total)})
         if not any(shifts):
+            settled = True
             break
         current = retime_frames(frames, names, total)
+    if args.correct > 0:
+        if not settled:                                      # the last round shifted the cameras: the poses of the recording as it now stands
+            kept, packed, table = stage(current)
+            rep = estimate(kept, packed, table)
+        report['correct'] = correct_rounds(eng, calib, args, names, h, kept, packed, table, rep, estimate)
+        rep = report['correct'][-1]['report']
+        for r in report['correct']:
+            del r['report']
     est.close()
     tracker.close()
     eng.close()
     report['total_shift'] = list(total)
+    if args.correct > 0:                                     # what --lags of the metrics scripts takes: the whole lag of every camera, frames
+        report['lags'] = {n: float(total[c] + (rep['lag_refined'][c] - rep['lag_refined'][h])) for c, n in enumerate(names)}
     print('integer shifts relative to %s: ' % hold + ', '.join('%s %+d' % (n, s) for n, s in zip(names, total)))
     if args.out:
         with open(args.out, 'w') as fh:

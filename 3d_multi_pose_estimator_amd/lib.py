@@ -228,6 +228,17 @@ class mpe_lag_report(C.Structure):
     _fields_ = [('n_cameras', C.c_int32), ('n_grid', C.c_int32), ('cam', mpe_lag_cam_report * MPE_MAX_CAMERAS)]
 
 
+class mpe_refine_timed_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('frame_start', C.c_int32), ('n_table', C.c_int32), ('joint_mask', C.c_uint32),
+                ('threshold', C.c_float), ('max_iters', C.c_int32), ('step_tol', C.c_double), ('huber_px', C.c_double),
+                ('lag', C.c_double * MPE_MAX_CAMERAS),
+                ('d_persons', C.c_void_p), ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p),
+                ('d_tid', C.c_void_p),
+                ('d_poses_out', C.c_void_p), ('d_status', C.c_void_p), ('d_cost0', C.c_void_p), ('d_cost1', C.c_void_p),
+                ('d_iters', C.c_void_p), ('d_n_views', C.c_void_p), ('d_n_timed', C.c_void_p)]
+
+
 class mpe_geom_args(C.Structure):
     _fields_ = [('sigma_m', C.c_double), ('clip_m', C.c_double), ('min_joints', C.c_int32), ('joint_mask', C.c_uint32),
                 ('min_conf', C.c_float), ('d_scores', C.c_void_p), ('d_n_votes', C.c_void_p), ('d_mean', C.c_void_p)]
@@ -315,6 +326,8 @@ MPE_CALIB_SUMS = 28
 # per-camera status bits of mpe_lag_estimate and the caps of mpe_lag_create
 MPE_LAG_FEW_OBS, MPE_LAG_EDGE, MPE_LAG_FLAT = 1, 2, 4
 MPE_LAG_MAX_WINDOW, MPE_LAG_MAX_SUB = 8, 8
+# mpe_refine_timed_batch: the status bits are mpe_refine_batch's, and a lag is within this many frames either way
+MPE_REFINE_TIMED_MAX_LAG = MPE_LAG_MAX_WINDOW
 
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
@@ -416,6 +429,7 @@ SYMBOLS = {
     'mpe_lag_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                C.POINTER(C.c_int64)]),
     'mpe_lag_estimate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(mpe_lag_report)]),
+    'mpe_refine_timed_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_timed_args)]),
     'mpe_geom_scores_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args)]),
     'mpe_geom_match_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_geom_args), C.c_void_p, C.c_void_p]),
     'mpe_residual_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_residual_stats_args)]),

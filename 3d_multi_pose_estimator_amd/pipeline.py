@@ -1162,6 +1162,55 @@ class Engine:
         self._chk(self.lib.mpe_refine_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
         return res
 
+    def refine_timed(self, db, frame_start, persons, table_poses, table_flags, table_n_persons, table_ids, kind, lags, joint_mask=None,
+                     threshold=0.5, max_iters=10, step_tol=1e-6, huber_px=0.0, out=None):
+        """refine with every camera looking at the joint where its track says it was at that camera's time
+        (mpe_refine_timed_batch; include/mpe.h has the rule, harness/refine_timed.py states it in numpy and the two agree
+        bit for bit): what corrects the sub-frame lags LagEstimator.estimate reports.  db holds the detections of the
+        table frames frame_start .. frame_start + db.n_frames - 1, persons [B,pcap,V] i32 their rows; the table (poses,
+        flags, n_persons, ids of the whole sequence, of `kind` 'est' or 'triang' as LagEstimator.accumulate takes them; pcap
+        is the table's) gives the start poses and, through the tracks, the offsets; lags: V floats, frames, with the sign
+        of the lag report.  out: the tensor [B,pcap,J,3] that takes the poses; it must not share storage with table_poses.
+        -> the dict of refine plus n_timed u8 [B,pcap,J] (observing cameras that used an offset); one launch on the
+        current stream.  With every lag 0 the result is refine's on the call's frames of the table, bit for bit."""
+        if kind not in ('est', 'triang'):
+            raise ValueError('kind must be est or triang')
+        tri, B = kind == 'triang', db.n_frames
+        pcap = int(table_poses.shape[1]) if table_poses.dim() == 4 else -1
+        n_table = _check_pose_rows(self.J, pcap, tri, tri, table_poses, table_flags, table_n_persons, table_ids, device=self.device)
+        if persons.dtype != torch.int32 or tuple(persons.shape) != (B, pcap, self.V) or not persons.is_contiguous():
+            raise ValueError('persons must be int32 [%d,%d,%d], contiguous' % (B, pcap, self.V))
+        lags = [float(x) for x in lags]
+        if len(lags) != self.V:
+            raise ValueError('lags must be %d floats, one per camera' % self.V)
+        if joint_mask is None:
+            joint_mask = (1 << self.J) - 1 if tri else sum(1 << j for j in self.params.used_joints)
+        if out is None:
+            out = torch.empty((B, pcap, self.J, 3), dtype=table_poses.dtype, device=self.device)
+        elif out.dtype != table_poses.dtype or tuple(out.shape) != (B, pcap, self.J, 3) or not out.is_contiguous() or out.device != table_poses.device:
+            raise ValueError('out must be a contiguous tensor [%d,%d,%d,3] of the type and device of table_poses' % (B, pcap, self.J))
+        elif out.numel() and out.untyped_storage().data_ptr() == table_poses.untyped_storage().data_ptr():
+            raise ValueError('out must not share storage with table_poses: other frames read their neighbours from the table')
+        shape = (B, pcap, self.J)
+        res = {'poses': out, 'status': torch.empty(shape, dtype=torch.uint8, device=self.device),
+               'cost0': torch.empty(shape, dtype=torch.float64, device=self.device),
+               'cost1': torch.empty(shape, dtype=torch.float64, device=self.device),
+               'iters': torch.empty(shape, dtype=torch.uint8, device=self.device),
+               'n_views': torch.empty(shape, dtype=torch.uint8, device=self.device),
+               'n_timed': torch.empty(shape, dtype=torch.uint8, device=self.device)}
+        a = L.mpe_refine_timed_args()
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, pcap, self.J, int(tri), int(tri)
+        a.frame_start, a.n_table, a.joint_mask, a.threshold = int(frame_start), n_table, int(joint_mask), float(threshold)
+        a.max_iters, a.step_tol, a.huber_px = int(max_iters), float(step_tol), float(huber_px)
+        for c, x in enumerate(lags):
+            a.lag[c] = x
+        a.d_persons, a.d_poses, a.d_flags = persons.data_ptr(), table_poses.data_ptr(), table_flags.data_ptr()
+        a.d_n_persons, a.d_tid = table_n_persons.data_ptr(), table_ids.data_ptr()
+        a.d_poses_out, a.d_status, a.d_cost0, a.d_cost1 = out.data_ptr(), res['status'].data_ptr(), res['cost0'].data_ptr(), res['cost1'].data_ptr()
+        a.d_iters, a.d_n_views, a.d_n_timed = res['iters'].data_ptr(), res['n_views'].data_ptr(), res['n_timed'].data_ptr()
+        self._chk(self.lib.mpe_refine_timed_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return res
+
     def body_refine(self, sk, db, persons, n_persons, poses, flags, ids, sweeps=8, bone_weight=300.0, huber_px=0.0, joint_mask=None,
                     threshold=0.5, frames=None):
         """The body-level fit (mpe_body_refine_batch; include/mpe.h has the rule, harness/skeleton_refine.py states it in

@@ -620,6 +620,68 @@ int mpe_lag_read(mpe_ctx *ctx, void *stream, mpe_lag_state *st, double *cost, in
                  int64_t *n_unsupported);
 int mpe_lag_estimate(mpe_ctx *ctx, void *stream, mpe_lag_state *st, int32_t min_obs, mpe_lag_report *report);
 
+/* Time-aware refinement: mpe_refine_batch with every camera looking at the joint where the joint's track says it was at that
+ * camera's time -- what corrects the sub-frame lags mpe_lag_estimate reports.  A camera that lags by L frames saw, in its
+ * picture of frame f, the world at f + L; the track of the joint in the table gives how far the joint moved between f and
+ * f + L, and camera c projects the unknown point displaced by that much.  The displacements are taken from the table once
+ * and are constants of the call: the problem keeps its three unknowns per joint.  Stateless.  All binary64, every operation
+ * named below rounded on its own (nothing fused); harness/refine_timed.py states the same in numpy, and the two agree bit
+ * for bit.
+ * Inputs: everything mpe_refine_batch takes; the table of mpe_lag_batch, given at every call (d_poses [n_table][pcap][J][3],
+ *   d_flags, d_n_persons [n_table], d_tid [n_table][pcap], frame_start, n_table: the batch holds the detections of the table
+ *   frames frame_start .. frame_start + n_frames - 1 and d_persons [n_frames][pcap][V] their rows); and lag[c], frames,
+ *   c < V, with the sign the lag report has: lag > 0 means camera c's picture of frame f shows the world at f + lag.
+ * Per camera c, with L = lag[c]: s = floor(L) ; alpha = L - (double)s (one subtraction; exact for L >= 0 and for every
+ *   multiple of 2^-k frames within the window; 0 <= alpha <= 1).
+ * Start.  The start point of joint (f, p, j) is joint j of row p of table frame F = frame_start + f.  The observing cameras
+ *   are those of mpe_refine_batch given the batch, d_persons, and the table's n_persons and flags of frame F.
+ * Timed cameras.  With t = tid[F][p] and the row of a track as mpe_lag_batch has it (the lowest row of that id below the
+ *   frame's rows, with per-row flags the flag set; none outside 0 .. n_table - 1), an observing camera with L != 0 is timed
+ *   for joint j when t >= 0 and the rows of (F, t), (F+s, t) and -- when alpha != 0 -- (F+s+1, t) exist and joint j of each
+ *   is flagged (per-joint flags; a per-row flag stands for every joint) and has three finite coordinates.  Then, with X_f,
+ *   X_a, X_b joint j of those rows widened to f64:
+ *   alpha == 0: X_l = X_a.  Otherwise X_l,i = X_a,i + alpha*(X_b,i - X_a,i)                         i = 0..2
+ *   d_c,i = X_l,i - X_f,i
+ *   A camera with L == 0, or one that is not timed (at a track's or the table's ends, say: nothing is extrapolated), has no
+ *   offset.  d_n_timed = the number of observing cameras that are timed, whether the joint is solved or not.
+ * Solve.  Cost, Jacobian, LM step, acceptance, statuses and outputs are those of mpe_refine_batch, except that wherever
+ *   camera c projects a point X (the start, the iterate, the trial) a timed camera projects (X0 + d_c,0, X1 + d_c,1,
+ *   X2 + d_c,2): pc_2 > 0 is tested there and the Jacobian is taken there (the offset is a constant, so it is the
+ *   Jacobian by X).  A camera without offset projects X itself, with no addition: with every lag 0 the seven shared
+ *   outputs are the bits of mpe_refine_batch given the call's frames of the table.
+ * The offsets come from the input table, never from d_poses_out, so the result does not depend on how a recording is cut
+ *   into calls.  d_poses_out is [n_frames][pcap][J][3] and must not overlap the table (other frames' workgroups read their
+ *   neighbours from it).
+ * One launch, ordered on `stream`; neither synchronises nor allocates; n_frames == 0 does nothing.  MPE_ERR_INVALID for
+ *   what mpe_refine_batch and mpe_lag_batch refuse on the arguments they share (max_iters, step_tol, huber_px, n_frames
+ *   other than the batch's, n_joints other than the context's, frame_start < 0, frame_start + n_frames > n_table, a NULL
+ *   array), for a lag[c], c < V, that is not finite or exceeds MPE_LAG_MAX_WINDOW in magnitude, and for a d_poses_out whose
+ *   bytes overlap the table's poses; MPE_ERR_CAPACITY for more than 2^23 frames.
+ * Not done here: the DLT and the MLP stay untimed, as do mpe_calib_* and mpe_body_refine_batch; velocity is not an unknown;
+ *   no offset is extrapolated beyond a track's ends; wire timestamps are not read. */
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64, joint_flags; /* of the table: 0 / 1 as for mpe_lag_batch                       */
+    int32_t frame_start, n_table;  /* the call's frames are frame_start .. + n_frames - 1 of n_table */
+    uint32_t joint_mask;           /* bit j: joint j is refined                                      */
+    float threshold;               /* 0.5, as for mpe_reproject_batch                                */
+    int32_t max_iters;             /* 1 .. MPE_REFINE_MAX_ITERS                                      */
+    double step_tol;               /* metres, >= 0                                                   */
+    double huber_px;               /* pixels, >= 0; 0: plain least squares                           */
+    double lag[MPE_MAX_CAMERAS];   /* frames, by camera slot; |lag| <= MPE_LAG_MAX_WINDOW            */
+    const int32_t *d_persons;      /* [n_frames][pcap][V], of the call's frames                      */
+    const void *d_poses;           /* [n_table][pcap][J][3]                                          */
+    const uint8_t *d_flags;        /* [n_table][pcap] or [n_table][pcap][J]                          */
+    const int32_t *d_n_persons;    /* [n_table]                                                      */
+    const int32_t *d_tid;          /* [n_table][pcap]                                                */
+    void *d_poses_out;             /* [n_frames][pcap][J][3], the type of d_poses                    */
+    uint8_t *d_status;             /* [n_frames][pcap][J]                                            */
+    double *d_cost0, *d_cost1;     /* [n_frames][pcap][J]                                            */
+    uint8_t *d_iters, *d_n_views;  /* [n_frames][pcap][J]                                            */
+    uint8_t *d_n_timed;            /* [n_frames][pcap][J]                                            */
+} mpe_refine_timed_args;
+int mpe_refine_timed_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_refine_timed_args *a);
+
 /* Geometric cross-view matching: a score per edge-node (h1,h2) that needs the calibration only -- how closely the
  * back-projected rays of the two 2D skeletons meet in space (the standard multi-view baseline; no GAT, no MLP weights).
  * All binary64, every operation named below rounded on its own (nothing fused), quotients and roots correctly rounded;

@@ -93,6 +93,22 @@ def load_transform_manager(path):
     return tm
 
 
+def load_intrinsics(path, params=None):
+    """The "intrinsics" list of a ``tm_*.json`` that harness.camfit wrote -> (k [n,4] float32, dist [n,5] float64) in the
+    order of ``params.camera_names`` (default: the package's parameters), what Calibration takes as `intrinsics`; None
+    when the file has no such list."""
+    if params is None:
+        from .parameters import parameters as params
+    with open(path) as fh:
+        doc = json.load(fh)
+    if 'intrinsics' not in doc:
+        return None
+    by_name = {e['camera']: e for e in doc['intrinsics']}
+    k = np.array([[float.fromhex(by_name[c][key]) for key in ('fx', 'fy', 'cx', 'cy')] for c in params.camera_names], np.float32)
+    dist = np.array([[float.fromhex(x) for x in by_name[c]['dist']] for c in params.camera_names], np.float64)
+    return k, dist
+
+
 def default_transform_path(params):
     """Resolve ``parameters.transformations_path`` the way the reference does (cwd
     relative), falling back to the calibration shipped with this package."""
@@ -114,11 +130,21 @@ class Calibration:
     """All per-camera constants of the path, indexed by position in
     ``params.camera_names`` (== ``used_cameras`` for the shipped presets)."""
 
-    def __init__(self, params, tm=None):
+    def __init__(self, params, tm=None, intrinsics=None):
+        """intrinsics: None (the numbers of `params`), or (k [n,4]: fx fy cx cy, dist [n,5]) in the order of
+        ``params.camera_names``: K32 is built from the four numbers rounded to float32, dist is taken as given."""
         if tm is None:
             tm = load_transform_manager(default_transform_path(params))
         self.params = params
         self.tm = tm
+        if intrinsics is not None:
+            k, dist = intrinsics
+            k, dist = np.array(k, np.float32), np.array(dist, np.float64)
+            if k.shape != (len(params.camera_names), 4) or dist.shape != (len(params.camera_names), 5) or \
+                    not (np.isfinite(k).all() and np.isfinite(dist).all() and (k[:, :2] > 0).all()):
+                raise ValueError('intrinsics must be finite k [%d,4] with fx, fy > 0 and dist [%d,5]' % ((len(params.camera_names),) * 2))
+            intrinsics = (k, dist)
+        self._intrinsics = intrinsics
         names = list(params.camera_names)
         self.names = names
         n = len(names)
@@ -135,12 +161,16 @@ class Calibration:
             self.T_i[i] = tm.get_transform(cam, 'root')
             ti = torch.from_numpy(self.T_i[i]).type(torch.float32)
             self.T_i32[i] = ti.numpy()
-            k = camera_matrix_f32(params, params.cameras[i])
+            if intrinsics is None:
+                k = camera_matrix_f32(params, params.cameras[i])
+            else:
+                fx, fy, cx, cy = (float(x) for x in intrinsics[0][i])
+                k = torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
             self.K32[i] = k.numpy()
             self.Kinv32[i] = torch.inverse(k).numpy()
             self.centre32[i] = torch.matmul(ti, torch.tensor([0.0, 0.0, 0.0, 1.0])).numpy()
             ci = params.cameras[i]
-            self.dist[i] = [params.kd0[ci], params.kd1[ci], params.p1[ci], params.p2[ci], params.kd2[ci]]
+            self.dist[i] = [params.kd0[ci], params.kd1[ci], params.p1[ci], params.p2[ci], params.kd2[ci]] if intrinsics is None else intrinsics[1][i]
             self.P[i] = self.T_d[i][0:3, :]
 
     @property
@@ -163,4 +193,14 @@ class Calibration:
             T = np.eye(4)
             T[:3, :] = E[i][:3, :]
             tm.add_transform('root', cam, T)
-        return Calibration(self.params, tm)
+        return Calibration(self.params, tm, self._intrinsics)
+
+    def intrinsics(self):
+        """-> k [n,4] float32: fx, fy, cx, cy of every camera, read out of K32."""
+        return np.ascontiguousarray(np.stack([self.K32[:, 0, 0], self.K32[:, 1, 1], self.K32[:, 0, 2], self.K32[:, 1, 2]], axis=1), np.float32)
+
+    def with_intrinsics(self, k, dist):
+        """A new Calibration with K32 rebuilt from k [n,4] (fx, fy, cx, cy, rounded to float32), Kinv32 by torch.inverse as
+        __init__ does it, and dist [n,5] in the place of the stored one, in the order of ``names``; the extrinsics are
+        kept, ``params`` is untouched and this object is not modified."""
+        return Calibration(self.params, self.tm, (k, dist))

@@ -2351,6 +2351,235 @@ int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_ca
 
 }  // extern "C"
 
+// ---- camera fit (camfit.hip sums on the device; the step below is host work, once per pass) ----
+#include "camfit_solve.h"
+
+struct mpe_camfit_host {
+    camfit_cam cam[MPE_MAX_CAMERAS];
+    double cams[MPE_MAX_CAMERAS * CAMFIT_CAM];  // staging of the trial set for the copy to the device
+    double sums[MPE_MAX_CAMERAS * MPE_CAMFIT_SUMS];
+    int64_t n_obs[MPE_MAX_CAMERAS], n_skipped[MPE_MAX_CAMERAS];
+};
+
+namespace {
+
+// the trial sets to the staging buffer and from there to the device
+int camfit_upload(mpe_ctx *ctx, hipStream_t s, mpe_camfit_state *st) {
+    mpe_camfit_host *h = st->host;
+    for (int c = 0; c < st->V; ++c) {
+        double *d = h->cams + (size_t)c * CAMFIT_CAM;
+        const camfit_set &t = h->cam[c].t;
+        std::memcpy(d, t.E, sizeof t.E);
+        std::memcpy(d + 12, t.dist, sizeof t.dist);
+        for (int i = 0; i < 4; ++i) d[17 + i] = (double)t.k[i];
+    }
+    HIPCHK(ctx, hipMemcpyAsync(st->cams, h->cams, (size_t)st->V * CAMFIT_CAM * sizeof(double), hipMemcpyHostToDevice, s));
+    return MPE_OK;
+}
+
+// accepted = trial = (E, k, dist) for every camera, the sums zeroed, the trial set on the device
+int camfit_start(mpe_ctx *ctx, hipStream_t s, mpe_camfit_state *st, const double *E, const float *k, const double *dist) {
+    for (int c = 0; c < st->V; ++c) camfit_cam_start(&st->host->cam[c], E + 12 * c, k + 4 * c, dist + 5 * c);
+    int rc = camfit_upload(ctx, s, st);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_camfit_clear(s, st, st->V));
+    HIPCHK(ctx, hipStreamSynchronize(s));            // the staging buffer is the state's own: the next call may rewrite it
+    return MPE_OK;
+}
+
+// the context's own cameras: cfg.P, (fx, fy, cx, cy) of cfg.K, cfg.dist.  A K of another form than
+// [[fx,0,cx],[0,fy,cy],[0,0,1]] is refused.
+int camfit_start_own(mpe_ctx *ctx, const char *who, hipStream_t s, mpe_camfit_state *st) {
+    float k[MPE_MAX_CAMERAS * 4];
+    for (int c = 0; c < st->V; ++c) {
+        const float *K = ctx->hcfg.K[c];
+        if (K[1] != 0.0f || K[3] != 0.0f || K[6] != 0.0f || K[7] != 0.0f || K[8] != 1.0f)
+            return fail(ctx, MPE_ERR_INVALID, "%s: K of camera %d is not [[fx,0,cx],[0,fy,cy],[0,0,1]]", who, c);
+        k[4 * c] = K[0], k[4 * c + 1] = K[4], k[4 * c + 2] = K[2], k[4 * c + 3] = K[5];
+    }
+    return camfit_start(ctx, s, st, &ctx->hcfg.P[0][0], k, &ctx->hcfg.dist[0][0]);
+}
+
+int camfit_fetch(mpe_ctx *ctx, hipStream_t s, mpe_camfit_state *st) {
+    mpe_camfit_host *h = st->host;
+    HIPCHK(ctx, hipMemcpyAsync(h->sums, st->acc, (size_t)st->V * MPE_CAMFIT_SUMS * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h->n_obs, st->n_obs, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h->n_skipped, st->n_skipped, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return MPE_OK;
+}
+
+void camfit_copy_out(const camfit_set &from, int c, double *E, float *k, double *dist) {
+    if (E) std::memcpy(E + 12 * c, from.E, sizeof from.E);
+    if (k) std::memcpy(k + 4 * c, from.k, sizeof from.k);
+    if (dist) std::memcpy(dist + 5 * c, from.dist, sizeof from.dist);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpe_camfit_destroy(mpe_ctx *ctx, mpe_camfit_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_destroy: NULL state");
+    DeviceGuard dg(ctx);
+    dev_free(ctx, st->cams);
+    dev_free(ctx, st->acc);
+    dev_free(ctx, st->n_obs);
+    dev_free(ctx, st->n_skipped);
+    dev_free(ctx, st->S);
+    delete st->host;
+    delete st;
+    return MPE_OK;
+}
+
+int mpe_camfit_create(mpe_ctx *ctx, mpe_camfit_state **out) {
+    return create_state(ctx, "mpe_camfit_create", out, mpe_camfit_destroy, [&](mpe_camfit_state *st) {
+        st->host = new (std::nothrow) mpe_camfit_host();
+        if (!st->host) return fail(ctx, MPE_ERR_NOMEM, "mpe_camfit_create: out of memory");
+        st->V = ctx->cfg.n_cameras;
+        st->max_frames = ctx->cfg.max_frames;
+        for (int c = 0; c < st->V; ++c) {            // the form of K, before anything is allocated on the device
+            const float *K = ctx->hcfg.K[c];
+            if (K[1] != 0.0f || K[3] != 0.0f || K[6] != 0.0f || K[7] != 0.0f || K[8] != 1.0f)
+                return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_create: K of camera %d is not [[fx,0,cx],[0,fy,cy],[0,0,1]]", c);
+        }
+        int rc = dev_alloc(ctx, &st->cams, (size_t)st->V * CAMFIT_CAM);
+        if (!rc) rc = dev_alloc(ctx, &st->acc, (size_t)st->V * MPE_CAMFIT_SUMS);
+        if (!rc) rc = dev_alloc(ctx, &st->n_obs, st->V);
+        if (!rc) rc = dev_alloc(ctx, &st->n_skipped, st->V);
+        if (!rc) rc = dev_alloc(ctx, &st->S, camfit_workspace_doubles(st->max_frames, st->V), false);
+        if (!rc) rc = camfit_start_own(ctx, "mpe_camfit_create", nullptr, st);
+        return rc;
+    });
+}
+
+int mpe_camfit_reset(mpe_ctx *ctx, void *stream, mpe_camfit_state *st) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_reset: NULL state");
+    DeviceGuard dg(ctx);
+    return camfit_start_own(ctx, "mpe_camfit_reset", static_cast<hipStream_t>(stream), st);
+}
+
+int mpe_camfit_set_cameras(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const double *E, const float *k, const double *dist) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !E || !k || !dist) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_set_cameras: NULL argument");
+    for (int c = 0; c < st->V; ++c) {
+        bool ok = true;
+        for (int i = 0; i < 12; ++i) ok &= calib_finite(E[12 * c + i]) != 0;
+        for (int i = 0; i < 4; ++i) ok &= calib_finite((double)k[4 * c + i]) != 0;
+        for (int i = 0; i < 5; ++i) ok &= calib_finite(dist[5 * c + i]) != 0;
+        if (!ok) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_set_cameras: camera %d has a value that is not finite", c);
+        if (!(k[4 * c] > 0.0f) || !(k[4 * c + 1] > 0.0f))
+            return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_set_cameras: fx %g and fy %g of camera %d must be positive", (double)k[4 * c],
+                        (double)k[4 * c + 1], c);
+    }
+    DeviceGuard dg(ctx);
+    return camfit_start(ctx, static_cast<hipStream_t>(stream), st, E, k, dist);
+}
+
+int mpe_camfit_get_cameras(mpe_ctx *ctx, const mpe_camfit_state *st, double *E_accepted, float *k_accepted, double *dist_accepted,
+                           double *E_trial, float *k_trial, double *dist_trial) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_get_cameras: NULL state");
+    for (int c = 0; c < st->V; ++c) {
+        camfit_copy_out(st->host->cam[c].a, c, E_accepted, k_accepted, dist_accepted);
+        camfit_copy_out(st->host->cam[c].t, c, E_trial, k_trial, dist_trial);
+    }
+    return MPE_OK;
+}
+
+int mpe_camfit_launches(mpe_ctx *ctx, const mpe_camfit_state *st, int64_t *n) { return state_launches(ctx, "mpe_camfit_launches", st, n); }
+
+int mpe_camfit_batch(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const mpe_batch *b, const mpe_calib_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_camfit_batch", b, a, &run);
+    if (rc) return rc;
+    if (!(a->huber_px >= 0.0)) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: huber_px %g must not be negative", a->huber_px);
+    if (st->V != ctx->cfg.n_cameras || b->n_frames > st->max_frames)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: the state belongs to another context");
+    if (!run) return MPE_OK;
+    if (row_inputs_missing(a)) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: NULL argument");
+    HIPCHK(ctx, launch_camfit(static_cast<hipStream_t>(stream), st->V, st, *b, *a));
+    return MPE_OK;
+}
+
+int mpe_camfit_read(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, double *sums, int64_t *n_obs, int64_t *n_skipped) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_read: NULL state");
+    DeviceGuard dg(ctx);
+    int rc = camfit_fetch(ctx, static_cast<hipStream_t>(stream), st);
+    if (rc) return rc;
+    if (sums) std::memcpy(sums, st->host->sums, (size_t)st->V * MPE_CAMFIT_SUMS * sizeof(double));
+    if (n_obs) std::memcpy(n_obs, st->host->n_obs, (size_t)st->V * sizeof(int64_t));
+    if (n_skipped) std::memcpy(n_skipped, st->host->n_skipped, (size_t)st->V * sizeof(int64_t));
+    return MPE_OK;
+}
+
+int mpe_camfit_step(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const mpe_camfit_step_args *a, mpe_camfit_report *report) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_step: NULL argument");
+    if (a->free_mask == 0 || (a->free_mask & ~(uint32_t)CAMFIT_ALL))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_step: free_mask 0x%x must name at least one of the six groups and nothing else", a->free_mask);
+    int idx[CAMFIT_N];
+    const int n_free = camfit_free(a->free_mask, idx);
+    if (a->min_obs < 6 || a->min_obs < n_free)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_step: min_obs %lld is below %d, the larger of 6 and the free unknowns of a camera",
+                    (long long)a->min_obs, n_free > 6 ? n_free : 6);
+    if (!(a->rot_tol >= 0.0) || !(a->trans_tol >= 0.0) || !(a->pix_tol >= 0.0) || !(a->lens_tol >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_step: rot_tol %g, trans_tol %g, pix_tol %g and lens_tol %g must not be negative", a->rot_tol,
+                    a->trans_tol, a->pix_tol, a->lens_tol);
+    DeviceGuard dg(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    mpe_camfit_host *h = st->host;
+    int rc = camfit_fetch(ctx, s, st);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_camfit_clear(s, st, st->V));
+    for (int c = 0; c < st->V; ++c)
+        if (h->cam[c].passes > 0 && h->n_obs[c] != h->cam[c].n_obs) {
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_step: the passes did not see the same data (camera %d: %lld observations, %lld in the first pass)",
+                        c, (long long)h->n_obs[c], (long long)h->cam[c].n_obs);
+        }
+    const camfit_rule rule{a->rot_tol, a->trans_tol, a->pix_tol, a->lens_tol, (long long)a->min_obs, a->free_mask};
+    int all_done = 1;
+    for (int c = 0; c < st->V; ++c) {
+        camfit_cam_step(&h->cam[c], h->sums + (size_t)c * MPE_CAMFIT_SUMS, h->n_obs[c], (a->hold_mask >> c) & 1u, &rule);
+        all_done &= camfit_cam_done(&h->cam[c]);
+    }
+    rc = camfit_upload(ctx, s, st);
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (report) {
+        std::memset(report, 0, sizeof *report);
+        report->n_cameras = st->V;
+        report->all_done = all_done;
+        for (int c = 0; c < st->V; ++c) {
+            const camfit_cam &cam = h->cam[c];
+            mpe_camfit_cam_report &r = report->cam[c];
+            r.status = cam.status;
+            r.passes = cam.passes;
+            r.n_obs = h->n_obs[c];
+            r.n_skipped = h->n_skipped[c];
+            r.cost_start = cam.cost_start;
+            r.cost = cam.Aa[CAMFIT_C];
+            r.lambda = cam.lambda;
+            r.last_rot = cam.last_rot;
+            r.last_trans = cam.last_trans;
+            r.last_pix = cam.last_pix;
+            r.last_lens = cam.last_lens;
+            std::memcpy(r.delta, cam.delta, sizeof r.delta);
+        }
+    }
+    return MPE_OK;
+}
+
+}  // extern "C"
+
 // ---- time lags (lag.hip sums on the device; the pick below is host work, once per pass) ----
 #include "lag_pick.h"
 

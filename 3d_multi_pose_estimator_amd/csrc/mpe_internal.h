@@ -273,6 +273,20 @@ struct mpe_calib_state {
     mpe_calib_host *host = nullptr;
 };
 
+// camfit.hip: what mpe_camfit_batch accumulates and mpe_camfit_step reads.  The Levenberg-Marquardt state of the cameras lives
+// on the host (api.hip, csrc/camfit_solve.h).
+constexpr int CAMFIT_CAM = 21;      // doubles of a trial camera on the device: E [12], dist [5], (fx, fy, cx, cy) widened (exact)
+struct mpe_camfit_host;
+struct mpe_camfit_state {
+    int V = 0, max_frames = 0;
+    int64_t launches = 0;           // kernels enqueued since mpe_camfit_create
+    double *cams = nullptr;         // [V][CAMFIT_CAM] the trial set
+    double *acc = nullptr;          // [V][MPE_CAMFIT_SUMS] sums of the pass so far
+    unsigned long long *n_obs = nullptr, *n_skipped = nullptr;   // [V]
+    double *S = nullptr;            // scratch [max_frames][V][MPE_CAMFIT_SUMS]: the per-frame partials of a call
+    mpe_camfit_host *host = nullptr;
+};
+
 // lag.hip: what mpe_lag_batch accumulates and mpe_lag_read / mpe_lag_estimate read.  The pick of the least entry is host
 // work (api.hip, csrc/lag_pick.h).
 struct mpe_lag_state {
@@ -464,6 +478,10 @@ hipError_t launch_consolidate(hipStream_t s, const DevCfg *cfg, int V, int hmax,
 size_t calib_workspace_doubles(int max_frames, int V);
 hipError_t launch_calib(hipStream_t s, const DevCfg *cfg, int V, mpe_calib_state *st, const mpe_batch &b, const mpe_calib_args &a);
 hipError_t launch_calib_clear(hipStream_t s, mpe_calib_state *st, int V);
+// camfit.hip
+size_t camfit_workspace_doubles(int max_frames, int V);
+hipError_t launch_camfit(hipStream_t s, int V, mpe_camfit_state *st, const mpe_batch &b, const mpe_calib_args &a);
+hipError_t launch_camfit_clear(hipStream_t s, mpe_camfit_state *st, int V);
 // lag.hip
 size_t lag_counter_words(int V, int K);
 hipError_t launch_lag(hipStream_t s, const DevCfg *cfg, mpe_lag_state *st, const mpe_batch &b, const mpe_lag_args &a);

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import synthetic
-from ..calibration import Calibration, load_transform_manager
+from ..calibration import Calibration, load_intrinsics, load_transform_manager
 from ..lib import MPE_EVAL_NO_ASSIGNMENT, MPE_EVAL_OVER_BUDGET, MPE_EVAL_OVER_CAP, MPE_EVAL_SKIPPED
 from ..parameters import parameters
 from ..pipeline import Engine
@@ -41,6 +41,9 @@ def build_parser(description):
                    help="Directory that contains the models' files")
     p.add_argument('--datastep', type=int, nargs='?', required=False, default=12, help='Data step used to compute the metrics')
     p.add_argument('--batch', type=int, default=256, help='frames per device batch')
+    p.add_argument('--cameras', type=str, default=None, metavar='cams.json',
+                   help='start from this camera file (harness.camfit --out, or a tm_*.json): its transforms, and its "intrinsics" list when it has '
+                        'one, in the place of the packaged calibration')
     p.add_argument('--synthetic', type=int, default=0, help='generate this many synthetic Panoptic-shaped frames instead of --testfiles')
     p.add_argument('--random-weights', action='store_true', help='deterministic hash-initialised weights (no checkpoint offline)')
     p.add_argument('--teacher-scores', action='store_true',
@@ -250,6 +253,15 @@ def load_models(eng, args, need_mlp):
     if need_mlp:
         saved = torch.load(mdir + 'pose_estimator.pytorch', map_location='cpu')
         eng.load_mlp(saved['model_state_dict'])
+
+
+def start_calibration(args):
+    """The calibration a script starts from: the packaged one, or with --cameras the transforms of that file and, when
+    the file has an "intrinsics" list (harness.camfit --out), its fx, fy, cx, cy and lens terms."""
+    path = getattr(args, 'cameras', None)
+    if not path:
+        return Calibration(parameters)
+    return Calibration(parameters, load_transform_manager(path), load_intrinsics(path, parameters))
 
 
 def dataset_transform(tm_dir, file_name):
@@ -659,7 +671,7 @@ def max_skeletons_per_camera(work):
 
 
 def run(args, mode):
-    calib = Calibration(parameters)
+    calib = start_calibration(args)
     device_gt = getattr(args, 'device_gt', False) and not args.synthetic       # synthetic frames have no file to parse
     refine = int(getattr(args, 'refine', 0) or 0)
     smooth = int(getattr(args, 'smooth', 0) or 0)

@@ -46,8 +46,7 @@ def project(calib, cam_idx, p3d):
     pc = (T @ np.append(p3d.astype(np.float32), np.float32(1.0)))[:3]
     h = pc / pc[2]
     r = np.float32(h[0] * h[0] + h[1] * h[1])
-    ci = calib.params.cameras[cam_idx]
-    kd = np.array([calib.params.kd0[ci], calib.params.kd1[ci], calib.params.kd2[ci]], np.float32)
+    kd = np.asarray(calib.dist[cam_idx], np.float64)[[0, 1, 4]].astype(np.float32)     # the calibration's own, which a fitted one replaces
     f = np.float32(1) + kd[0] * r + kd[1] * r * r + kd[2] * r * r * r
     d = np.array([h[0] * f, h[1] * f, np.float32(1.0)], np.float32)
     px = calib.K32[cam_idx] @ d

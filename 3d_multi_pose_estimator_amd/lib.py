@@ -205,6 +205,21 @@ class mpe_calib_report(C.Structure):
     _fields_ = [('n_cameras', C.c_int32), ('all_done', C.c_int32), ('cam', mpe_calib_cam_report * MPE_MAX_CAMERAS)]
 
 
+class mpe_camfit_step_args(C.Structure):
+    _fields_ = [('rot_tol', C.c_double), ('trans_tol', C.c_double), ('pix_tol', C.c_double), ('lens_tol', C.c_double),
+                ('min_obs', C.c_int64), ('hold_mask', C.c_uint32), ('free_mask', C.c_uint32)]
+
+
+class mpe_camfit_cam_report(C.Structure):
+    _fields_ = [('status', C.c_int32), ('passes', C.c_int32), ('n_obs', C.c_int64), ('n_skipped', C.c_int64),
+                ('cost_start', C.c_double), ('cost', C.c_double), ('lambda_', C.c_double), ('last_rot', C.c_double),
+                ('last_trans', C.c_double), ('last_pix', C.c_double), ('last_lens', C.c_double), ('delta', C.c_double * 13)]
+
+
+class mpe_camfit_report(C.Structure):
+    _fields_ = [('n_cameras', C.c_int32), ('all_done', C.c_int32), ('cam', mpe_camfit_cam_report * MPE_MAX_CAMERAS)]
+
+
 class mpe_lag_config(C.Structure):
     _fields_ = [('pcap', C.c_int32), ('n_joints', C.c_int32), ('window', C.c_int32), ('sub', C.c_int32), ('pose_f64', C.c_int32),
                 ('joint_flags', C.c_int32), ('max_frames', C.c_int32), ('reserved', C.c_int32)]
@@ -323,6 +338,12 @@ MPE_CONSOLIDATE_RAY_DOUBLES = 3520
 MPE_CALIB_HELD, MPE_CALIB_FEW_OBS, MPE_CALIB_CONVERGED, MPE_CALIB_STALLED, MPE_CALIB_ACCEPTED, MPE_CALIB_REJECTED = 1, 2, 4, 8, 16, 32
 MPE_CALIB_SUMS = 28
 
+# the groups of unknowns of mpe_camfit_step (free_mask), by name, and the sums a camera accumulates
+MPE_CAMFIT_POSE, MPE_CAMFIT_FOCAL, MPE_CAMFIT_CENTRE, MPE_CAMFIT_K1, MPE_CAMFIT_K2, MPE_CAMFIT_K3 = 1, 2, 4, 8, 16, 32
+MPE_CAMFIT_GROUPS = {'pose': 1, 'focal': 2, 'centre': 4, 'k1': 8, 'k2': 16, 'k3': 32}
+MPE_CAMFIT_UNKNOWNS = 13
+MPE_CAMFIT_SUMS = 105
+
 # per-camera status bits of mpe_lag_estimate and the caps of mpe_lag_create
 MPE_LAG_FEW_OBS, MPE_LAG_EDGE, MPE_LAG_FLAT = 1, 2, 4
 MPE_LAG_MAX_WINDOW, MPE_LAG_MAX_SUB = 8, 8
@@ -421,6 +442,15 @@ SYMBOLS = {
     'mpe_calib_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'mpe_calib_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_calib_step_args), C.POINTER(mpe_calib_report)]),
     'mpe_calib_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'mpe_camfit_create': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    'mpe_camfit_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'mpe_camfit_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mpe_camfit_set_cameras': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, c_f32p, c_f64p]),
+    'mpe_camfit_get_cameras': (C.c_int, [C.c_void_p, C.c_void_p, c_f64p, c_f32p, c_f64p, c_f64p, c_f32p, c_f64p]),
+    'mpe_camfit_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_calib_args)]),
+    'mpe_camfit_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'mpe_camfit_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mpe_camfit_step_args), C.POINTER(mpe_camfit_report)]),
+    'mpe_camfit_launches': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'mpe_lag_create': (C.c_int, [C.c_void_p, C.POINTER(mpe_lag_config), C.POINTER(C.c_void_p)]),
     'mpe_lag_reset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_lag_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),

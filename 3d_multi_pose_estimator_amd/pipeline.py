@@ -1346,6 +1346,15 @@ class Engine:
         calibration is never modified: Calibrator.calibration() gives the one to build the next engine from."""
         return Calibrator(self, kind, huber_px, min_obs, hold)
 
+    def camera_fitter(self, kind, free=('pose', 'focal', 'centre', 'k1', 'k2', 'k3'), huber_px=0.0, min_obs=50, hold=()):
+        """A CameraFitter for poses of `kind` ('est' or 'triang'): the calibrator with seven more unknowns per camera --
+        fx, fy, cx, cy and the radial lens terms kd0, kd1, kd2 fitted together with the extrinsics from a recording's own
+        poses (mpe_camfit_*; include/mpe.h has the rule, harness/camfit.py states it in numpy).  free: the groups that
+        are unknowns; the others keep their values.  min_obs is at least the larger of 6 and the number of free unknowns.
+        This engine's own calibration is never modified: CameraFitter.calibration() gives the one to build the next
+        engine from."""
+        return CameraFitter(self, kind, free, huber_px, min_obs, hold)
+
     def lag_estimator(self, kind, window=4, sub=4, huber_px=0.0, pcap=None, max_frames=None):
         """A LagEstimator for a table of tracked poses of `kind` ('est': f32 poses with per-row flags, 'triang': f64 poses
         with per-joint flags, as the calibrator takes them): how many frames every camera runs ahead of or behind the
@@ -1740,6 +1749,114 @@ class Calibrator(_DeviceState):
 
     def reset(self):
         """Start afresh from the engine's own extrinsics."""
+        self._open()
+        super().reset()
+
+
+class CameraFitter(_DeviceState):
+    """Engine.camera_fitter's object: the trial set (extrinsics, fx fy cx cy as float32, lens terms) and the 105 sums per
+    camera on the device, the Levenberg-Marquardt state of the cameras in the library.  Used as the Calibrator is: a pass
+    is accumulate() over every batch of the recording, in any chunking (the sums are the same bits), then step().
+    accumulate() stays on the current stream and neither synchronises nor reads back; step() synchronises."""
+    _prefix, _noun = 'mpe_camfit', 'camera fitter'
+
+    def __init__(self, eng, kind, free, huber_px, min_obs, hold):
+        if kind not in ('est', 'triang'):
+            raise ValueError('kind must be est or triang')
+        if not huber_px >= 0.0:
+            raise ValueError('huber_px must be >= 0')
+        if isinstance(free, str):
+            free = [g for g in free.split(',') if g]
+        unknown = [g for g in free if g not in L.MPE_CAMFIT_GROUPS]
+        if unknown or not free:
+            raise ValueError('free names groups out of %s' % ', '.join(L.MPE_CAMFIT_GROUPS))
+        names = list(eng.params.used_cameras_skeleton_matching)
+        idx = [names.index(h) if isinstance(h, str) else int(h) for h in hold]
+        if any(not 0 <= i < eng.V for i in idx):
+            raise ValueError('hold names cameras of the engine')
+        self.kind, self.huber_px, self.min_obs = kind, float(huber_px), int(min_obs)
+        self.free_mask = sum(L.MPE_CAMFIT_GROUPS[g] for g in set(free))
+        self.hold_mask = sum(1 << i for i in set(idx))
+        self._create(eng)
+
+    def accumulate(self, db, persons, n_persons, poses, flags, joint_mask=None, threshold=0.5):
+        """The observations of one batch added to the pass (arguments as Engine.refine takes them)."""
+        self._open()
+        eng = self.eng
+        B, tri, joint_mask = eng._pose_args(db, persons, n_persons, poses, flags, self.kind, joint_mask, ('est', 'triang'))
+        a = L.mpe_calib_args()
+        a.n_frames, a.pcap, a.n_joints = B, eng.pcap, eng.J
+        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
+        a.huber_px = self.huber_px
+        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
+        eng._chk(eng.lib.mpe_camfit_batch(eng.ctx, eng._stream(), self.state, C.byref(db.struct), C.byref(a)))
+
+    def read(self):
+        """The sums of the pass so far (synchronises) -> {'acc' [V,105] f64, 'n_obs' [V] i64, 'n_skipped' [V] i64}."""
+        self._open()
+        eng = self.eng
+        acc, n, k = np.zeros((eng.V, L.MPE_CAMFIT_SUMS)), np.zeros(eng.V, np.int64), np.zeros(eng.V, np.int64)
+        i64p = C.POINTER(C.c_int64)
+        eng._chk(eng.lib.mpe_camfit_read(eng.ctx, eng._stream(), self.state, acc.ctypes.data_as(L.c_f64p), n.ctypes.data_as(i64p),
+                                         k.ctypes.data_as(i64p)))
+        return {'acc': acc, 'n_obs': n, 'n_skipped': k}
+
+    def step(self, rot_tol=1e-7, trans_tol=1e-6, pix_tol=1e-3, lens_tol=1e-7):
+        """The end of a pass: per camera the pass is accepted or rejected and the next trial set is built
+        (mpe_camfit_step).  -> Calibrator.step's keys with 'last_pix', 'last_lens' and 'delta' [V,13]."""
+        self._open()
+        eng = self.eng
+        a, rep = L.mpe_camfit_step_args(), L.mpe_camfit_report()
+        a.rot_tol, a.trans_tol, a.pix_tol, a.lens_tol = float(rot_tol), float(trans_tol), float(pix_tol), float(lens_tol)
+        a.min_obs, a.hold_mask, a.free_mask = self.min_obs, self.hold_mask, self.free_mask
+        eng._chk(eng.lib.mpe_camfit_step(eng.ctx, eng._stream(), self.state, C.byref(a), C.byref(rep)))
+        cams = [rep.cam[c] for c in range(rep.n_cameras)]
+        out = {k: np.array([getattr(c, k) for c in cams], np.int32) for k in ('status', 'passes')}
+        out.update({k: np.array([getattr(c, k) for c in cams], np.int64) for k in ('n_obs', 'n_skipped')})
+        out.update({k: np.array([getattr(c, k) for c in cams], np.float64)
+                    for k in ('cost_start', 'cost', 'last_rot', 'last_trans', 'last_pix', 'last_lens')})
+        out['lambda'] = np.array([c.lambda_ for c in cams], np.float64)
+        out['delta'] = np.array([list(c.delta) for c in cams], np.float64).reshape(-1, L.MPE_CAMFIT_UNKNOWNS)
+        out['all_done'] = bool(rep.all_done)
+        return out
+
+    def cameras(self):
+        """-> (accepted, trial), each (E [V,3,4] f64, k [V,4] f32: fx fy cx cy, dist [V,5] f64), in the engine's camera order."""
+        self._open()
+        eng = self.eng
+        sets = [(np.zeros((eng.V, 3, 4)), np.zeros((eng.V, 4), np.float32), np.zeros((eng.V, 5))) for _ in range(2)]
+        ptrs = [p for E, k, d in sets for p in (E.ctypes.data_as(L.c_f64p), k.ctypes.data_as(L.c_f32p), d.ctypes.data_as(L.c_f64p))]
+        eng._chk(eng.lib.mpe_camfit_get_cameras(eng.ctx, self.state, *ptrs))
+        return sets[0], sets[1]
+
+    def set_cameras(self, E, k, dist):
+        """Start afresh from E [V,3,4], k [V,4] (fx fy cx cy, rounded to float32) and dist [V,5] (engine camera order):
+        accepted = trial = these, the sums zeroed."""
+        self._open()
+        eng = self.eng
+        E, k, dist = np.ascontiguousarray(E, np.float64), np.ascontiguousarray(k, np.float32), np.ascontiguousarray(dist, np.float64)
+        if E.shape != (eng.V, 3, 4) or k.shape != (eng.V, 4) or dist.shape != (eng.V, 5):
+            raise ValueError('E, k, dist must be [%d,3,4], [%d,4], [%d,5]' % (eng.V, eng.V, eng.V))
+        eng._chk(eng.lib.mpe_camfit_set_cameras(eng.ctx, eng._stream(), self.state, E.ctypes.data_as(L.c_f64p), k.ctypes.data_as(L.c_f32p),
+                                                dist.ctypes.data_as(L.c_f64p)))
+
+    def calibration(self):
+        """A new Calibration: the engine's, with the accepted extrinsics (Calibration.with_extrinsics) and then the accepted
+        intrinsics and lens terms (Calibration.with_intrinsics)."""
+        calib = self.eng.calib
+        (Ea, ka, da), _ = self.cameras()
+        E, k, dist = np.array(calib.P, np.float64), calib.intrinsics(), np.array(calib.dist, np.float64)
+        for i, cam in enumerate(self.eng.params.used_cameras_skeleton_matching):
+            at = calib.index(cam)
+            E[at], k[at], dist[at] = Ea[i], ka[i], da[i]
+        return calib.with_extrinsics(E).with_intrinsics(k, dist)
+
+    def launches(self):
+        self._open()
+        return super().launches()
+
+    def reset(self):
+        """Start afresh from the engine's own cameras."""
         self._open()
         super().reset()
 

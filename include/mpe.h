@@ -513,6 +513,98 @@ int mpe_calib_read(mpe_ctx *ctx, void *stream, mpe_calib_state *st, double *sums
 int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_calib_step_args *a, mpe_calib_report *report);
 int mpe_calib_launches(mpe_ctx *ctx, const mpe_calib_state *st, int64_t *n);
 
+/* Camera fit: the intrinsics and the radial lens terms of every camera fitted together with its extrinsics from a
+ * recording's own poses -- mpe_calib_* with seven more unknowns per camera.  The 3D joints are held fixed; a pass
+ * (mpe_camfit_batch over every batch of the recording) reduces all observations into one 13 x 13 system per camera on the
+ * device, mpe_camfit_step solves the systems on the host.  The context's own calibration is never modified.  All binary64,
+ * every operation named below rounded on its own (nothing fused); harness/camfit.py states the same in numpy: the sums
+ * agree bit for bit, and so does the step.
+ * Unknowns, per camera, in this order: 0-2 w, 3-5 tau (the rigid perturbation pc + w x pc + tau, exactly mpe_calib_batch's),
+ *   6 fx, 7 fy, 8 cx, 9 cy, 10 kd0, 11 kd1, 12 kd2.  The model is that of mpe_refine_batch as it is: the tangential terms
+ *   dist[2], dist[3] are not read, are carried through untouched and are not unknowns.  K has the form
+ *   [[fx,0,cx],[0,fy,cy],[0,0,1]]; a context whose K has another form is refused by mpe_camfit_create (MPE_ERR_INVALID).
+ * Trial set, per camera: extrinsics [12] f64, (fx, fy, cx, cy) held as FLOAT32, dist[5] f64.  K is float32 because the
+ *   context, every kernel and every caller carry it that way: the step rounds (double)fx + delta to float before the next
+ *   pass, so the cost a pass reports is the cost at exactly the numbers a new context will evaluate.
+ * One pass, per observation.  Every observation mpe_calib_batch would count is counted: the selection, the finite test,
+ *   pc_2 > 0 before any quotient, the skip rule, the weight w and rho(e) are the same, taken at the trial set (T = the trial
+ *   extrinsics, kd = the trial dist[0], dist[1], dist[4], K = the trial numbers widened).  Jx_0..5, Jy_0..5 are
+ *   mpe_calib_batch's lines with the trial K and dist in them.  With d0 = h0*f, d1 = h1*f:
+ *     Jx_6 = d0 ; Jy_6 = 0       Jx_7 = 0 ; Jy_7 = d1       Jx_8 = 1 ; Jy_8 = 0       Jx_9 = 0 ; Jy_9 = 1
+ *     Jx_{10+i} = (fx*h0)*r^(i+1) ; Jy_{10+i} = (fy*h1)*r^(i+1),  i = 0..2, the powers taken as r, r*r, (r*r)*r
+ *   Every summed observation adds MPE_CAMFIT_SUMS = 105 numbers to its camera, every one of the one form
+ *   w*(a_k*a_l + b_k*b_l) -- the structural zeros are computed like everything else:
+ *     A_kl += w*(Jx_k*Jx_l + Jy_k*Jy_l)   k <= l, row by row: (0,0) (0,1) .. (0,12) (1,1) .. (12,12)    q = 0..90
+ *     g_k  += w*(Jx_k*rx + Jy_k*ry)                                                                  q = 91..103
+ *     C    += rho(e)                                                                                 q = 104
+ *   and 1 to n_obs[c]; a skipped one adds 1 to n_skipped[c].
+ * Order: mpe_calib_batch's.  Per frame the left fold from 0.0 over p, then j; then the frames of a call in increasing f,
+ *   every frame whether its partial is zero or not; then calls in the order made.  Any cut of a recording into batches
+ *   gives the same bits.
+ * mpe_camfit_batch: two launches whatever the frame count, ordered on `stream`; neither synchronises nor allocates;
+ *   n_frames == 0 does nothing.  It takes mpe_calib_args and refuses what mpe_calib_batch refuses.
+ * mpe_camfit_step: mpe_calib_step's rule per camera (csrc/camfit_solve.h writes out every sum), with these additions.
+ *   free_mask names the groups that are unknowns: MPE_CAMFIT_POSE (0-5), _FOCAL (6, 7), _CENTRE (8, 9), _K1 (10), _K2 (11),
+ *     _K3 (12); zero or a bit outside these: MPE_ERR_INVALID.  The row and column of a held unknown are left out of the
+ *     solve and its delta is 0.  The solve is the unpivoted LDL^T of mpe_calib_step over the free unknowns in ascending
+ *     index, M = A + lambda*diag(A); with only MPE_CAMFIT_POSE free it performs the same operations in the same order.
+ *   Compose: the extrinsics as in mpe_calib_step from delta_0..5 when MPE_CAMFIT_POSE is free (else copied); for a free
+ *     intrinsic fx_t = (float)((double)fx_a + delta_6), fy, cx, cy likewise; for a free lens term kd_t = kd_a + delta.
+ *     A trial whose fx or fy is not finite or is <= 0 counts as a failed solve (lambda * 10, at most 8 retries, then
+ *     MPE_CALIB_STALLED).
+ *   Accepted iff the cost fell (strict; the first pass is accepted).  MPE_CALIB_CONVERGED when the accepted step had
+ *     |w| < rot_tol, max |tau_k| < trans_tol, max |delta_6..9| < pix_tol (pixels) and max |delta_10..12| < lens_tol -- or
+ *     when the trial just built equals the accepted set bit for bit in every free unknown: the float rounding left
+ *     nothing to move.
+ *   min_obs >= max(6, the number of free unknowns), else MPE_ERR_INVALID; hold_mask, MPE_CALIB_FEW_OBS, the n_obs check
+ *     ("the passes did not see the same data") and the status bits (MPE_CALIB_*) are mpe_calib_step's.
+ * mpe_camfit_set_cameras: host E [V][12], k [V][4] float (fx, fy, cx, cy), dist [V][5]; accepted = trial = these, the
+ *   Levenberg-Marquardt state and the sums start afresh; a value that is not finite, or fx or fy <= 0: MPE_ERR_INVALID.
+ *   mpe_camfit_reset: the same with the context's own.  mpe_camfit_get_cameras: host copies of the accepted and the trial
+ *   set (any pointer may be NULL).  mpe_camfit_read: synchronises and returns the sums of the pass so far, [V][105], and the
+ *   counts [V] (any may be NULL).  One state serves one thread and one stream of work at a time. */
+typedef struct mpe_camfit_state mpe_camfit_state;
+enum {
+    MPE_CAMFIT_POSE = 1,
+    MPE_CAMFIT_FOCAL = 2,
+    MPE_CAMFIT_CENTRE = 4,
+    MPE_CAMFIT_K1 = 8,
+    MPE_CAMFIT_K2 = 16,
+    MPE_CAMFIT_K3 = 32
+};
+#define MPE_CAMFIT_UNKNOWNS 13
+#define MPE_CAMFIT_SUMS 105
+typedef struct {
+    double rot_tol, trans_tol;     /* radians, metres                                                */
+    double pix_tol, lens_tol;      /* pixels (fx, fy, cx, cy); the three kd                          */
+    int64_t min_obs;               /* >= max(6, free unknowns)                                       */
+    uint32_t hold_mask;            /* bit c: camera c is held                                        */
+    uint32_t free_mask;            /* MPE_CAMFIT_* bits: the groups that are unknowns                */
+} mpe_camfit_step_args;
+typedef struct {
+    int32_t status, passes;        /* MPE_CALIB_* bits; passes this camera's state has seen          */
+    int64_t n_obs, n_skipped;      /* of the pass just read                                          */
+    double cost_start, cost;       /* C_a after the first pass and now                               */
+    double lambda;
+    double last_rot, last_trans;   /* |w| and |tau| of the last trial built                          */
+    double last_pix, last_lens;    /* max |delta_6..9| and max |delta_10..12| of that trial          */
+    double delta[13];              /* that trial's step, in the order of the unknowns                */
+} mpe_camfit_cam_report;
+typedef struct {
+    int32_t n_cameras, all_done;
+    mpe_camfit_cam_report cam[MPE_MAX_CAMERAS];
+} mpe_camfit_report;
+int mpe_camfit_create(mpe_ctx *ctx, mpe_camfit_state **out);
+int mpe_camfit_destroy(mpe_ctx *ctx, mpe_camfit_state *st);
+int mpe_camfit_reset(mpe_ctx *ctx, void *stream, mpe_camfit_state *st);
+int mpe_camfit_set_cameras(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const double *E, const float *k, const double *dist);
+int mpe_camfit_get_cameras(mpe_ctx *ctx, const mpe_camfit_state *st, double *E_accepted, float *k_accepted, double *dist_accepted,
+                           double *E_trial, float *k_trial, double *dist_trial);
+int mpe_camfit_batch(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const mpe_batch *b, const mpe_calib_args *a);
+int mpe_camfit_read(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, double *sums, int64_t *n_obs, int64_t *n_skipped);
+int mpe_camfit_step(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const mpe_camfit_step_args *a, mpe_camfit_report *report);
+int mpe_camfit_launches(mpe_ctx *ctx, const mpe_camfit_state *st, int64_t *n);
+
 /* Time lags: how many frames each camera runs ahead of or behind the poses of a recording, estimated from the recording
  * itself -- the time half of the rig adjustment of which mpe_calib_* is the space half.  The 3D poses of the whole
  * sequence, with track ids, are a table; every detection of a camera is compared with the projection of its track's pose

@@ -5,6 +5,8 @@
 //
 //   k_lat_gemm         fc1 / fc2 of the graph-attention layers >= 1 (gat2.py:53-55) fed with bf16 PLANES written by the producer's epilogue
 //                      (no wave splits anything), all weight fragments of a wave requested at once, coefficient epilogue
+//   k_last_fused       the last layer's fc1 + fc2 (k_lat_gemm's FUSE2 arithmetic) at BATCH size from fp32 rows: the one kernel here that the
+//                      batch path launches (api.hip: last_layer_fusable), a persistent grid bound by the matrix pipe, not by latency
 //   (gat.hip)          k_lat_l0a: topology tables + layer-0 fc1 with in-place featurisation; k_lat_attention: both halves of the
 //                      attention stage in one launch;  (cluster.hip) k_lat_tail: last layer's scores + clustering + every pair solve
 //
@@ -256,6 +258,143 @@ __global__ __launch_bounds__(64 * NT) void k_lat_gemm(const unsigned short *__re
     } while (LOOP && tm + tm_step < ntm);                    // row tiles of the workgroup
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// k_last_fused: the FUSE2 arithmetic above (fc1 150 -> 150 + LeakyReLU, then fc2 150 -> 1 with its coefficients; same products, same
+// orders, same bits) at batch size, fed with the fp32 rows of the batch path.  A persistent grid of ten-wave workgroups walks the
+// 16-row tiles; wave w owns columns 16 w ... 16 w + 15 of fc1 and keeps its NK x 3 weight fragments in registers for the whole launch.
+// Per tile and workgroup:
+//   * the 16 x 160 fp32 rows are exactly one float4 per thread: requested a whole tile ahead (two tiles of rows are in flight per
+//     workgroup), split once (split4_lat: the planes every other kernel makes) and written to the other of two LDS plane images
+//     after this tile's MFMAs -- the tile kernels split every row once per 80-column tile, and fc2's wave-per-tile kernel a third
+//     time after a trip through HBM;
+//   * every wave multiplies its column tile from the current image (30 MFMAs), adds the bias, applies LeakyReLU and writes the
+//     three planes of its 16 x 16 result into one of two images of the fc1 rows (they never leave the CU);
+//   * ONE barrier; behind it fc2 of the tile just finished is dealt to one wave, which does its 30 MFMAs at the top of its next
+//     iteration while the other nine are already in the next tile's fc1.  fc2's sixteen weight rows (one real, fifteen of zeros) wait
+//     in LDS as planes: 15 fragment reads per fc2, no registers held.
+// Ten waves on four SIMDs leave two SIMDs with three waves and two with two (waves are dealt to the SIMDs in turn: 0 4 8 | 1 5 9 |
+// 2 6 | 3 7); fc2 goes to waves 2, 3, 6, 7 in turn, i.e. to the slack of the two-wave SIMDs (a heuristic about placement only).
+// Hazards, with s_a[x] / s_h[x] the images of parity x and B(i) the barrier that ends iteration i: s_a[i+1] is written in
+// iteration i and was last read in iteration i - 1, before B(i-1); s_h[i] is written in iteration i, read by fc2 at the top of
+// iteration i + 1 (before that wave reaches B(i+1)) and written again in iteration i + 2, behind B(i+1).
+// Rows behind M are clamped to row M - 1 on the way in (valid memory, results not stored); the request for a tile behind the last one
+// does the same, so no request hangs on a condition.  The loads are plain loads: the compiler counts and waits for them.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int NK, int NT>
+__global__ __launch_bounds__(64 * NT) void k_last_fused(const float *__restrict__ A, int lda, const unsigned short *__restrict__ W3, size_t w_plane,
+                                                         int ldw, const float *__restrict__ bias, int M, float slope, LatFc2 f2) {
+    static_assert(NT * 16 == NK * 32 && NT * 64 == 16 * NK * 8, "whole fc1 rows per workgroup; one float4 of the row tile per thread");
+    static_assert(NT >= 8, "fc2 is dealt to waves 2, 3, 6, 7");
+    constexpr int KS = NK * 32 + 8;                          // LDS row stride of a plane (bf16 elements), as k_lat_gemm
+    constexpr int IMG = 3 * 16 * KS;                         // one image: three planes of sixteen rows
+    constexpr int NTHR = 64 * NT;
+    __shared__ __attribute__((aligned(16))) unsigned short s_a[2][IMG], s_h[2][IMG], s_w2[IMG];
+    const int ntm = (M + 15) / 16, step = gridDim.x;
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int fq = lane >> 4, fr = lane & 15;
+    bf16x8 wv[NK][3];
+    {
+        const unsigned short *pw = W3 + (size_t)(wave * 16 + fr) * ldw + 8 * fq;
+#pragma unroll
+        for (int kt = 0; kt < NK; ++kt)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) wv[kt][p] = *reinterpret_cast<const bf16x8 *>(pw + p * w_plane + kt * GEMM_BK);
+    }
+    for (int c = t; c < 3 * 16 * NK * 4; c += NTHR) {        // fc2's planes, rows 0 ... 15
+        const int p = c / (16 * NK * 4), rem = c - p * (16 * NK * 4);
+        const int r = rem / (NK * 4), ch = rem - r * (NK * 4);
+        *reinterpret_cast<u32x4 *>(&s_w2[(p * 16 + r) * KS + ch * 8]) =
+            *reinterpret_cast<const u32x4 *>(f2.W3 + p * f2.w_plane + (size_t)r * f2.ldw + ch * 8);
+    }
+    const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + wave * 16 + fq * 4);
+    const float bias2 = f2.bias[0], al = f2.attn_l[0], ar = f2.attn_r[0];
+    const int sr = t / (NK * 8), sc = t - sr * (NK * 8);    // this thread's float4 of a row tile: row sr, columns 4 sc ...
+    auto fetch = [&](int tm) {
+        int grow = tm * 16 + sr;
+        grow = grow < M ? grow : M - 1;
+        return *reinterpret_cast<const f32x4 *>(A + (size_t)grow * lda + sc * 4);
+    };
+    auto put = [&](int buf, const f32x4 &x) {
+        uint2 q0, q1, q2;
+        split4_lat(x, q0, q1, q2);
+        unsigned short *d = &s_a[buf][sr * KS + sc * 4];
+        *reinterpret_cast<uint2 *>(d) = q0;
+        *reinterpret_cast<uint2 *>(d + 16 * KS) = q1;
+        *reinterpret_cast<uint2 *>(d + 32 * KS) = q2;
+    };
+    auto fc2 = [&](int tm, int buf) {
+        f32x4 e = {0.f, 0.f, 0.f, 0.f}, o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kt = 0; kt < NK; ++kt) {
+            bf16x8 ap[3], wp[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                ap[p] = *reinterpret_cast<const bf16x8 *>(&s_h[buf][(p * 16 + fr) * KS + kt * GEMM_BK + 8 * fq]);
+                wp[p] = *reinterpret_cast<const bf16x8 *>(&s_w2[(p * 16 + fr) * KS + kt * GEMM_BK + 8 * fq]);
+            }
+            if (kt & 1) SB_STAGE(o, ap, wp);
+            else SB_STAGE(e, ap, wp);
+        }
+        const int m = tm * 16 + fr;
+        if (fq == 0 && m < M) {                              // output column 0 of the row
+            const float y = (e[0] + o[0]) + bias2;
+            f2.C[(size_t)m * f2.ldc] = y;
+            f2.a12[(size_t)m * 32] = __builtin_fmaf(y, al, 0.f);
+            f2.a12[(size_t)m * 32 + 16] = __builtin_fmaf(y, ar, 0.f);
+        }
+    };
+    auto fc1 = [&](int buf) {                               // this wave's 16 x 16 tile of the fc1 rows -> planes in s_h[buf]
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_odd = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kt = 0; kt < NK; ++kt) {
+            bf16x8 ap[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) ap[p] = *reinterpret_cast<const bf16x8 *>(&s_a[buf][(p * 16 + fr) * KS + kt * GEMM_BK + 8 * fq]);
+            if (kt & 1) SB_STAGE(acc_odd, ap, wv[kt]);
+            else SB_STAGE(acc, ap, wv[kt]);
+        }
+        f32x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = (acc[i] + acc_odd[i]) + bv[i];
+            v[i] = v[i] > 0.f ? v[i] : v[i] * slope;
+        }
+        uint2 q0, q1, q2;                                    // (columns behind n are exact zeros: zero weight rows, zero bias)
+        split4_lat(v, q0, q1, q2);
+        unsigned short *d = &s_h[buf][fr * KS + wave * 16 + fq * 4];
+        *reinterpret_cast<uint2 *>(d) = q0;
+        *reinterpret_cast<uint2 *>(d + 16 * KS) = q1;
+        *reinterpret_cast<uint2 *>(d + 32 * KS) = q2;
+    };
+    auto fc2_wave = [](int it) { return 2 + (it & 1) + 4 * ((it >> 1) & 1); };
+    // Two tiles per pass of the loop, so that the images have constant indices and the rows in flight need no register moves: the
+    // float4 requested in one half is split and stored at the end of the NEXT half, about a tile's time later.  Requested and used
+    // within one half (the compiler issues the load behind the MFMAs, next to its use) the launch ran at the memory round trip per
+    // tile: 83 us against 69.  Measured and not kept (profiles/last_layer_timing.txt): the requests pinned to the top of each half
+    // (no gain), the split of the next tile ahead of the MFMAs (slower).
+    int tm = blockIdx.x, it = 0;
+    put(0, fetch(tm));
+    f32x4 n_even, n_odd = fetch(tm + step);
+    __syncthreads();
+    for (;;) {
+        if (it > 0 && wave == fc2_wave(it - 1)) fc2(tm - step, 1);
+        n_even = fetch(tm + 2 * step);
+        fc1(0);
+        put(1, n_odd);
+        __syncthreads();
+        tm += step, ++it;
+        if (tm >= ntm) break;
+        if (wave == fc2_wave(it - 1)) fc2(tm - step, 0);
+        n_odd = fetch(tm + 2 * step);
+        fc1(1);
+        put(0, n_even);
+        __syncthreads();
+        tm += step, ++it;
+        if (tm >= ntm) break;
+    }
+    if (wave == fc2_wave(it - 1)) fc2(tm - step, (it - 1) & 1);
+}
+
 }  // namespace lat
 
 // Row-tile groups of an fc1 launch: one workgroup per (row tile, column group) while that fits the chip in one round (the kernels hold
@@ -301,6 +440,20 @@ hipError_t launch_lat_gemm_fused(hipStream_t s, const unsigned short *Apl, int l
     const int ntm = (m + 15) / 16;
     hipLaunchKernelGGL((lat::k_lat_gemm<5, 10, true, true, false, true>), dim3((unsigned)ntm), dim3(640), 0, s, Apl, lda, a_plane, W3, w_plane, ldw, bias,
                        nullptr, 0, nullptr, 0, 0, m, n, slope, nullptr, nullptr, nullptr, 0, f2);
+    return hipGetLastError();
+}
+
+// The same layer pair at batch size from fp32 rows (k_last_fused): a persistent grid, one workgroup per CU (the CU count rounded down
+// to a multiple of eight, as launch_linear_sb16 has it), each walking row tiles blockIdx, blockIdx + grid, ...
+hipError_t launch_last_fused(hipStream_t s, const float *A, int lda, const unsigned short *W3, size_t w_plane, int ldw, const float *bias, int m,
+                             float slope, const unsigned short *W3b, size_t w_plane_b, int ldw_b, const float *bias_b, float *C2, int ldc2,
+                             const float *attn_l, const float *attn_r, float *a12) {
+    if (m <= 0) return hipSuccess;
+    if (lda < 160 || ldw != 160 || ldw_b != 160 || (lda & 3)) return hipErrorInvalidValue;      // (lat_gemm_fusable's shapes)
+    lat::LatFc2 f2{W3b, w_plane_b, ldw_b, bias_b, C2, ldc2, attn_l, attn_r, a12};
+    const int ntm = (m + 15) / 16, cu = device_cu_count();
+    const int n_cu = cu >= 8 ? cu / 8 * 8 : 8;
+    hipLaunchKernelGGL((lat::k_last_fused<5, 10>), dim3((unsigned)(ntm < n_cu ? ntm : n_cu)), dim3(640), 0, s, A, lda, W3, w_plane, ldw, bias, m, slope, f2);
     return hipGetLastError();
 }
 

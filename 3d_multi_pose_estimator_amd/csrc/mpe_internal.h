@@ -331,6 +331,10 @@ bool lat_gemm_fusable(int k1_pad, int n1, int k2_pad, int n2, int out_dim2);
 hipError_t launch_lat_gemm_fused(hipStream_t s, const unsigned short *Apl, int lda, size_t a_plane, const unsigned short *W3, size_t w_plane, int ldw,
                                  const float *bias, int m, int n, float slope, const unsigned short *W3b, size_t w_plane_b, int ldw_b, const float *bias_b,
                                  float *C2, int ldc2, const float *attn_l, const float *attn_r, float *a12);
+// ... at batch size from the fp32 rows of the batch path (k_last_fused: persistent grid, the same bits)
+hipError_t launch_last_fused(hipStream_t s, const float *A, int lda, const unsigned short *W3, size_t w_plane, int ldw, const float *bias, int m,
+                             float slope, const unsigned short *W3b, size_t w_plane_b, int ldw_b, const float *bias_b, float *C2, int ldc2,
+                             const float *attn_l, const float *attn_r, float *a12);
 // gemm_f64.hip: exact products, f64 accumulation on the f64 matrix pipe (MLP mode 5: the f64-evaluated network, not the fast path; the slope rule is in include/mpe.h)
 hipError_t launch_linear_f64(hipStream_t s, const float *A, int lda, const float *W, int ldw, const float *bias, float *C, int ldc,
                              int m_cap, const int32_t *d_m, int n, int k_pad, bool leaky, float slope);

@@ -101,17 +101,26 @@ __device__ __forceinline__ void split8_lat(const f32x4 &x0, const f32x4 &x1, bf1
     p2 = __builtin_bit_cast(bf16x8, q2);
 }
 
-// the three bf16 planes of four values, as split8 makes them -> three 8-byte stores
-__device__ __forceinline__ void store_planes4(unsigned short *dst, size_t plane, const f32x4 &v) {
+// the three bf16 planes of four values, as split8 makes them: four bf16 (8 bytes) per plane
+__device__ __forceinline__ void split4_lat(const f32x4 &v, uint2 &q0, uint2 &q1, uint2 &q2) {
     const unsigned a0 = pack2_lat(v[0], v[1]), a1 = pack2_lat(v[2], v[3]);
     const float r0 = sub1(v[0], __uint_as_float(a0 << 16)), r1 = sub1(v[1], __uint_as_float(a0 & 0xFFFF0000u));
     const float r2 = sub1(v[2], __uint_as_float(a1 << 16)), r3 = sub1(v[3], __uint_as_float(a1 & 0xFFFF0000u));
     const unsigned b0 = pack2_lat(r0, r1), b1 = pack2_lat(r2, r3);
     const float s0 = sub1(r0, __uint_as_float(b0 << 16)), s1 = sub1(r1, __uint_as_float(b0 & 0xFFFF0000u));
     const float s2 = sub1(r2, __uint_as_float(b1 << 16)), s3 = sub1(r3, __uint_as_float(b1 & 0xFFFF0000u));
-    *reinterpret_cast<uint2 *>(dst) = make_uint2(a0, a1);
-    *reinterpret_cast<uint2 *>(dst + plane) = make_uint2(b0, b1);
-    *reinterpret_cast<uint2 *>(dst + 2 * plane) = make_uint2(pack2_lat(s0, s1), pack2_lat(s2, s3));
+    q0 = make_uint2(a0, a1);
+    q1 = make_uint2(b0, b1);
+    q2 = make_uint2(pack2_lat(s0, s1), pack2_lat(s2, s3));
+}
+
+// ... -> three 8-byte stores
+__device__ __forceinline__ void store_planes4(unsigned short *dst, size_t plane, const f32x4 &v) {
+    uint2 q0, q1, q2;
+    split4_lat(v, q0, q1, q2);
+    *reinterpret_cast<uint2 *>(dst) = q0;
+    *reinterpret_cast<uint2 *>(dst + plane) = q1;
+    *reinterpret_cast<uint2 *>(dst + 2 * plane) = q2;
 }
 
 // the three planes of ONE value (plane stride in elements)

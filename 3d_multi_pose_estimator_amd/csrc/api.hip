@@ -1036,6 +1036,12 @@ int mpe_linear(mpe_ctx *ctx, void *stream, const float *d_a, int32_t lda, const 
         return fail(ctx, MPE_ERR_INVALID, "mpe_linear: bad argument");
     if (ldw % LD_ALIGN || ldw < k || lda < ldw || ldc % 4 || ldc < n)
         return fail(ctx, MPE_ERR_INVALID, "mpe_linear: strides must satisfy ldw%%32==0, lda>=ldw>=k, ldc%%4==0");
+    // every form reads A and W in 16-byte pieces (vector loads or LDS-DMA) and all but the f64 form store C as four floats
+    if (lda % 4 || (reinterpret_cast<uintptr_t>(d_a) & 15) || (reinterpret_cast<uintptr_t>(d_w) & 15) || (reinterpret_cast<uintptr_t>(d_c) & 15))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_linear: rows must be 16-byte aligned (d_a, d_w, d_c; lda %% 4 == 0)");
+    // the split form's tile kernel addresses a row of its 256-row tile by a 32-bit byte offset per lane, (row - m0) * lda * 4 (gemm_sb16.hip)
+    if (lda > LINEAR_MAX_LDA)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_linear: lda %d beyond %d (255 rows of it must fit a 32-bit byte offset)", lda, LINEAR_MAX_LDA);
     Linear L;
     L.w = const_cast<float *>(d_w);
     L.b = const_cast<float *>(d_bias);
@@ -1043,8 +1049,6 @@ int mpe_linear(mpe_ctx *ctx, void *stream, const float *d_a, int32_t lda, const 
     L.out_dim = n;
     L.ldw = ldw;
     if (slope_on & 32) {
-        if (lda % 4 || (reinterpret_cast<uintptr_t>(d_a) & 15) || (reinterpret_cast<uintptr_t>(d_w) & 15))
-            return fail(ctx, MPE_ERR_INVALID, "mpe_linear (f64 form): rows must be 16-byte aligned (lda %% 4 == 0)");
         HIPCHK(ctx, launch_linear_f64(static_cast<hipStream_t>(stream), d_a, lda, d_w, ldw, d_bias, d_c, ldc, m, d_m, n, ldw, (slope_on & 1) != 0, slope));
         return MPE_OK;
     }
@@ -1348,6 +1352,11 @@ int mpe_mlp_forward(mpe_ctx *ctx, void *stream, const float *d_x, int32_t ld_x, 
     if ((size_t)m > (size_t)ctx->cfg.max_frames * ctx->cfg.max_persons_per_frame)
         return fail(ctx, MPE_ERR_CAPACITY, "mpe_mlp_forward: %d rows exceed capacity", m);
     if (ld_x < ctx->mlp_ld_in) return fail(ctx, MPE_ERR_INVALID, "mpe_mlp_forward: ld_x must be >= %d (zero padded)", ctx->mlp_ld_in);
+    // (the first layer reads d_x as mpe_linear reads A; d_y is written by a strided copy of n_out floats per row)
+    if (ld_x % 4 || ld_x > LINEAR_MAX_LDA || (reinterpret_cast<uintptr_t>(d_x) & 15))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_mlp_forward: rows of d_x must be 16-byte aligned (ld_x %% 4 == 0) and ld_x <= %d", LINEAR_MAX_LDA);
+    if (ld_y < ctx->mlp[ctx->mlp_layers - 1].out_dim)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_mlp_forward: ld_y %d < output width %d", ld_y, ctx->mlp[ctx->mlp_layers - 1].out_dim);
     hipStream_t s = static_cast<hipStream_t>(stream);
     float *y;
     int ldy;

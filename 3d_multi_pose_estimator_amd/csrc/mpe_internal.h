@@ -19,6 +19,9 @@ constexpr int GEMM_BN_MAX = 208;   // widest feature tile of the GEMM variants (
 // stays inside the allocation
 inline int weight_rows(int out_dim) { return (out_dim + 15) / 16 * 16 + GEMM_BN_MAX; }
 constexpr int LD_ALIGN = 32;   // every activation / weight row stride is a multiple of this
+// largest activation stride the public GEMM entry points take: k_linear_sb (gemm_sb16.hip) addresses the rows of a 256-row tile by
+// a 32-bit byte offset per lane, (row - m0) * lda * 4 + chunk, computed in int: 255 * 2^21 * 4 + 128 < 2^31
+constexpr int LINEAR_MAX_LDA = 1 << 21;
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 

@@ -1090,7 +1090,17 @@ int mpe_partition_scores(mpe_ctx *ctx, void *stream, const mpe_partition_scores_
  * mpe_upload_linear (zero padded).  d_m, if not NULL, overrides M with a device-side count.
  * flags: bit 0 = apply LeakyReLU(slope), bit 1 = f64 running sums (see mpe_set_precision), bit 2 = the split-bf16 form
  * (csrc/gemm_sb16.hip; the planes are made for the call), with bit 3 = without its f64 sums and bit 4 = an f64 flush per K stage;
- * bit 5 = the f64 matrix-pipe form (csrc/gemm_f64.hip). */
+ * bit 5 = the f64 matrix-pipe form (csrc/gemm_f64.hip).
+ * What is read and written (every form; tests/test_gpu_linear_contract.py):
+ *   rows   M = min(m, *d_m) when d_m is given (m is then the capacity: kernel and grid are chosen from it, the bits of a row do
+ *          not depend on it); M <= 0 launches or writes nothing.  Rows >= M of A are never read into a result (they may hold
+ *          anything, NaN included) and rows >= M of C are never written.
+ *   A      read over ldw columns of rows [0, M): columns [k, ldw) meet the zero padding of W and must be FINITE (0 * NaN is NaN);
+ *          columns >= ldw are never read.
+ *   C      written in [0, M) x [0, n) only: columns [n, ldc) and everything outside those rows keep their bytes.
+ * MPE_ERR_INVALID, before anything is launched, unless ldw % 32 == 0, k <= ldw <= lda <= 2^21 (the split form's tile kernel
+ * addresses 255 rows of lda floats by a 32-bit byte offset), lda % 4 == 0, ldc % 4 == 0, ldc >= n, and d_a, d_w, d_c are
+ * 16-byte aligned (operands are moved in 16-byte pieces). */
 int mpe_upload_linear(mpe_ctx *ctx, const float *w, const float *b, int32_t out_dim, int32_t in_dim,
                       float **d_w, float **d_b, int32_t *ldw);
 int mpe_free_device(mpe_ctx *ctx, void *d_ptr);
@@ -1158,7 +1168,10 @@ int mpe_cluster_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const floa
 /* MLP input rows only: d_rows [n_frames*Pcap][ld_rows] f32 (row r = frame*Pcap + p). */
 int mpe_mlp_input_rows(mpe_ctx *ctx, void *stream, const mpe_batch *b, const int32_t *d_persons,
                        const int32_t *d_n_persons, float *d_rows, int32_t ld_rows, uint8_t *d_valid);
-/* PoseEstimatorMLP.forward on d_x [m][ld_x] -> d_y [m][out_dim] (no x10). */
+/* PoseEstimatorMLP.forward on d_x [m][ld_x] -> d_y [m][ld_y] (out_dim columns written, the rest of a row kept; no x10).
+ * d_x is read as mpe_linear reads A: over round_up(in_dim, 128) columns, those beyond in_dim zero (finite at least); columns
+ * beyond that are never read.  MPE_ERR_INVALID, before anything is launched, unless round_up(in_dim, 128) <= ld_x <= 2^21,
+ * ld_x % 4 == 0, d_x is 16-byte aligned and ld_y >= out_dim. */
 int mpe_mlp_forward(mpe_ctx *ctx, void *stream, const float *d_x, int32_t ld_x, int32_t m,
                     float *d_y, int32_t ld_y);
 

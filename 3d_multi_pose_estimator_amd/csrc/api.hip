@@ -611,6 +611,17 @@ int gat_layer_linear(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, int l, Gat
         a->ft2 = ctx->act[2];
         *n_rows_ft2 = n_nodes;
     }
+    // Layer 0 on device-featurised rows (fp32, 40-wide heads, implicit topology): coefficients and attention in ONE launch that
+    // writes whole rows (gat.hip: k_l0_attention), so the coefficient kernel below is not launched.  The cross-check switches that
+    // name the kernels of today's two launches keep them (read per call: tests toggle them).
+    a->l0_whole_rows = 0;
+    if (in == GAT_IN_IMPLICIT && l == 0 && !b->d_en_pair && !half_rows && !red && !no_epi && !getenv("MPE_NO_FUSED_ATTENTION") &&
+        !getenv("MPE_FUSED_NO_OVERLAP") && !getenv("MPE_NO_HEAD_SRC_TABLE") &&
+        l0_attention_available(ctx->cfg.max_heads_per_frame, V, g.heads, g.out_dim)) {
+        a->l0_whole_rows = 1;
+        a->a12_ready = 0;
+        return MPE_OK;
+    }
     if (!done && cp && g.out_dim == 40 && !half_rows && ctx->gat_split && !red) {
         // the split-bf16 form with f64 sums (layer-0 fc2: K = 902) has no coefficient epilogue: a1 | a2 by the coefficient kernel
         // (canonical order = the epilogue's, gat.hip:coef40), so that the attention stage still finds them ready
@@ -646,6 +657,13 @@ void agg_scores_out(const mpe_ctx *ctx, AggArgs *a, float *d_scores_en, float *d
 
 int gat_attention(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, int l, const AggArgs &a, int n_rows_ft2) {
     const GatLayer &g = ctx->gat[l];
+    if (a.l0_whole_rows && !a.score_mode && !a.out_pl && a.ld % 4 == 0 && a.ld_out % 4 == 0) {
+        HIPCHK(ctx, launch_l0_attention(s, *b, ctx->cfg.n_cameras, ctx->cfg.max_heads_per_frame, ctx->node_off, ctx->en_pair, g.attn_l,
+                                        g.attn_r, a));
+        ++ctx->l0_attention_launches;
+        return MPE_OK;
+    }
+    // (a one-layer network writes scores from layer 0: the kernels below compute the coefficients themselves when a12_ready == 0)
     HIPCHK(ctx, launch_gat_attention(s, *b, ctx->cfg.n_cameras, ctx->cfg.max_heads_per_frame, ctx->node_off,
                                      ctx->head_frame, ctx->en_frame, ctx->en_pair, g.attn_l, g.attn_r, ctx->a12, a,
                                      n_rows_ft2, ctx->head_src, explicit_deg_cap(ctx->cfg.max_heads_per_frame), ctx->x_m_cap));
@@ -1184,18 +1202,34 @@ int mpe_gat_layer(mpe_ctx *ctx, void *stream, const mpe_batch *b, int32_t layer,
     if (layer < 0 || layer >= ctx->gat_layers) return fail(ctx, MPE_ERR_INVALID, "GAT layer index %d out of range", layer);
     const GatLayer &g = ctx->gat[layer];
     const int hd = g.heads * g.out_dim;
-    if ((rc = stage_layer_checks(ctx, b, layer, d_in, ld_in, g.in_dim, d_out, ld_out, hd))) return rc;
+    // layer 0 with d_in == NULL: the rows are featurised on the device, as mpe_gat_forward(d_feats == NULL) has them
+    const bool implicit0 = layer == 0 && !d_in;
+    if ((rc = stage_layer_checks(ctx, b, layer, implicit0 ? static_cast<const void *>(d_out) : d_in, implicit0 ? g.in_dim : ld_in, g.in_dim,
+                                 d_out, ld_out, hd)))
+        return rc;
+    if (implicit0 && b->d_en_pair) return fail(ctx, MPE_ERR_INVALID, "mpe_gat_layer: device-featurised rows need the implicit topology");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int n_nodes = b->n_heads + b->n_edge_nodes;
     if ((rc = gat_topology(ctx, s, b))) return rc;
-    if (layer == 0) {
+    if (implicit0) {
+        const int V = ctx->cfg.n_cameras, J = ctx->cfg.n_joints;
+        // (the attention kernels differ in what they leave for frames without a graph: such rows read 0 here)
+        if (n_nodes > 0) HIPCHK(ctx, hipMemsetAsync(ctx->act[0], 0, (size_t)n_nodes * ctx->act_ld * sizeof(float), s));
+        if (ctx->l0_grouped) {
+            HIPCHK(ctx, launch_head_features(s, ctx->d_cfg, *b, J, ctx->xc, ctx->l0_ld, 0, 0, false, ctx->cam_count, V));
+            HIPCHK(ctx, launch_group_heads(s, b->n_heads, V, b->d_head_cam, ctx->cam_count, ctx->cam_list, ctx->cfg.max_heads, true));
+        } else {
+            HIPCHK(ctx, launch_head_features(s, ctx->d_cfg, *b, J, ctx->x0, ctx->feat_ld, 0, 0, true));
+        }
+    } else if (layer == 0) {
         if ((rc = ensure_dense_workspace(ctx))) return rc;
         if ((rc = copy_rows_in(ctx, s, ctx->xdense, ctx->feat_ld, d_in, ld_in, g.in_dim, n_nodes))) return rc;
     } else if ((rc = copy_rows_in(ctx, s, ctx->act[0], ctx->act_ld, d_in, ld_in, g.in_dim, n_nodes)))
         return rc;
     AggArgs a = gat_agg_args(ctx, layer);
     int n_rows_ft2 = 0;
-    if ((rc = gat_layer_linear(ctx, s, b, layer, layer == 0 ? GAT_IN_DENSE0 : GAT_IN_ACT, &a, &n_rows_ft2))) return rc;
+    if ((rc = gat_layer_linear(ctx, s, b, layer, implicit0 ? GAT_IN_IMPLICIT : layer == 0 ? GAT_IN_DENSE0 : GAT_IN_ACT, &a, &n_rows_ft2)))
+        return rc;
     a.out_mode = activation;
     a.out = ctx->act[0];
     a.ld_out = ctx->act_ld;
@@ -2207,6 +2241,12 @@ int mpe_profile_read_bf16(mpe_ctx *ctx, double *ms, double *flop, int64_t *launc
     if (ms) *ms = ctx->bf_ms;
     if (flop) *flop = ctx->bf_flop;
     if (launches) *launches = ctx->bf_launches;
+    return MPE_OK;
+}
+
+int mpe_l0_attention_launches(mpe_ctx *ctx, int64_t *n) {
+    if (!ctx || !n) return MPE_ERR_INVALID;
+    *n = ctx->l0_attention_launches;
     return MPE_OK;
 }
 

@@ -1750,6 +1750,351 @@ hipError_t launch_gat_attention(hipStream_t s, const mpe_batch &b, int V, int ma
     return launch_aggregate(s, b, V, max_heads_per_frame, node_off, head_frame, en_frame, en_pair, a2, head_src, x_deg_cap);
 }
 
+// ---------------------------------------------------------------------------------------
+// Layer 0 with implicit topology, 40-wide heads, fp32 rows: the attention stage AND the coefficients of the head rows in one
+// launch that writes whole rows.  ft2 holds the H head rows of a frame only (H x heads*40 floats, 32 KB at 5 x 4); every
+// edge-node row is the constant row en_const_ft2 with the constant coefficients en_const_a, and every in-edge source of a head
+// other than the head itself carries that row.  One workgroup serves one slab of a frame's output rows (node order: heads, then
+// edge-nodes): it loads the head rows into LDS, computes a1 | a2 of them in the canonical order (coef40), the softmax weights of
+// its own rows, and then one thread writes one 16-byte column group, consecutive threads consecutive groups of one row -- a row
+// leaves as one contiguous run of heads*160 bytes, where k_gat_fused (one workgroup per frame and attention head) writes
+// 160-byte pieces at the row stride.  Every value is computed by the expressions of k_gat_fused / k_attn_coef in their order:
+// the same bits (tests/test_gpu_l0_attention.py).  Slabs repeat the load and the coefficients only.
+// ---------------------------------------------------------------------------------------
+#ifndef MPE_L0_SLABS
+#define MPE_L0_SLABS 1                              // workgroups per frame (profiles/layer0_attention_timing.txt)
+#endif
+#ifndef MPE_L0_THREADS
+#define MPE_L0_THREADS 512                          // eight waves share a frame's head rows: two workgroups, sixteen waves per CU
+#endif
+constexpr int L0_THREADS = MPE_L0_THREADS;
+constexpr size_t L0_LDS_LIMIT = 64 * 1024;
+
+struct L0Lds {                                      // offsets in floats
+    int hdp, r_cap;
+    size_t ft, c, al, ar, ca, a1, a2, ws, we, deg, pair, wen, total;
+};
+
+__host__ __device__ inline L0Lds l0_lds(int hmax, int V, int heads, int slabs) {
+    L0Lds o;
+    const int hd = heads * 40;
+    const int mc = hmax * hmax * (V - 1) / (2 * V) + 1;              // the caps of fused_lds_bytes (implicit topology)
+    o.hdp = hd + 4;                                                  // (+4: bank spread of the coefficient pass, as k_attn_coef)
+    o.r_cap = (hmax + mc + slabs - 1) / slabs;                       // rows of a slab
+    size_t n = 0;
+    o.ft = n, n += (size_t)hmax * o.hdp;
+    o.c = n, n += hd;
+    o.al = n, n += hd;
+    o.ar = n, n += hd;
+    o.ca = n, n += 32;
+    o.a1 = n, n += (size_t)hmax * heads;
+    o.a2 = n, n += (size_t)hmax * heads;
+    o.ws = n, n += (size_t)hmax * heads;
+    o.we = n, n += (size_t)hmax * heads;
+    o.deg = n, n += (size_t)((hmax + 3) & ~3);
+    o.pair = n, n += (size_t)((o.r_cap + 3) & ~3);
+    o.wen = n, n += (size_t)o.r_cap * heads * 3;
+    o.total = n;
+    return o;
+}
+
+// (row, column) of the items first, first + step, ... of a [rows][W] array: one division per loop instead of one per item
+struct RowCol {
+    int row, col, dq, dr, W;
+    __device__ __forceinline__ RowCol(int first, int step, int W_) : W(W_) {
+        row = first / W;
+        col = first - row * W;
+        dq = step / W;
+        dr = step - dq * W;
+    }
+    __device__ __forceinline__ void next() {
+        row += dq;
+        col += dr;
+        if (col >= W) {
+            col -= W;
+            ++row;
+        }
+    }
+};
+
+// one 16-byte column group of an edge-node row: the expression of k_gat_fused, (f1 w1 + f2 w2) + f3 w3, then the activation
+__device__ __forceinline__ float4 l0_en_group(const float4 f1, const float4 f2, const float4 f3, float w1, float w2, float w3,
+                                              int mode, float slope) {
+#pragma clang fp contract(off)
+    const float p1[4] = {f1.x, f1.y, f1.z, f1.w}, p2[4] = {f2.x, f2.y, f2.z, f2.w}, p3[4] = {f3.x, f3.y, f3.z, f3.w};
+    float r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float acc = p1[k] * w1;
+        acc = acc + p2[k] * w2;
+        acc = acc + p3[k] * w3;
+        r[k] = agg_activate(acc, mode, slope);
+    }
+    return make_float4(r[0], r[1], r[2], r[3]);
+}
+
+// One 16-byte column group of a head row at layer 0, in the order of weighted_sum8.  In-edge 0 carries the head's own row s with
+// the weight ws, each of the deg - 1 others the same row c with the same weight we, i.e. the same product m = c we.  Chain j of
+// the eight sums the in-edges j, j + 8, ... in ascending order from 0: chain 0 is ((0 + s ws) + m) + ..., a chain j >= 1 of n terms
+// is T(n) = ((0 + m) + m) + ..., and with deg = 8 q + r a chain has q + 1 terms for j < r and q otherwise.  Every addition of
+// weighted_sum8 is made, in its order; chains that are equal term by term are computed once.
+__device__ __forceinline__ float4 l0_head_group(const float4 s, float ws, const float4 c, float we, int deg, int mode, float slope) {
+#pragma clang fp contract(off)
+    const int q = deg >> 3, r = deg & 7;
+    const float sv[4] = {s.x, s.y, s.z, s.w}, cv[4] = {c.x, c.y, c.z, c.w};
+    float m[4], tq[4], tq1[4], a0[4], o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        m[k] = cv[k] * we;
+        tq[k] = 0.f;
+    }
+    for (int n = 0; n < q; ++n)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tq[k] = tq[k] + m[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        tq1[k] = tq[k] + m[k];
+        const float p0 = sv[k] * ws;
+        a0[k] = 0.f + p0;
+    }
+    const int n0 = q + (r > 0 ? 1 : 0);
+    for (int n = 1; n < n0; ++n)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a0[k] = a0[k] + m[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float a1 = 1 < r ? tq1[k] : tq[k], a2 = 2 < r ? tq1[k] : tq[k], a3 = 3 < r ? tq1[k] : tq[k];
+        const float a4 = 4 < r ? tq1[k] : tq[k], a5 = 5 < r ? tq1[k] : tq[k], a6 = 6 < r ? tq1[k] : tq[k], a7 = 7 < r ? tq1[k] : tq[k];
+        const float x = ((a0[k] + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
+        o[k] = agg_activate(x, mode, slope);
+    }
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+template <int G>
+__global__ __launch_bounds__(L0_THREADS) void k_l0_attention(int V, int hmax, int slabs, const int32_t *__restrict__ head_off,
+                                                      const int32_t *__restrict__ en_off, const int32_t *__restrict__ slot_n,
+                                                      const int32_t *__restrict__ node_off, const int32_t *__restrict__ en_pair,
+                                                      const float *__restrict__ attn_l, const float *__restrict__ attn_r,
+                                                      AggArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) float s_l0[];
+    // the slabs of a frame on one XCD (workgroups with equal id % 8 share an L2): they read the same head rows
+    const int bid = blockIdx.x, nwg = gridDim.x;
+    const int xcd = bid & 7, xq = nwg >> 3, xr = nwg & 7;
+    const int vid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+    const int f = vid / slabs, slab = vid - f * slabs;
+    const int heads = a.heads, hd = heads * 40, DV = hd / 4;
+    const int hb = head_off[f], H = head_off[f + 1] - hb;
+    const int eb = en_off[f], M = en_off[f + 1] - eb;
+    const int N = H + M, nb = node_off[f];
+    const L0Lds o = l0_lds(hmax, V, heads, slabs);
+    // frames without a graph produce nothing; a frame beyond max_heads_per_frame (k_topology raised the status flag) neither:
+    // what k_gat_fused does with them when it writes feature rows
+    if (M <= 0 || H > hmax || N > o.r_cap * slabs) return;
+    const int R = (N + slabs - 1) / slabs;                           // rows of this frame's slabs (<= r_cap)
+    const int n0 = min(N, slab * R), n1 = min(N, n0 + R);
+    const int m0 = max(n0, H) - H, m1 = max(n1, H) - H;              // edge-nodes [m0, m1), heads [n0, min(n1, H))
+    const int hp = o.hdp;
+    float *s_ft = s_l0 + o.ft;                      // [hmax][hdp] head rows of the frame
+    float *s_c = s_l0 + o.c;                        // [hd] the edge-nodes' row
+    float *s_al = s_l0 + o.al, *s_ar = s_l0 + o.ar; // [hd] attn_l, attn_r
+    float *s_ca = s_l0 + o.ca;                      // [32] a1 | a2 of that row
+    float *s_a1 = s_l0 + o.a1, *s_a2 = s_l0 + o.a2; // [hmax][heads]
+    float *s_ws = s_l0 + o.ws, *s_we = s_l0 + o.we; // [hmax][heads] softmax weight of a head's self loop / of each of its other in-edges
+    int *s_deg = reinterpret_cast<int *>(s_l0 + o.deg);              // [hmax] in-degree
+    int *s_pair = reinterpret_cast<int *>(s_l0 + o.pair);            // [r_cap] h1 << 16 | h2
+    float *s_wen = s_l0 + o.wen;                    // [r_cap][heads][3]
+    const int t = threadIdx.x;
+
+    // front: head rows (four 16-byte requests in flight per thread), constants, pairs of the slab, in-degrees
+    {
+        const int total = H * DV;
+        RowCol p(t, L0_THREADS, DV);
+        for (int i0 = t; i0 < total; i0 += 4 * L0_THREADS) {
+            float4 v[4];
+            int off[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool in = i0 + u * L0_THREADS < total;
+                const int r = in ? p.row : 0, cg = in ? p.col : 0;            // (requests past the end repeat the first chunk)
+                v[u] = *reinterpret_cast<const float4 *>(a.ft2 + (size_t)(hb + r) * a.ld + cg * 4);
+                off[u] = in ? r * hp + cg * 4 : -1;
+                p.next();
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (off[u] >= 0) *reinterpret_cast<float4 *>(s_ft + off[u]) = v[u];
+        }
+        for (int i = t; i < DV; i += L0_THREADS) {
+            *reinterpret_cast<float4 *>(s_c + i * 4) = *reinterpret_cast<const float4 *>(a.en_const_ft2 + i * 4);
+            *reinterpret_cast<float4 *>(s_al + i * 4) = *reinterpret_cast<const float4 *>(attn_l + i * 4);
+            *reinterpret_cast<float4 *>(s_ar + i * 4) = *reinterpret_cast<const float4 *>(attn_r + i * 4);
+        }
+        if (t < 32) s_ca[t] = a.en_const_a[t];
+        for (int m = m0 + t; m < m1; m += L0_THREADS)
+            s_pair[m - m0] = (en_pair[2 * (size_t)(eb + m)] << 16) | en_pair[2 * (size_t)(eb + m) + 1];
+        for (int h = t; h < H; h += L0_THREADS) {
+            // head h sits in the camera slot s with start[s] <= h < start[s] + n[s]; its in-edges: itself and one edge-node per
+            // head of the other slots
+            const int32_t *sn = slot_n + (size_t)f * V;
+            int acc = 0, ns = 0;
+            for (int s = 0; s < V; ++s) {
+                const int n = sn[s];
+                if (h >= acc && h < acc + n) ns = n;
+                acc += n;
+            }
+            s_deg[h] = 1 + H - ns;
+        }
+    }
+    __syncthreads();
+    // a1 | a2 of the head rows, all attention heads, in the canonical order
+    {
+        RowCol p(t, L0_THREADS, heads);
+        for (int i = t; i < H * heads; i += L0_THREADS, p.next()) {
+            const int hh = p.col;
+            const float *fv = s_ft + p.row * hp + hh * 40;
+            float v[40];
+#pragma unroll
+            for (int q = 0; q < 10; ++q) {
+                const float4 x = *reinterpret_cast<const float4 *>(fv + 4 * q);
+                v[4 * q] = x.x;
+                v[4 * q + 1] = x.y;
+                v[4 * q + 2] = x.z;
+                v[4 * q + 3] = x.w;
+            }
+            float x1, x2;
+            coef40([&](int d) { return v[d]; }, s_al + hh * 40, s_ar + hh * 40, hh & 1, x1, x2);
+            s_a1[i] = x1;
+            s_a2[i] = x2;
+        }
+    }
+    __syncthreads();
+    // rows out: a thread owns two 16-byte column groups half a row apart (one pair, one in-degree and one row address per 32 bytes;
+    // the lanes of a store instruction still write consecutive 16 bytes of a row), and walks the rows of the slab
+    const int P = DV / 2;                           // (DV = 10 heads: even)
+    const int RP = L0_THREADS / P;                         // rows per pass of the workgroup
+    const int rsub = t / P, cp = t - rsub * P;
+    const int dA = cp * 4, dB = (cp + P) * 4;
+#ifdef MPE_L0_TIMING_ONLY
+    // DIAGNOSTIC builds only (make exp EXPFLAGS=-DMPE_L0_TIMING_ONLY): the front, then whole-row stores of a constant -- what the
+    // access pattern alone costs (profiles/layer0_attention_timing.txt)
+    if (rsub < RP) {
+        const float x = s_a1[0];
+        float *dst = a.out + (size_t)(nb + n0 + rsub) * a.ld_out;
+        for (int node = n0 + rsub; node < n1; node += RP, dst += (size_t)RP * a.ld_out) {
+            *reinterpret_cast<float4 *>(dst + dA) = make_float4(x, x, x, x);
+            *reinterpret_cast<float4 *>(dst + dB) = make_float4(x, x, x, x);
+        }
+    }
+    return;
+#endif
+    // softmax weights.  Edge-node X: in-edges (h1, h2, X), one thread per (X, attention head).
+    {
+        RowCol p(t, L0_THREADS, heads);
+        for (int i = t; i < (m1 - m0) * heads; i += L0_THREADS, p.next()) {
+            const int hh = p.col;
+            const int pr = s_pair[p.row];
+            const int h1 = pr >> 16, h2 = pr & 0xFFFF;
+            const float a2v = s_ca[16 + hh];
+            float e1 = s_a1[h1 * heads + hh] + a2v, e2 = s_a1[h2 * heads + hh] + a2v, e3 = s_ca[hh] + a2v;
+            e1 = e1 > 0.f ? e1 : e1 * a.alpha;
+            e2 = e2 > 0.f ? e2 : e2 * a.alpha;
+            e3 = e3 > 0.f ? e3 : e3 * a.alpha;
+            const float mx = fmaxf(fmaxf(e1, e2), e3);
+            const float x1 = expf(e1 - mx), x2 = expf(e2 - mx), x3 = expf(e3 - mx);
+            const float sum = (x1 + x2) + x3;
+            s_wen[i * 3 + 0] = x1 / sum;
+            s_wen[i * 3 + 1] = x2 / sum;
+            s_wen[i * 3 + 2] = x3 / sum;
+        }
+    }
+    // Head h: one lane group per (head, attention head), the fixed-shape reductions of k_gat_fused: lane j takes the in-edges
+    // j, j + G, ... in ascending order.  In-edge 0 is the self loop, every other source is an edge-node (a1 = en_const_a).
+    {
+        const int gl = t & (G - 1);
+        const int hend = min(n1, H);
+        RowCol p(n0 * heads + t / G, L0_THREADS / G, heads);
+        for (int i = n0 * heads + t / G; i < hend * heads; i += L0_THREADS / G, p.next()) {
+            const int hh = p.col;
+            const int deg = s_deg[p.row];
+            const float a2v = s_a2[i];
+            float xs = s_a1[i] + a2v, xe = s_ca[hh] + a2v;
+            xs = xs > 0.f ? xs : xs * a.alpha;
+            xe = xe > 0.f ? xe : xe * a.alpha;
+            float mx = -INFINITY;
+            for (int e = gl; e < deg; e += G) mx = fmaxf(mx, e == 0 ? xs : xe);
+            mx = group_max<G>(mx);
+            const float es = expf(xs - mx), ee = expf(xe - mx);
+            float sum = 0.f;
+            for (int e = gl; e < deg; e += G) sum = sum + (e == 0 ? es : ee);
+            sum = group_sum<G>(sum);
+            if (gl == 0) {
+                s_ws[i] = es / sum;
+                s_we[i] = ee / sum;
+            }
+        }
+    }
+    __syncthreads();
+    if (rsub < RP) {
+        const int hhA = dA / 40, hhB = dB / 40;
+        const float4 cA = *reinterpret_cast<const float4 *>(s_c + dA), cB = *reinterpret_cast<const float4 *>(s_c + dB);
+        const int mode = a.out_mode;
+        const float slope = a.out_slope;
+        float *dst = a.out + (size_t)(nb + n0 + rsub) * a.ld_out;
+        for (int node = n0 + rsub; node < n1; node += RP, dst += (size_t)RP * a.ld_out) {
+            float4 oA, oB;
+            if (node >= H) {
+                const int ml = node - H - m0;
+                const int pr = s_pair[ml];
+                const float *p1 = s_ft + (pr >> 16) * hp, *p2 = s_ft + (pr & 0xFFFF) * hp;
+                const float *wA = s_wen + (ml * heads + hhA) * 3, *wB = s_wen + (ml * heads + hhB) * 3;
+                oA = l0_en_group(*reinterpret_cast<const float4 *>(p1 + dA), *reinterpret_cast<const float4 *>(p2 + dA), cA, wA[0], wA[1],
+                                 wA[2], mode, slope);
+                oB = l0_en_group(*reinterpret_cast<const float4 *>(p1 + dB), *reinterpret_cast<const float4 *>(p2 + dB), cB, wB[0], wB[1],
+                                 wB[2], mode, slope);
+            } else {
+                const int deg = s_deg[node];
+                const float *sv = s_ft + node * hp;
+                const int iA = node * heads + hhA, iB = node * heads + hhB;
+                oA = l0_head_group(*reinterpret_cast<const float4 *>(sv + dA), s_ws[iA], cA, s_we[iA], deg, mode, slope);
+                oB = l0_head_group(*reinterpret_cast<const float4 *>(sv + dB), s_ws[iB], cB, s_we[iB], deg, mode, slope);
+            }
+            *reinterpret_cast<float4 *>(dst + dA) = oA;
+            *reinterpret_cast<float4 *>(dst + dB) = oB;
+        }
+    }
+}
+
+// Can layer 0 of this context take k_l0_attention?  (the routing itself is gat_layer_linear's, api.hip)
+bool l0_attention_available(int max_heads_per_frame, int V, int heads, int out_dim) {
+    if (out_dim != 40 || heads < 1 || heads > 16 || V < 2 || max_heads_per_frame < 1) return false;
+    const int mc = max_heads_per_frame * max_heads_per_frame * (V - 1) / (2 * V) + 1;
+    if (max_heads_per_frame + mc > 65535) return false;                   // (pairs travel as two 16-bit halves)
+    return l0_lds(max_heads_per_frame, V, heads, MPE_L0_SLABS).total * sizeof(float) <= L0_LDS_LIMIT;
+}
+
+hipError_t launch_l0_attention(hipStream_t s, const mpe_batch &b, int V, int max_heads_per_frame, const int32_t *node_off,
+                               const int32_t *en_pair, const float *attn_l, const float *attn_r, const AggArgs &a) {
+    if (b.n_frames <= 0) return hipSuccess;
+    if (b.d_en_pair || !a.en_const_ft2 || !a.en_const_a || a.ft_half || a.score_mode || a.out_pl || a.ld % 4 || a.ld_out % 4 ||
+        !l0_attention_available(max_heads_per_frame, V, a.heads, a.out_dim))
+        return hipErrorInvalidValue;
+    const int slabs = MPE_L0_SLABS;
+    const size_t shm = l0_lds(max_heads_per_frame, V, a.heads, slabs).total * sizeof(float);
+    const int max_deg = max_heads_per_frame + 1;
+    const dim3 grid(b.n_frames * slabs);
+    // the lane-group rule of the head softmax (launch_gat_attention): sixteen lanes serve in-degrees up to 32, thirty-two up to 64
+#define MPE_L0(G_)                                                                                                   \
+    hipLaunchKernelGGL((k_l0_attention<G_>), grid, dim3(L0_THREADS), shm, s, V, max_heads_per_frame, slabs, b.d_frame_head_off, \
+                       b.d_frame_en_off, b.d_slot_n, node_off, en_pair, attn_l, attn_r, a)
+    if (max_deg <= 32) MPE_L0(16);
+    else if (max_deg <= 64) MPE_L0(32);
+    else MPE_L0(64);
+#undef MPE_L0
+    return hipGetLastError();
+}
+
 // the general kernels' two halves as one launch (small batches; implicit topology)
 hipError_t launch_lat_attention(hipStream_t s, const mpe_batch &b, int V, int max_heads_per_frame, const int32_t *node_off,
                                 const int32_t *head_frame, const int32_t *en_frame, const int32_t *en_pair, const AggArgs &a,

@@ -137,6 +137,7 @@ struct mpe_ctx {
     bool l0_grouped = true;
     float *act[3] = {nullptr, nullptr, nullptr};   // [max_nodes][act_ld]
     float *a12 = nullptr;          // [max_nodes][2*16]
+    int64_t l0_attention_launches = 0;   // launches of k_l0_attention this context queued (mpe_l0_attention_launches; counted on the host)
     // small batches: every cross-camera pair of a batch solved beside the clustering (cluster.hip: k_lat_tail) for the row kernel of the
     // SAME batch to fetch: two buffers [heads][hmax][J][3] f64 written in turn, and ONE note of the batch whose pairs the last
     // mpe_match_batch solved -- kept until the next batch call, used once (pair_handoff.h has the rule)
@@ -393,7 +394,12 @@ struct AggArgs {
     const float *attn_l, *attn_r;   // [heads*out_dim]: for the kernels that compute a1 | a2 themselves when a12_ready == 0 (general path, small batches)
     unsigned short *out_pl;    // small batches (lat.hip): the output as three bf16 planes [3][rows][ld_out] INSTEAD of fp32 rows
     size_t out_pl_plane;       // plane stride in elements
+    int l0_whole_rows;         // layer 0 routed to k_l0_attention (gat_layer_linear): a12 was NOT filled, the kernel computes a1 | a2 itself
 };
+// layer 0, implicit topology, 40-wide heads, fp32 rows: coefficients + attention in one launch that writes whole rows
+bool l0_attention_available(int max_heads_per_frame, int V, int heads, int out_dim);
+hipError_t launch_l0_attention(hipStream_t s, const mpe_batch &b, int V, int max_heads_per_frame, const int32_t *node_off,
+                               const int32_t *en_pair, const float *attn_l, const float *attn_r, const AggArgs &a);
 hipError_t launch_aggregate(hipStream_t s, const mpe_batch &b, int V, int max_heads_per_frame,
                             const int32_t *node_off, const int32_t *head_frame, const int32_t *en_frame,
                             const int32_t *en_pair, const AggArgs &a, const uint16_t *head_src, int x_deg_cap = 0);

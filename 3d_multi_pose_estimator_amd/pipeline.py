@@ -898,13 +898,25 @@ class Engine:
 
     def gat_layer(self, db, layer, x, activation=0):
         """One GraphAttention2 layer + the activation GAT2.forward applies (mpe_gat_layer).
-        x [n_nodes, in_dim] rows in node order -> [n_nodes, heads*out_dim]."""
-        x = x.to(self.device, torch.float32).contiguous()
+        x [n_nodes, in_dim] rows in node order -> [n_nodes, heads*out_dim].  Layer 0 with x = None: the rows are featurised on
+        the device, the production route of layer 0 (implicit topology)."""
         _, nh, od = self.gat_dims[layer]
+        if x is None:
+            out = torch.empty((db.n_heads + db.n_edge_nodes, nh * od), dtype=torch.float32, device=self.device)
+            self._chk(self.lib.mpe_gat_layer(self.ctx, self._stream(), C.byref(db.struct), layer, None, 0,
+                                             _ptr(out), out.shape[1], int(activation)))
+            return out
+        x = x.to(self.device, torch.float32).contiguous()
         out = torch.empty((x.shape[0], nh * od), dtype=torch.float32, device=self.device)
         self._chk(self.lib.mpe_gat_layer(self.ctx, self._stream(), C.byref(db.struct), layer, _ptr(x), x.shape[1],
                                          _ptr(out), out.shape[1], int(activation)))
         return out
+
+    def l0_attention_launches(self):
+        """How often this engine's context queued the whole-row layer-0 attention launch (mpe_l0_attention_launches)."""
+        n = C.c_int64()
+        self._chk(self.lib.mpe_l0_attention_launches(self.ctx, C.byref(n)))
+        return n.value
 
     def edge_softmax_aggregate(self, db, layer, ft2):
         """The DGL half of a layer (gat2.py:57-66): ft2 [n_nodes, heads*out_dim] -> aggregated rows."""

@@ -1132,7 +1132,9 @@ int mpe_set_gat_output(mpe_ctx *ctx, int32_t mode);
  * flattened output (:141-147).  d_in [n_nodes][ld_in] holds the layer's input rows in node order
  * (frame by frame: heads, then edge-nodes; in_dim columns used), d_out [n_nodes][ld_out] receives
  * heads*out_dim columns.  activation: 0 = LeakyReLU(hidden slope), 1 = sigmoid, 2 = none.
- * Layer 0 takes dense F-wide rows (no de-duplication of the constant edge-node rows). */
+ * Layer 0 takes dense F-wide rows (no de-duplication of the constant edge-node rows); with d_in == NULL (ld_in ignored) it
+ * featurises the rows on the device as mpe_gat_forward(d_feats == NULL) does (implicit topology only) -- the production route of
+ * layer 0; rows of frames without a graph then read 0 or the head's own transformed row, depending on the attention kernel. */
 int mpe_gat_layer(mpe_ctx *ctx, void *stream, const mpe_batch *b, int32_t layer, const float *d_in, int32_t ld_in,
                   float *d_out, int32_t ld_out, int32_t activation);
 
@@ -1806,6 +1808,11 @@ int mpe_profile_read(mpe_ctx *ctx, double *gemm_ms, double *gemm_flop, int64_t *
 int mpe_profile_read_split(mpe_ctx *ctx, double *ms, double *flop, int64_t *launches);
 /* ... and the plain bf16 launches of the reduced-precision modes (configs[4]): one bf16 product per product, priced against the bf16 peak */
 int mpe_profile_read_bf16(mpe_ctx *ctx, double *ms, double *flop, int64_t *launches);
+/* How often this context has queued the whole-row layer-0 attention launch (k_l0_attention: layer 0 on device-featurised fp32
+ * rows, implicit topology, 40-wide heads, none of MPE_NO_FUSED_ATTENTION / MPE_NO_COEF_EPILOGUE / MPE_FUSED_NO_OVERLAP /
+ * MPE_NO_HEAD_SRC_TABLE set) since it was created; counted on the host.  Every other layer-0 call takes the coefficient kernel
+ * and the attention kernels of the other layers. */
+int mpe_l0_attention_launches(mpe_ctx *ctx, int64_t *n);
 
 #ifdef __cplusplus
 }

@@ -532,7 +532,9 @@ static bool last_layer_fusable(const mpe_ctx *ctx, const GatLayer &g) {
 
 // fc1 -> LeakyReLU(alpha) -> fc2 of layer l (gat2.py:53-55): leaves ft2 in a->ft2 / n_rows_ft2
 // fuse_last: the caller is the production route (device-featurised rows) and lets the last layer take the fused launch
-int gat_layer_linear(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, int l, GatInput in, AggArgs *a, int *n_rows_ft2, bool fuse_last = false) {
+// clear_fc1_pad: the caller is a stage entry point (one layer on caller rows), see the GAT_IN_ACT branch
+int gat_layer_linear(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, int l, GatInput in, AggArgs *a, int *n_rows_ft2, bool fuse_last = false,
+                     bool clear_fc1_pad = false) {
     GatLayer &g = ctx->gat[l];
     const int V = ctx->cfg.n_cameras, J = ctx->cfg.n_joints;
     const int n_nodes = b->n_heads + b->n_edge_nodes;
@@ -602,6 +604,13 @@ int gat_layer_linear(mpe_ctx *ctx, hipStream_t s, const mpe_batch *b, int l, Gat
         a->ft2 = ctx->act[2];
         *n_rows_ft2 = n_nodes;
     } else {
+        // fc2 reads act[1] over fc2.ldw columns and fc1 writes fc1.out_dim of them (150 of 160 in the deployed last layer).  Inside a
+        // forward pass the columns between hold the same rows of this batch's wider layers: finite wherever the row is, and they meet
+        // zero weights.  A stage entry point finds there what the call BEFORE it left -- rows of another batch, a NaN of a bad
+        // detection included, and 0 * NaN is NaN -- so it clears them (tests/test_gpu_nonfinite.py: Test B, gat_layer first).
+        if (clear_fc1_pad && n_nodes > 0 && g.fc2.ldw > g.fc1.out_dim)
+            HIPCHK(ctx, hipMemset2DAsync(ctx->act[1] + g.fc1.out_dim, (size_t)ctx->act_ld * sizeof(float), 0,
+                                         (size_t)(g.fc2.ldw - g.fc1.out_dim) * sizeof(float), n_nodes, s));
         if ((rc = gat_linear(ctx, s, ctx->act[0], ctx->act_ld, g.fc1, ctx->act[1], ctx->act_ld, n_nodes, nullptr,
                              true, ctx->gat_alpha, false)))
             return rc;
@@ -1228,7 +1237,7 @@ int mpe_gat_layer(mpe_ctx *ctx, void *stream, const mpe_batch *b, int32_t layer,
         return rc;
     AggArgs a = gat_agg_args(ctx, layer);
     int n_rows_ft2 = 0;
-    if ((rc = gat_layer_linear(ctx, s, b, layer, implicit0 ? GAT_IN_IMPLICIT : layer == 0 ? GAT_IN_DENSE0 : GAT_IN_ACT, &a, &n_rows_ft2)))
+    if ((rc = gat_layer_linear(ctx, s, b, layer, implicit0 ? GAT_IN_IMPLICIT : layer == 0 ? GAT_IN_DENSE0 : GAT_IN_ACT, &a, &n_rows_ft2, false, true)))
         return rc;
     a.out_mode = activation;
     a.out = ctx->act[0];

@@ -203,6 +203,14 @@ int mpe_set_precision(mpe_ctx *ctx, int32_t gat_acc64, int32_t mlp_acc64);
  *   d_scores   [n_edge_nodes]  sigmoid output of every edge-node (may be NULL)
  *   d_persons  [n_frames][Pcap][V] frame-local head id per camera, -1 = None
  *   d_n_persons[n_frames]
+ * Non-finite input.  A detection may be inf, NaN, or finite as a double and infinite as a float (1e39 is a legal JSON number;
+ *   d_xy is f64 and the network's rows are f32).  Values of a joint whose bit in d_joint_mask is CLEARED are never read: whatever
+ *   they hold, no result of any frame changes.  A non-finite value under a SET bit affects its own frame only: every other frame
+ *   of the batch keeps every bit of its scores, persons and count.  The frame's own scores may be NaN (a NaN score is below every
+ *   threshold); its person table stays structurally valid -- 0 <= n <= Pcap, every entry -1 or a frame-local head of that column's
+ *   camera, no head twice.  The call returns MPE_OK and raises no status bit.  Nothing survives into later calls on the context:
+ *   the batches after a bad one give the bits a fresh context gives (tests/test_gpu_nonfinite.py; which workspace columns that
+ *   rests on: DESIGN.md 5.1).
  * A batch of zero frames is accepted by every batch entry point and does nothing. */
 int mpe_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b,
                     float *d_scores, int32_t *d_persons, int32_t *d_n_persons);
@@ -217,6 +225,11 @@ int mpe_match_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b,
  * generation and the three counts equal) and the d_persons / d_n_persons arrays that call wrote.  The hand-off is used once: any batch
  * entry point of the context (every function that takes an mpe_batch, this one included) ends it, and everything else solves its pairs
  * itself.  Results never depend on which of the two happens.
+ * Non-finite input.  As at mpe_match_batch, per PERSON: values under a cleared mask bit are never read; a non-finite value under a
+ *   set bit affects the slots of the persons that hold its head and no other slot of the frame or the batch (poses and flags, bit
+ *   for bit).  d_valid of such a slot is what the reference's own test sum(|row|) > 1 gives on its row: 0 when the row holds a NaN,
+ *   1 when it holds infinities only; the pose under a set flag is then whatever the network makes of the row.  MPE_OK, no status
+ *   bit, and nothing survives into later calls (rows of NaN in the MLP workspaces included, with more or fewer persons after).
  * THE CALLER'S RULE.  One thing the library cannot see: new contents written into the same arrays between the two calls (a copy into
  * a reused arena, a kernel of the caller's) with equal counts, and persons at the same address.  A caller that rewrites a batch's
  * arrays between mpe_match_batch and mpe_mlp3d_batch -- instead of matching the new contents first, as the pipeline's call order does --
@@ -229,6 +242,9 @@ int mpe_mlp3d_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b,
 /* 3D stage B: caller gather + triangulate (metrics_from_triangulation.py:234-272,
  * pose_estimator_utils.py:52-75).
  *   d_poses [n_frames][Pcap][J][3] f64, d_joint_valid [n_frames][Pcap][J] 1 = joint emitted
+ * Non-finite input.  As at mpe_match_batch, per person: values under a cleared mask bit are never read; a non-finite value under a
+ *   set bit affects the joints of the persons that hold its head (the pair solves run a fixed number of sweeps, the median search
+ *   ends without a result on NaN) and no other slot.  MPE_OK, no status bit; the call keeps nothing on the context.
  *   flags bit 0: emit every triangulated joint (what `triangulate` itself returns); otherwise
  *   joints outside parameters.used_joints come back as zeros, as the caller's copy does.
  *   flags bit 1: gather only joints whose values[0] (the joint id) is > 0, as the caller in
@@ -1122,6 +1138,9 @@ int mpe_dense_rows(mpe_ctx *ctx, void *stream, const mpe_batch *b, float *d_rows
  * node order (frame by frame: heads, then edge-nodes), as GAT2.forward(inputs, g) receives.
  * d_scores_en [n_edge_nodes]; optional d_scores_heads [n_heads] (the reference also evaluates
  * the last layer at head nodes; unused downstream). */
+/* Non-finite input (d_feats == NULL).  As at mpe_match_batch: values under a cleared mask bit are never read; a non-finite value
+ * under a set bit affects the scores (edge-nodes and heads) of its own frame only; MPE_OK, no status bit; nothing survives into
+ * later calls on the context.  Caller-provided rows: a row of d_feats affects the frame it belongs to. */
 int mpe_gat_forward(mpe_ctx *ctx, void *stream, const mpe_batch *b, const float *d_feats, int32_t ld_feats,
                     float *d_scores_en, float *d_scores_heads);
 /* Activation of the last GAT layer: 1 = sigmoid (final_activation = nn.Sigmoid(), the deployed
@@ -1134,7 +1153,11 @@ int mpe_set_gat_output(mpe_ctx *ctx, int32_t mode);
  * heads*out_dim columns.  activation: 0 = LeakyReLU(hidden slope), 1 = sigmoid, 2 = none.
  * Layer 0 takes dense F-wide rows (no de-duplication of the constant edge-node rows); with d_in == NULL (ld_in ignored) it
  * featurises the rows on the device as mpe_gat_forward(d_feats == NULL) does (implicit topology only) -- the production route of
- * layer 0; rows of frames without a graph then read 0 or the head's own transformed row, depending on the attention kernel. */
+ * layer 0; rows of frames without a graph then read 0 or the head's own transformed row, depending on the attention kernel.
+ * Non-finite input.  As at mpe_match_batch: with d_in == NULL values under a cleared mask bit are never read and a non-finite value
+ * under a set bit affects the rows of its own frame only; a non-finite row of d_in affects the rows of the frame it belongs to.
+ * MPE_OK, no status bit.  Nothing survives into later calls, and nothing an earlier call left in the workspaces reaches this one:
+ * the rows are laid over cleared workspace rows, pad columns of the layer's own fc1 output included. */
 int mpe_gat_layer(mpe_ctx *ctx, void *stream, const mpe_batch *b, int32_t layer, const float *d_in, int32_t ld_in,
                   float *d_out, int32_t ld_out, int32_t activation);
 
@@ -1167,7 +1190,10 @@ int mpe_set_threshold(mpe_ctx *ctx, float threshold);
 int mpe_cluster_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const float *d_scores,
                       int32_t *d_persons, int32_t *d_n_persons);
 
-/* MLP input rows only: d_rows [n_frames*Pcap][ld_rows] f32 (row r = frame*Pcap + p). */
+/* MLP input rows only: d_rows [n_frames*Pcap][ld_rows] f32 (row r = frame*Pcap + p).
+ * Non-finite input.  As at mpe_mlp3d_batch: values under a cleared mask bit are never read; a non-finite value under a set bit
+ * reaches the rows of the persons that hold its head and no other row; d_valid of such a row is the reference's sum(|row|) > 1 on
+ * it (a NaN in the row: 0; infinities only: 1).  MPE_OK, no status bit; the call keeps nothing on the context. */
 int mpe_mlp_input_rows(mpe_ctx *ctx, void *stream, const mpe_batch *b, const int32_t *d_persons,
                        const int32_t *d_n_persons, float *d_rows, int32_t ld_rows, uint8_t *d_valid);
 /* PoseEstimatorMLP.forward on d_x [m][ld_x] -> d_y [m][ld_y] (out_dim columns written, the rest of a row kept; no x10).

@@ -10,6 +10,7 @@
 #include "mpe_internal.h"
 #include "assign_int.h"
 #include "relink_config.h"
+#include "fmt_double.h"               // MPE_FMT_MAX_LEN
 
 using namespace mpe;
 
@@ -2840,6 +2841,65 @@ int mpe_refine_timed_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const
     if ((int64_t)a->n_frames * a->pcap > 0x7FFFFFFFLL)             // one workgroup per 1 .. 8 rows, no stride loop
         return fail(ctx, MPE_ERR_CAPACITY, "mpe_refine_timed_batch: %d frames of %d rows are more workgroups than a launch takes", a->n_frames, a->pcap);
     HIPCHK(ctx, launch_refine_timed(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
+    return MPE_OK;
+}
+
+// ---- the pose document (jsonwrite.hip) ----
+size_t mpe_json_write_bound(int32_t n_frames, int32_t pcap, int32_t n_joints, int32_t with_ids) {
+    if (n_frames < 0 || pcap < 0 || n_joints < 0) return 0;
+    // `"jj": [x, y, z], ` with three 24-byte tokens; `{}, ` around a row; an id of 11 bytes with `, `; a frame number of 20
+    const size_t joint = 4 + 8 + 3 * MPE_FMT_MAX_LEN + 2, row = 2 + 2 + (size_t)n_joints * joint;
+    const size_t line = 10 + 20 + (with_ids ? 10 + (size_t)pcap * 13 + 1 : 0) + 13 + (size_t)pcap * row + 3;
+    return (size_t)n_frames * line;
+}
+
+size_t mpe_json_write_scratch_bytes(int32_t n_frames, int32_t pcap, int32_t n_joints) {
+    if (n_frames < 0 || pcap < 0 || n_joints < 0) return 0;
+    return json_write_scratch_bytes(n_frames, pcap, n_joints);
+}
+
+int mpe_json_write_launches(mpe_ctx *ctx, int64_t *n) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!n) return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_launches: NULL argument");
+    *n = ctx->json_write_launches;
+    return MPE_OK;
+}
+
+int mpe_json_write_poses(mpe_ctx *ctx, void *stream, const mpe_json_write_args *a) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: NULL argument");
+    DeviceGuard dg(ctx);
+    if (a->n_joints != ctx->cfg.n_joints || a->pcap < 1 || (a->pose_f64 & ~1) || (a->joint_flags & ~1))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: joints %d (the context has %d) / pcap %d / pose_f64 %d / joint_flags %d", a->n_joints,
+                    ctx->cfg.n_joints, a->pcap, a->pose_f64, a->joint_flags);
+    if (a->n_frames < 0 || a->frame_start < 0 || a->frame_start > ((int64_t)1 << 62))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: n_frames %d / frame_start %lld", a->n_frames, (long long)a->frame_start);
+    if (!(fabs(a->scale) < HUGE_VAL)) return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: scale %g is not finite", a->scale);
+    if (a->text_cap >= ((uint64_t)1 << 32))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: text_cap %llu; the extents are 32-bit offsets", (unsigned long long)a->text_cap);
+    if (a->pcap > MPE_JSON_WRITE_MAX_PERSONS) return fail(ctx, MPE_ERR_CAPACITY, "mpe_json_write_poses: pcap %d over %d", a->pcap, MPE_JSON_WRITE_MAX_PERSONS);
+    if (a->n_frames > (1 << 23)) return fail(ctx, MPE_ERR_CAPACITY, "mpe_json_write_poses: %d frames over 2^23 per call", a->n_frames);
+    if ((int64_t)a->n_frames * a->pcap * a->n_joints * 3 >= ((int64_t)1 << 31))
+        return fail(ctx, MPE_ERR_CAPACITY, "mpe_json_write_poses: %d frames of %d rows are 2^31 coordinates or more", a->n_frames, a->pcap);
+    if (!a->d_frame_off || !a->d_total || (a->text_cap && !a->d_text)) return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: NULL argument");
+    if (a->n_frames > 0) {
+        if (!a->d_poses || !a->d_flags || !a->d_n_persons || !a->d_text || !a->d_bodies_extent || !a->d_rows_written || !a->d_status || !a->d_scratch)
+            return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: NULL argument");
+        const size_t need = json_write_scratch_bytes(a->n_frames, a->pcap, a->n_joints);
+        if (a->scratch_bytes < need || (reinterpret_cast<uintptr_t>(a->d_scratch) & 15u))
+            return fail(ctx, MPE_ERR_INVALID, "mpe_json_write_poses: scratch of %zu bytes, %zu needed, 16-byte aligned", a->scratch_bytes, need);
+    }
+    HIPCHK(ctx, launch_json_write(static_cast<hipStream_t>(stream), *a, &ctx->json_write_launches));
+    return MPE_OK;
+}
+
+int mpe_format_f64(mpe_ctx *ctx, void *stream, const double *d_values, int64_t n, char *d_slots, uint8_t *d_len) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(ctx, MPE_ERR_INVALID, "mpe_format_f64: n %lld outside 0 .. 2^31 - 1", (long long)n);
+    if (n == 0) return MPE_OK;
+    if (!d_values || !d_slots || !d_len) return fail(ctx, MPE_ERR_INVALID, "mpe_format_f64: NULL argument");
+    DeviceGuard dg(ctx);
+    HIPCHK(ctx, launch_format_f64(static_cast<hipStream_t>(stream), d_values, n, d_slots, d_len));
     return MPE_OK;
 }
 

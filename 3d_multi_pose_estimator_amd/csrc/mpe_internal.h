@@ -137,6 +137,7 @@ struct mpe_ctx {
     bool l0_grouped = true;
     float *act[3] = {nullptr, nullptr, nullptr};   // [max_nodes][act_ld]
     float *a12 = nullptr;          // [max_nodes][2*16]
+    int64_t json_write_launches = 0;     // kernels queued for mpe_json_write_poses (mpe_json_write_launches; counted on the host)
     int64_t l0_attention_launches = 0;   // launches of k_l0_attention this context queued (mpe_l0_attention_launches; counted on the host)
     // small batches: every cross-camera pair of a batch solved beside the clustering (cluster.hip: k_lat_tail) for the row kernel of the
     // SAME batch to fetch: two buffers [heads][hmax][J][3] f64 written in turn, and ONE note of the batch whose pairs the last
@@ -459,6 +460,11 @@ hipError_t launch_track(hipStream_t s, mpe_track_state *st, const mpe_track_args
 // smooth.hip
 hipError_t launch_smooth_reset(hipStream_t s, mpe_smooth_state *st);
 hipError_t launch_smooth(hipStream_t s, mpe_smooth_state *st, const mpe_smooth_args &a);
+
+// jsonwrite.hip: *launches counts the kernels the runtime accepted
+size_t json_write_scratch_bytes(int64_t n_frames, int64_t pcap, int64_t J);
+hipError_t launch_json_write(hipStream_t s, const mpe_json_write_args &a, int64_t *launches);
+hipError_t launch_format_f64(hipStream_t s, const double *d_values, int64_t n, char *d_slots, uint8_t *d_len);
 
 // skel.hip
 void skel_schedule(const int32_t *bones, int n_bones, std::vector<uint32_t> *table, int *steps_upto);

@@ -642,6 +642,18 @@ def add_lags_option(p):
     return p
 
 
+def add_write_option(p):
+    """--write-poses of metrics_from_model and metrics_from_triangulation -> p"""
+    p.add_argument('--write-poses', dest='write_poses', type=str, default=None, metavar='poses.jsonl',
+                   help='implies --device-metrics; the poses that are scored (after --refine, --smooth, --bones and so on) are written to this '
+                        'file as JSON on the GPU (mpe_json_write_poses), one line per frame handed to the inference path, numbered from 0 in '
+                        'that order: {"frame": n, "ids": [...], "bodies": [{"<joint>": [x, y, z], ...}, ...]}, metres, "ids" (the tracker\'s, '
+                        'with --relink the relinker\'s) with --track.  The lines are appended chunk by chunk in --batch order; one further '
+                        'line reports the frames, rows, joints and bytes written and the joints dropped because a coordinate was not finite.  '
+                        'harness.write_poses.read_lines reads the file back')
+    return p
+
+
 def load_lags(path, names):
     """lags.json as harness.lag --out writes it ({'lags': {camera: frames}}; a bare {camera: frames} or a list over `names`
     is taken, too) -> [lag of every camera in `names`], 0.0 for a camera the file does not name."""
@@ -702,7 +714,8 @@ def run(args, mode):
         if not getattr(args, 'track', False):
             raise ValueError('--lags needs --track: the offsets of a joint come from its track')
         lags = load_lags(args.lags_file, list(parameters.used_cameras_skeleton_matching))
-    if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine:
+    write_path = getattr(args, 'write_poses', None)
+    if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine or write_path:
         args.device_metrics = True
     src = [] if device_gt else None
     work = collect_work(args, calib, src)
@@ -722,6 +735,9 @@ def run(args, mode):
     regrouped = []                                         # --regroup: per round, the counts of every batch
     consolidated = []                                        # --merge / --found: the same of the consolidation
     used_mask = sum(1 << int(j) for j in parameters.used_joints)     # the joints both 3D stages of this script fill in
+    written = None
+    if write_path:
+        written = {'file': open(write_path, 'wb'), 'frames': 0, 'rows': 0, 'joints': 0, 'bytes': 0, 'dropped': 0}
     if getattr(args, 'track', False):
         from .tracking import TrackSummary
         tracker, summary = eng.tracker(mode, max_gap=args.track_gap, gate=args.track_gate), TrackSummary()
@@ -866,6 +882,25 @@ def run(args, mode):
             summary.add(tr['ids'].cpu().numpy(), tr['gap'].cpu().numpy())
         if scorer is not None:
             last.update(flags=flags, n_persons=n_persons, ids=tr['ids'])
+        if written is not None:
+            # what evaluate scored, every frame of the chunk; a frame the tracker did not see (no cross-camera pair) has the id -1
+            ids = None
+            if tracker is not None:
+                ids = torch.full(tuple(poses.shape[:2]), -1, dtype=torch.int32, device=poses.device).index_copy_(0, keep, tr['ids'])
+            w = eng.write_poses(poses, flags, n_persons, 'est' if mode == 'mlp' else 'triang', ids=ids, frame_start=written['frames'])
+            data = w.bytes()
+            written['file'].write(data)
+            # every written joint opens one list, as do "bodies" and "ids" once per line; flagged joints of the rows in use
+            n_lines = int(poses.shape[0])
+            joints = data.count(b'": [') - n_lines * (1 if ids is None else 2)
+            per_row = (flags != 0).sum(dim=-1) if flags.dim() == 3 else (flags != 0).to(torch.int64) * J
+            in_use = torch.arange(poses.shape[1], device=poses.device)[None, :] < n_persons.clamp(0, poses.shape[1])[:, None]
+            flagged = int((per_row * in_use).sum())
+            written['frames'] += int(poses.shape[0])
+            written['rows'] += int(w.rows_written.sum())
+            written['joints'] += joints
+            written['dropped'] += flagged - joints
+            written['bytes'] += len(data)
         return ev
 
     def score_tracks(ev, h):
@@ -964,6 +999,11 @@ def run(args, mode):
         print(report_line(out['track_score'], args.track_score_mm))
         scorer.close()
         gt_tracker.close()
+    if written is not None:
+        written.pop('file').close()
+        out['write_poses'] = written
+        print('Wrote %d frames to %s: %d rows, %d joints, %d bytes, %d joints dropped as not finite'
+              % (written['frames'], write_path, written['rows'], written['joints'], written['bytes'], written['dropped']))
     out['n_data'] = n_data
     if device_gt:
         out['gt_windows'], out['gt_declined'] = gt_windows

@@ -5,12 +5,12 @@
 
 or, with nothing but this repository:  --synthetic 200 --random-weights
 """
-from .common import add_lags_option, build_parser, run
+from .common import add_lags_option, add_write_option, build_parser, run
 
 
 def main(argv=None):
-    args = add_lags_option(build_parser('Print accuracy and time metrics of the skeleton-matching and pose estimation models '
-                                        '(CMU Panoptic only)')).parse_args(argv)
+    args = add_write_option(add_lags_option(build_parser('Print accuracy and time metrics of the skeleton-matching and pose estimation models '
+                                        '(CMU Panoptic only)'))).parse_args(argv)
     return run(args, 'mlp')
 
 

@@ -295,6 +295,15 @@ class mpe_gt_args(C.Structure):
                 ('d_gt_xyz', C.c_void_p), ('d_gt_joint', C.c_void_p), ('d_gt_valid', C.c_void_p), ('d_n_gt_in', C.c_void_p)]
 
 
+class mpe_json_write_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('frame_start', C.c_int64), ('scale', C.c_double),
+                ('d_poses', C.c_void_p), ('d_flags', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_track_id', C.c_void_p),
+                ('d_text', C.c_void_p), ('text_cap', C.c_uint64), ('d_frame_off', C.c_void_p), ('d_bodies_extent', C.c_void_p),
+                ('d_rows_written', C.c_void_p), ('d_status', C.c_void_p), ('d_total', C.c_void_p), ('d_scratch', C.c_void_p),
+                ('scratch_bytes', C.c_size_t)]
+
+
 # key slots of mpe_json_parse_bodies_device: joint key "j" -> slot j (0..30), "-1" -> slot 31
 MPE_GT_KEY_SLOTS, MPE_GT_M1_SLOT = 32, 31
 
@@ -349,6 +358,11 @@ MPE_LAG_FEW_OBS, MPE_LAG_EDGE, MPE_LAG_FLAT = 1, 2, 4
 MPE_LAG_MAX_WINDOW, MPE_LAG_MAX_SUB = 8, 8
 # mpe_refine_timed_batch: the status bits are mpe_refine_batch's, and a lag is within this many frames either way
 MPE_REFINE_TIMED_MAX_LAG = MPE_LAG_MAX_WINDOW
+
+# per-frame status bit and the total's capacity bit of mpe_json_write_poses; the bytes of a conversion slot, the longest
+# line that is put together on chip, and the row cap
+MPE_WRITE_NONFINITE, MPE_WRITE_CAPACITY = 1, 2
+MPE_JSON_WRITE_SLOT_BYTES, MPE_JSON_WRITE_STAGE_BYTES, MPE_JSON_WRITE_MAX_PERSONS = 32, 16384, 1024
 
 # per-frame status bits of mpe_eval_batch
 MPE_EVAL_SKIPPED, MPE_EVAL_OVER_CAP, MPE_EVAL_OVER_BUDGET, MPE_EVAL_NO_ASSIGNMENT = 1, 2, 4, 8
@@ -493,6 +507,12 @@ SYMBOLS = {
     'mpe_json_bodies_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'mpe_json_parse_bodies_device': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_json_bodies_args)]),
     'mpe_gt_from_bodies': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_gt_args)]),
+    'mpe_json_write_poses': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_json_write_args)]),
+    'mpe_json_write_bound': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'mpe_json_write_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    'mpe_json_write_launches': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    # n is an int64_t in the header: passed as the 64-bit size type, which carries the same bits (a negative n included)
+    'mpe_format_f64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     'mpe_packed_free': (None, [C.c_void_p]),
     'mpe_pack_last_error': (C.c_char_p, []),
     'mpe_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),

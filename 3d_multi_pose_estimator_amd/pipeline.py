@@ -1112,6 +1112,67 @@ class Engine:
         return Relinker(self, mode, bones, tid_cap, self.pcap if pcap is None else int(pcap),
                         self.max_frames if max_frames is None else int(max_frames), options)
 
+    def write_poses(self, poses, flags, n_persons, kind, ids=None, frame_start=0, scale=1.0, joint_mask=None):
+        """The poses of B frames as a JSON document on the device (mpe_json_write_poses): one line per frame,
+        {"frame": frame_start + f, "ids": [...], "bodies": [{"<j>": [x, y, z], ...}, ...]}, byte for byte what
+        harness.write_poses.write_lines states with json.dumps.  kind 'est': f32 poses with person flags (what mlp3d
+        returns); 'triang': f64 poses with joint flags (what triangulate returns); rows per frame are those of `poses`
+        (the engine's Pcap or any other, up to 1024).  ids ([B,Pcap] int32, a tracker's or relinker's): written as "ids"
+        when given.  Every coordinate is written as (double)x * scale (100.0: centimetres, the unit of bodies_3D);
+        joint_mask: the joints to write (default: all).  Nothing is synchronised or read back here.  -> WrittenPoses"""
+        if kind not in ('est', 'triang'):
+            raise ValueError('kind must be est or triang')
+        tri = kind == 'triang'
+        if poses.dim() != 4 or not 1 <= int(poses.shape[1]) <= L.MPE_JSON_WRITE_MAX_PERSONS:
+            raise ValueError('poses must be [B,Pcap,%d,3] with Pcap within 1 .. %d' % (self.J, L.MPE_JSON_WRITE_MAX_PERSONS))
+        pcap = int(poses.shape[1])
+        B = _check_pose_rows(self.J, pcap, tri, tri, poses, flags, n_persons, ids, device=self.device)
+        if int(frame_start) < 0 or not np.isfinite(float(scale)):
+            raise ValueError('frame_start must not be negative and scale must be finite')
+        lib, dev = self.lib, self.device
+        bound = int(lib.mpe_json_write_bound(B, pcap, self.J, int(ids is not None)))
+        if bound >= 1 << 32:
+            raise ValueError('%d frames of %d rows can take %d bytes; a call writes less than 2^32' % (B, pcap, bound))
+        w = WrittenPoses()
+        w.text = torch.zeros((bound + 16,), dtype=torch.uint8, device=dev)
+        w.frame_off = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+        w.bodies_extent = torch.empty((B, 2), dtype=torch.uint32, device=dev)
+        w.rows_written = torch.empty((B,), dtype=torch.int32, device=dev)
+        w.status = torch.empty((B,), dtype=torch.int32, device=dev)
+        w._total = torch.empty((2,), dtype=torch.int64, device=dev)
+        scratch_bytes = int(lib.mpe_json_write_scratch_bytes(B, pcap, self.J))
+        scratch = torch.empty((max(16, scratch_bytes),), dtype=torch.uint8, device=dev)
+        a = L.mpe_json_write_args()
+        a.n_frames, a.pcap, a.n_joints, a.pose_f64, a.joint_flags = B, pcap, self.J, int(tri), int(tri)
+        a.joint_mask = (1 << self.J) - 1 if joint_mask is None else int(joint_mask)
+        a.frame_start, a.scale = int(frame_start), float(scale)
+        a.d_poses, a.d_flags, a.d_n_persons = poses.data_ptr(), flags.data_ptr(), n_persons.data_ptr()
+        a.d_track_id = None if ids is None else ids.data_ptr()
+        a.d_text, a.text_cap = w.text.data_ptr(), bound
+        a.d_frame_off, a.d_bodies_extent, a.d_rows_written = w.frame_off.data_ptr(), w.bodies_extent.data_ptr(), w.rows_written.data_ptr()
+        a.d_status, a.d_total = w.status.data_ptr(), w._total.data_ptr()
+        a.d_scratch, a.scratch_bytes = scratch.data_ptr(), scratch_bytes
+        self._chk(lib.mpe_json_write_poses(self.ctx, self._stream(), C.byref(a)))
+        w._keep = (poses, flags, n_persons, ids, scratch)      # inputs and scratch stay alive until the caller has synchronised
+        return w
+
+    def json_write_launches(self):
+        """Kernels this engine's context has queued for write_poses (counted on the host)."""
+        n = C.c_int64(0)
+        self._chk(self.lib.mpe_json_write_launches(self.ctx, C.byref(n)))
+        return n.value
+
+    def format_f64(self, values):
+        """repr of every finite double of `values` (a device f64 tensor) on the device (mpe_format_f64) -> (slots [n,32]
+        u8, zeroed behind the tokens, len [n] u8; 0 for an infinity or a NaN), device tensors."""
+        if values.dtype != torch.float64 or values.dim() != 1 or not values.is_contiguous() or values.device != self.device:
+            raise ValueError('values must be a contiguous float64 vector on %s' % self.device)
+        n = int(values.shape[0])
+        slots = torch.zeros((n, L.MPE_JSON_WRITE_SLOT_BYTES), dtype=torch.uint8, device=self.device)
+        length = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        self._chk(self.lib.mpe_format_f64(self.ctx, self._stream(), values.data_ptr(), n, slots.data_ptr(), length.data_ptr()))
+        return slots, length
+
     def _pose_args(self, db, persons, n_persons, poses, flags, kind, joint_mask, kinds):
         """The argument checks reproject and refine share -> (B, tri, joint_mask)."""
         B = db.n_frames
@@ -1582,6 +1643,38 @@ def _check_pose_rows(J, pcap, tri, per_joint, poses, flags, n_persons, ids=None,
     if device is not None and any(t.device != device for t in given):
         raise ValueError('poses, flags, n_persons and ids must be on %s' % device)
     return B
+
+
+class WrittenPoses:
+    """Engine.write_poses' result, device tensors: text (uint8; the document, then zeros for at least 16 bytes),
+    frame_off [B+1] i64 (line f is text[frame_off[f]:frame_off[f+1]]), bodies_extent [B,2] u32 (the "bodies" list of
+    every line with its brackets, offsets into text), rows_written [B] i32, status [B] i32 (MPE_WRITE_NONFINITE: a
+    flagged joint was dropped).  total_bytes and total_status (the OR of status) read two words back and synchronise;
+    bytes() makes one copy of the document through pinned memory."""
+
+    def _totals(self):
+        if not hasattr(self, '_host_total'):
+            self._host_total = [int(v) for v in self._total.cpu()]
+            self._keep = None
+            if self._host_total[1] & L.MPE_WRITE_CAPACITY:     # the bound is a bound: this is a defect, not an input
+                raise RuntimeError('the document needs %d bytes, mpe_json_write_bound gave %d' % (self._host_total[0], self.text.numel() - 16))
+        return self._host_total
+
+    @property
+    def total_bytes(self):
+        return self._totals()[0]
+
+    @property
+    def total_status(self):
+        return self._totals()[1]
+
+    def bytes(self):
+        n = self.total_bytes
+        if n == 0:
+            return b''
+        host = torch.empty((n,), dtype=torch.uint8).pin_memory()
+        host.copy_(self.text[:n])
+        return host.numpy().tobytes()
 
 
 class _DeviceState:

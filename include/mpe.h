@@ -1821,6 +1821,73 @@ int mpe_relink_launches(mpe_ctx *ctx, const mpe_relink_state *state, int64_t *n)
 /* h_counters [3] = births, linked, over_ids; synchronises `stream`. */
 int mpe_relink_read(mpe_ctx *ctx, void *stream, mpe_relink_state *state, int64_t *h_counters, int32_t *h_status);
 
+/* ---- the poses written as JSON on the device (csrc/jsonwrite.hip, csrc/fmt_double.h) -----------------------
+ * One line per frame, in frame order, each exactly what Python's json.dumps(obj) + "\n" writes (default separators) for
+ *   obj  = {"frame": frame_start + f, "ids": [d_track_id of each written row], "bodies": [body, ...]}
+ *   body = {"<j>": [x, y, z], ...}      j ascending
+ * (harness/write_poses.py: write_lines states it with numpy and json.dumps, and the two agree byte for byte).
+ *   Row p of frame f is looked at when p < min(max(d_n_persons[f], 0), pcap).  Its flagged joints are all J with
+ *   joint_flags == 0 and d_flags[f][p] != 0, and with joint_flags == 1 the j with d_flags[f][p][j] != 0.  Every
+ *   coordinate is written as (double)x * scale, one IEEE multiply (1.0: metres; 100.0: the centimetres of bodies_3D);
+ *   f32 poses are widened exactly first.  The written joints of a row are its flagged joints within joint_mask whose
+ *   three scaled coordinates are all finite; a flagged joint of the mask that is dropped because one is not sets
+ *   MPE_WRITE_NONFINITE in d_status[f].  A row without a written joint appears neither in "ids" nor in "bodies".
+ *   "ids" is there exactly when d_track_id is not NULL; ids are written as plain integers, -1 included.
+ *   A number is the shortest decimal that reads back to the same double, the closest to it among those, in the layout of
+ *   Python's repr (positional for 1e-4 <= |x| < 1e16 with ".0" behind an integer, otherwise d[.ddd]e+XX; "-0.0"), at
+ *   most 24 bytes; the device always produces it.
+ * A line is a function of its own frame alone: the outputs of any chunking of a recording, joined, are the output of the
+ * whole recording.  The body grammar is the one mpe_json_parse_bodies_device reads, so with n_joints <= 31 and scale 100
+ * the extents of d_bodies_extent can go back in as mpe_json_entry.
+ * Outputs: d_text (line f is d_text[d_frame_off[f] .. d_frame_off[f + 1])), d_frame_off [n_frames + 1], d_bodies_extent
+ * [n_frames][2] (begin and end of the "bodies" list with its brackets, offsets into d_text), d_rows_written [n_frames],
+ * d_status [n_frames], d_total [2]: the bytes needed and the OR of every d_status.  When the bytes needed exceed text_cap
+ * MPE_WRITE_CAPACITY is set in d_total[1], d_total[0] and d_frame_off still hold the need, and nothing is stored at or
+ * behind d_text + text_cap; the text below it is then not to be used.  mpe_json_write_bound is a size that is always
+ * enough.  d_scratch: mpe_json_write_scratch_bytes(n_frames, pcap, n_joints) bytes of device memory, 16-byte aligned.
+ * Ordered on `stream`; neither synchronises nor allocates.  Five kernels whatever the frames hold (one for n_frames ==
+ * 0, which writes d_frame_off[0] = 0 and d_total): mpe_json_write_launches counts the launches this context queued for
+ * mpe_json_write_poses, on the host.  A line of up to MPE_JSON_WRITE_STAGE_BYTES is put together on chip and stored in
+ * 16-byte pieces, a longer one is written to d_text directly; the bytes are the same.
+ * MPE_ERR_INVALID: a NULL pointer (d_track_id may be), n_joints other than the context's, n_frames or frame_start
+ * negative (frame_start at most 2^62), pcap < 1, pose_f64 / joint_flags other than 0 or 1, a scale that is NaN or
+ * infinite, text_cap of 2^32 or more, scratch_bytes below the need.  MPE_ERR_CAPACITY: pcap >
+ * MPE_JSON_WRITE_MAX_PERSONS, n_frames > 2^23, or 2^31 coordinates or more in one call.
+ * mpe_format_f64 runs the same conversion on a plain array: d_slots [n][MPE_JSON_WRITE_SLOT_BYTES] receives the tokens
+ * (the bytes behind a token are left as they were), d_len [n] their lengths, 0 for an infinity or a NaN. */
+#define MPE_WRITE_NONFINITE 1
+#define MPE_WRITE_CAPACITY 2
+#define MPE_JSON_WRITE_SLOT_BYTES 32
+#define MPE_JSON_WRITE_STAGE_BYTES 16384
+#define MPE_JSON_WRITE_MAX_PERSONS 1024
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t joint_mask;
+    int64_t frame_start;           /* "frame" of the first line */
+    double scale;
+    const void *d_poses;
+    const uint8_t *d_flags;
+    const int32_t *d_n_persons;    /* [n_frames] */
+    const int32_t *d_track_id;     /* [n_frames][pcap]; NULL: no "ids" */
+    char *d_text;                  /* [text_cap] */
+    uint64_t text_cap;
+    int64_t *d_frame_off;          /* [n_frames + 1] */
+    uint32_t *d_bodies_extent;     /* [n_frames][2] */
+    int32_t *d_rows_written;       /* [n_frames] */
+    int32_t *d_status;             /* [n_frames] */
+    int64_t *d_total;              /* [2] */
+    void *d_scratch;
+    size_t scratch_bytes;
+} mpe_json_write_args;
+int mpe_json_write_poses(mpe_ctx *ctx, void *stream, const mpe_json_write_args *a);
+/* 0 for a negative argument */
+size_t mpe_json_write_bound(int32_t n_frames, int32_t pcap, int32_t n_joints, int32_t with_ids);
+size_t mpe_json_write_scratch_bytes(int32_t n_frames, int32_t pcap, int32_t n_joints);
+int mpe_json_write_launches(mpe_ctx *ctx, int64_t *n);
+int mpe_format_f64(mpe_ctx *ctx, void *stream, const double *d_values, int64_t n, char *d_slots, uint8_t *d_len);
+
 
 /* Timing probe for bench.py: average duration (ms) of the dominant GEMM launches measured
  * with HIP events on the launch stream during the last mpe_match_batch / mpe_mlp3d_batch

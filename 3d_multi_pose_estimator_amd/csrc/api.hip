@@ -2262,48 +2262,68 @@ int mpe_l0_attention_launches(mpe_ctx *ctx, int64_t *n) {
 
 }  // extern "C"
 
-// ---- calibration (calib.hip sums on the device; the step below is host work, once per pass) ----
-#include "calib_solve.h"
+// ---- calibration and camera fit (normal_sums.h sums on the device; the step is host work, once per pass) ----
+// mpe_calib_* and mpe_camfit_* are one algorithm at two sizes.  What they share is written once below, over normal_state
+// and a family's host half; `who` is the entry point's name, the prefix of its messages.
+#include "camfit_solve.h"
+#include "normal_sums.h"
 
-struct mpe_calib_host {
-    calib_cam cam[MPE_MAX_CAMERAS];
-    double E[MPE_MAX_CAMERAS * 12];                  // staging of the trial set for the copy to the device
-    double sums[MPE_MAX_CAMERAS * MPE_CALIB_SUMS];
+template <typename Cam, int SUMS, int WIDTH>
+struct normal_host {
+    Cam cam[MPE_MAX_CAMERAS];
+    double cams[MPE_MAX_CAMERAS * WIDTH];            // staging of the trial set for the copy to the device
+    double sums[MPE_MAX_CAMERAS * SUMS];
     int64_t n_obs[MPE_MAX_CAMERAS], n_skipped[MPE_MAX_CAMERAS];
 };
+struct mpe_calib_host : normal_host<calib_cam, MPE_CALIB_SUMS, CALIB_CAM> {};
+struct mpe_camfit_host : normal_host<camfit_cam, MPE_CAMFIT_SUMS, CAMFIT_CAM> {};
 
 namespace {
 
-// accepted = trial = E for every camera, the sums zeroed, the trial set on the device
-int calib_start(mpe_ctx *ctx, hipStream_t s, mpe_calib_state *st, const double *E) {
-    for (int c = 0; c < st->V; ++c) {
-        calib_cam_start(&st->host->cam[c], E + 12 * c);
-        std::memcpy(st->host->E + 12 * c, E + 12 * c, 12 * sizeof(double));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(st->E, st->host->E, (size_t)st->V * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, launch_calib_clear(s, st, st->V));
+// a camera's trial set as the device holds it
+void stage_trial(const calib_cam &cam, double *d) { std::memcpy(d, cam.Et, sizeof cam.Et); }
+
+void stage_trial(const camfit_cam &cam, double *d) {
+    const camfit_set &t = cam.t;
+    std::memcpy(d, t.E, sizeof t.E);
+    std::memcpy(d + 12, t.dist, sizeof t.dist);
+    for (int i = 0; i < 4; ++i) d[17 + i] = (double)t.k[i];
+}
+
+// the trial sets to the staging buffer and from there to the device
+template <typename S>
+int normal_upload(mpe_ctx *ctx, hipStream_t s, S *st) {
+    for (int c = 0; c < st->V; ++c) stage_trial(st->host->cam[c], st->host->cams + (size_t)c * st->cam_width);
+    HIPCHK(ctx, hipMemcpyAsync(st->cams, st->host->cams, (size_t)st->V * st->cam_width * sizeof(double), hipMemcpyHostToDevice, s));
+    return MPE_OK;
+}
+
+// after every camera's *_cam_start: the trial set on the device, the sums zeroed
+template <typename S>
+int normal_start(mpe_ctx *ctx, hipStream_t s, S *st) {
+    int rc = normal_upload(ctx, s, st);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_normal_clear(s, st));
     HIPCHK(ctx, hipStreamSynchronize(s));            // the staging buffer is the state's own: the next call may rewrite it
     return MPE_OK;
 }
 
-int calib_fetch(mpe_ctx *ctx, hipStream_t s, mpe_calib_state *st) {
-    mpe_calib_host *h = st->host;
-    HIPCHK(ctx, hipMemcpyAsync(h->sums, st->acc, (size_t)st->V * MPE_CALIB_SUMS * sizeof(double), hipMemcpyDeviceToHost, s));
+template <typename S>
+int normal_fetch(mpe_ctx *ctx, hipStream_t s, S *st) {
+    auto *h = st->host;
+    HIPCHK(ctx, hipMemcpyAsync(h->sums, st->acc, (size_t)st->V * st->n_sums * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(h->n_obs, st->n_obs, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(h->n_skipped, st->n_skipped, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return MPE_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mpe_calib_destroy(mpe_ctx *ctx, mpe_calib_state *st) {
+template <typename S>
+int normal_destroy(mpe_ctx *ctx, const char *who, S *st) {
     if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_destroy: NULL state");
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "%s: NULL state", who);
     DeviceGuard dg(ctx);
-    dev_free(ctx, st->E);
+    dev_free(ctx, st->cams);
     dev_free(ctx, st->acc);
     dev_free(ctx, st->n_obs);
     dev_free(ctx, st->n_skipped);
@@ -2313,17 +2333,136 @@ int mpe_calib_destroy(mpe_ctx *ctx, mpe_calib_state *st) {
     return MPE_OK;
 }
 
+// the host half and the device arrays of a new state
+template <typename S, typename Host>
+int normal_alloc(mpe_ctx *ctx, const char *who, S *st, Host *host, int n_sums, int cam_width) {
+    if (!(st->host = host)) return fail(ctx, MPE_ERR_NOMEM, "%s: out of memory", who);
+    st->V = ctx->cfg.n_cameras;
+    st->max_frames = ctx->cfg.max_frames;
+    st->n_sums = n_sums;
+    st->cam_width = cam_width;
+    int rc = dev_alloc(ctx, &st->cams, (size_t)st->V * cam_width);
+    if (!rc) rc = dev_alloc(ctx, &st->acc, (size_t)st->V * n_sums);
+    if (!rc) rc = dev_alloc(ctx, &st->n_obs, st->V);
+    if (!rc) rc = dev_alloc(ctx, &st->n_skipped, st->V);
+    if (!rc) rc = dev_alloc(ctx, &st->S, normal_workspace_doubles(st), false);
+    return rc;
+}
+
+int normal_batch(mpe_ctx *ctx, const char *who, void *stream, normal_state *st, const mpe_batch *b, const mpe_calib_args *a,
+                 hipError_t (*launch)(hipStream_t, const mpe::DevCfg *, normal_state *, const mpe_batch &, const mpe_calib_args &)) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "%s: NULL argument", who);
+    DeviceGuard dg(ctx);
+    bool run;
+    rc = check_batch_rows(ctx, who, b, a, &run);
+    if (rc) return rc;
+    if (!(a->huber_px >= 0.0)) return fail(ctx, MPE_ERR_INVALID, "%s: huber_px %g must not be negative", who, a->huber_px);
+    if (st->V != ctx->cfg.n_cameras || b->n_frames > st->max_frames) return fail(ctx, MPE_ERR_INVALID, "%s: the state belongs to another context", who);
+    if (!run) return MPE_OK;
+    if (row_inputs_missing(a)) return fail(ctx, MPE_ERR_INVALID, "%s: NULL argument", who);
+    HIPCHK(ctx, launch(static_cast<hipStream_t>(stream), ctx->d_cfg, st, *b, *a));
+    return MPE_OK;
+}
+
+template <typename S>
+int normal_read(mpe_ctx *ctx, const char *who, void *stream, S *st, double *sums, int64_t *n_obs, int64_t *n_skipped) {
+    if (!ctx) return MPE_ERR_INVALID;
+    if (!st) return fail(ctx, MPE_ERR_INVALID, "%s: NULL state", who);
+    DeviceGuard dg(ctx);
+    int rc = normal_fetch(ctx, static_cast<hipStream_t>(stream), st);
+    if (rc) return rc;
+    if (sums) std::memcpy(sums, st->host->sums, (size_t)st->V * st->n_sums * sizeof(double));
+    if (n_obs) std::memcpy(n_obs, st->host->n_obs, (size_t)st->V * sizeof(int64_t));
+    if (n_skipped) std::memcpy(n_skipped, st->host->n_skipped, (size_t)st->V * sizeof(int64_t));
+    return MPE_OK;
+}
+
+// The step after the family's checks of its arguments: the sums read and zeroed, cam_step(cam, sums, n_obs, held) per
+// camera, the trial sets to the device, and what the two reports share.
+template <typename S, typename Report, typename Step>
+int normal_step(mpe_ctx *ctx, const char *who, void *stream, S *st, uint32_t hold_mask, Report *report, Step cam_step) {
+    DeviceGuard dg(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto *h = st->host;
+    int rc = normal_fetch(ctx, s, st);
+    if (rc) return rc;
+    HIPCHK(ctx, launch_normal_clear(s, st));
+    for (int c = 0; c < st->V; ++c)
+        if (h->cam[c].passes > 0 && h->n_obs[c] != h->cam[c].n_obs) {
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            return fail(ctx, MPE_ERR_INVALID, "%s: the passes did not see the same data (camera %d: %lld observations, %lld in the first pass)", who, c,
+                        (long long)h->n_obs[c], (long long)h->cam[c].n_obs);
+        }
+    int all_done = 1;
+    for (int c = 0; c < st->V; ++c) {
+        cam_step(&h->cam[c], h->sums + (size_t)c * st->n_sums, h->n_obs[c], (hold_mask >> c) & 1u);
+        all_done &= calib_lm_done(&h->cam[c]);
+    }
+    rc = normal_upload(ctx, s, st);
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (!report) return MPE_OK;
+    std::memset(report, 0, sizeof *report);
+    report->n_cameras = st->V;
+    report->all_done = all_done;
+    for (int c = 0; c < st->V; ++c) {
+        const auto &cam = h->cam[c];
+        auto &r = report->cam[c];
+        r.status = cam.status;
+        r.passes = cam.passes;
+        r.n_obs = h->n_obs[c];
+        r.n_skipped = h->n_skipped[c];
+        r.cost_start = cam.cost_start;
+        r.cost = cam.Aa[st->n_sums - 1];
+        r.lambda = cam.lambda;
+        r.last_rot = cam.last_rot;
+        r.last_trans = cam.last_trans;
+        std::memcpy(r.delta, cam.delta, sizeof r.delta);
+    }
+    return MPE_OK;
+}
+
+// accepted = trial = E for every camera
+int calib_start(mpe_ctx *ctx, hipStream_t s, mpe_calib_state *st, const double *E) {
+    for (int c = 0; c < st->V; ++c) calib_cam_start(&st->host->cam[c], E + 12 * c);
+    return normal_start(ctx, s, st);
+}
+
+// accepted = trial = (E, k, dist) for every camera
+int camfit_start(mpe_ctx *ctx, hipStream_t s, mpe_camfit_state *st, const double *E, const float *k, const double *dist) {
+    for (int c = 0; c < st->V; ++c) camfit_cam_start(&st->host->cam[c], E + 12 * c, k + 4 * c, dist + 5 * c);
+    return normal_start(ctx, s, st);
+}
+
+// (fx, fy, cx, cy) of the context's own cfg.K -> k [V][4].  A K of another form than [[fx,0,cx],[0,fy,cy],[0,0,1]] is
+// refused.
+int camfit_own_k(mpe_ctx *ctx, const char *who, float *k) {
+    for (int c = 0; c < ctx->cfg.n_cameras; ++c) {
+        const float *K = ctx->hcfg.K[c];
+        if (K[1] != 0.0f || K[3] != 0.0f || K[6] != 0.0f || K[7] != 0.0f || K[8] != 1.0f)
+            return fail(ctx, MPE_ERR_INVALID, "%s: K of camera %d is not [[fx,0,cx],[0,fy,cy],[0,0,1]]", who, c);
+        k[4 * c] = K[0], k[4 * c + 1] = K[4], k[4 * c + 2] = K[2], k[4 * c + 3] = K[5];
+    }
+    return MPE_OK;
+}
+
+void camfit_copy_out(const camfit_set &from, int c, double *E, float *k, double *dist) {
+    if (E) std::memcpy(E + 12 * c, from.E, sizeof from.E);
+    if (k) std::memcpy(k + 4 * c, from.k, sizeof from.k);
+    if (dist) std::memcpy(dist + 5 * c, from.dist, sizeof from.dist);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpe_calib_destroy(mpe_ctx *ctx, mpe_calib_state *st) { return normal_destroy(ctx, "mpe_calib_destroy", st); }
+
 int mpe_calib_create(mpe_ctx *ctx, mpe_calib_state **out) {
     return create_state(ctx, "mpe_calib_create", out, mpe_calib_destroy, [&](mpe_calib_state *st) {
-        st->host = new (std::nothrow) mpe_calib_host();
-        if (!st->host) return fail(ctx, MPE_ERR_NOMEM, "mpe_calib_create: out of memory");
-        st->V = ctx->cfg.n_cameras;
-        st->max_frames = ctx->cfg.max_frames;
-        int rc = dev_alloc(ctx, &st->E, (size_t)st->V * 12);
-        if (!rc) rc = dev_alloc(ctx, &st->acc, (size_t)st->V * MPE_CALIB_SUMS);
-        if (!rc) rc = dev_alloc(ctx, &st->n_obs, st->V);
-        if (!rc) rc = dev_alloc(ctx, &st->n_skipped, st->V);
-        if (!rc) rc = dev_alloc(ctx, &st->S, calib_workspace_doubles(st->max_frames, st->V), false);
+        int rc = normal_alloc(ctx, "mpe_calib_create", st, new (std::nothrow) mpe_calib_host(), MPE_CALIB_SUMS, CALIB_CAM);
         if (!rc) rc = calib_start(ctx, nullptr, st, &ctx->hcfg.P[0][0]);
         return rc;
     });
@@ -2358,32 +2497,11 @@ int mpe_calib_get_extrinsics(mpe_ctx *ctx, const mpe_calib_state *st, double *ac
 int mpe_calib_launches(mpe_ctx *ctx, const mpe_calib_state *st, int64_t *n) { return state_launches(ctx, "mpe_calib_launches", st, n); }
 
 int mpe_calib_batch(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_batch *b, const mpe_calib_args *a) {
-    int rc = check_batch(ctx, b);
-    if (rc) return rc;
-    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: NULL argument");
-    DeviceGuard dg(ctx);
-    bool run;
-    rc = check_batch_rows(ctx, "mpe_calib_batch", b, a, &run);
-    if (rc) return rc;
-    if (!(a->huber_px >= 0.0)) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: huber_px %g must not be negative", a->huber_px);
-    if (st->V != ctx->cfg.n_cameras || b->n_frames > st->max_frames)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: the state belongs to another context");
-    if (!run) return MPE_OK;
-    if (row_inputs_missing(a)) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_batch: NULL argument");
-    HIPCHK(ctx, launch_calib(static_cast<hipStream_t>(stream), ctx->d_cfg, st->V, st, *b, *a));
-    return MPE_OK;
+    return normal_batch(ctx, "mpe_calib_batch", stream, st, b, a, launch_calib);
 }
 
 int mpe_calib_read(mpe_ctx *ctx, void *stream, mpe_calib_state *st, double *sums, int64_t *n_obs, int64_t *n_skipped) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_read: NULL state");
-    DeviceGuard dg(ctx);
-    int rc = calib_fetch(ctx, static_cast<hipStream_t>(stream), st);
-    if (rc) return rc;
-    if (sums) std::memcpy(sums, st->host->sums, (size_t)st->V * MPE_CALIB_SUMS * sizeof(double));
-    if (n_obs) std::memcpy(n_obs, st->host->n_obs, (size_t)st->V * sizeof(int64_t));
-    if (n_skipped) std::memcpy(n_skipped, st->host->n_skipped, (size_t)st->V * sizeof(int64_t));
-    return MPE_OK;
+    return normal_read(ctx, "mpe_calib_read", stream, st, sums, n_obs, n_skipped);
 }
 
 int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_calib_step_args *a, mpe_calib_report *report) {
@@ -2392,150 +2510,19 @@ int mpe_calib_step(mpe_ctx *ctx, void *stream, mpe_calib_state *st, const mpe_ca
     if (a->min_obs < 6) return fail(ctx, MPE_ERR_INVALID, "mpe_calib_step: min_obs %lld is below 6, the unknowns of a camera", (long long)a->min_obs);
     if (!(a->rot_tol >= 0.0) || !(a->trans_tol >= 0.0))
         return fail(ctx, MPE_ERR_INVALID, "mpe_calib_step: rot_tol %g and trans_tol %g must not be negative", a->rot_tol, a->trans_tol);
-    DeviceGuard dg(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    mpe_calib_host *h = st->host;
-    int rc = calib_fetch(ctx, s, st);
-    if (rc) return rc;
-    HIPCHK(ctx, launch_calib_clear(s, st, st->V));
-    for (int c = 0; c < st->V; ++c)
-        if (h->cam[c].passes > 0 && h->n_obs[c] != h->cam[c].n_obs) {
-            HIPCHK(ctx, hipStreamSynchronize(s));
-            return fail(ctx, MPE_ERR_INVALID, "mpe_calib_step: the passes did not see the same data (camera %d: %lld observations, %lld in the first pass)",
-                        c, (long long)h->n_obs[c], (long long)h->cam[c].n_obs);
-        }
-    int all_done = 1;
-    for (int c = 0; c < st->V; ++c) {
-        calib_cam *cam = &h->cam[c];
-        calib_cam_step(cam, h->sums + (size_t)c * MPE_CALIB_SUMS, h->n_obs[c], (a->hold_mask >> c) & 1u, a->min_obs, a->rot_tol, a->trans_tol);
-        std::memcpy(h->E + 12 * c, cam->Et, 12 * sizeof(double));
-        all_done &= calib_cam_done(cam);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(st->E, h->E, (size_t)st->V * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    if (report) {
-        std::memset(report, 0, sizeof *report);
-        report->n_cameras = st->V;
-        report->all_done = all_done;
-        for (int c = 0; c < st->V; ++c) {
-            const calib_cam &cam = h->cam[c];
-            mpe_calib_cam_report &r = report->cam[c];
-            r.status = cam.status;
-            r.passes = cam.passes;
-            r.n_obs = h->n_obs[c];
-            r.n_skipped = h->n_skipped[c];
-            r.cost_start = cam.cost_start;
-            r.cost = cam.Aa[27];
-            r.lambda = cam.lambda;
-            r.last_rot = cam.last_rot;
-            r.last_trans = cam.last_trans;
-            std::memcpy(r.delta, cam.delta, sizeof r.delta);
-        }
-    }
-    return MPE_OK;
+    return normal_step(ctx, "mpe_calib_step", stream, st, a->hold_mask, report, [&](calib_cam *cam, const double *sums, long long n_obs, int held) {
+        calib_cam_step(cam, sums, n_obs, held, a->min_obs, a->rot_tol, a->trans_tol);
+    });
 }
 
-}  // extern "C"
-
-// ---- camera fit (camfit.hip sums on the device; the step below is host work, once per pass) ----
-#include "camfit_solve.h"
-
-struct mpe_camfit_host {
-    camfit_cam cam[MPE_MAX_CAMERAS];
-    double cams[MPE_MAX_CAMERAS * CAMFIT_CAM];  // staging of the trial set for the copy to the device
-    double sums[MPE_MAX_CAMERAS * MPE_CAMFIT_SUMS];
-    int64_t n_obs[MPE_MAX_CAMERAS], n_skipped[MPE_MAX_CAMERAS];
-};
-
-namespace {
-
-// the trial sets to the staging buffer and from there to the device
-int camfit_upload(mpe_ctx *ctx, hipStream_t s, mpe_camfit_state *st) {
-    mpe_camfit_host *h = st->host;
-    for (int c = 0; c < st->V; ++c) {
-        double *d = h->cams + (size_t)c * CAMFIT_CAM;
-        const camfit_set &t = h->cam[c].t;
-        std::memcpy(d, t.E, sizeof t.E);
-        std::memcpy(d + 12, t.dist, sizeof t.dist);
-        for (int i = 0; i < 4; ++i) d[17 + i] = (double)t.k[i];
-    }
-    HIPCHK(ctx, hipMemcpyAsync(st->cams, h->cams, (size_t)st->V * CAMFIT_CAM * sizeof(double), hipMemcpyHostToDevice, s));
-    return MPE_OK;
-}
-
-// accepted = trial = (E, k, dist) for every camera, the sums zeroed, the trial set on the device
-int camfit_start(mpe_ctx *ctx, hipStream_t s, mpe_camfit_state *st, const double *E, const float *k, const double *dist) {
-    for (int c = 0; c < st->V; ++c) camfit_cam_start(&st->host->cam[c], E + 12 * c, k + 4 * c, dist + 5 * c);
-    int rc = camfit_upload(ctx, s, st);
-    if (rc) return rc;
-    HIPCHK(ctx, launch_camfit_clear(s, st, st->V));
-    HIPCHK(ctx, hipStreamSynchronize(s));            // the staging buffer is the state's own: the next call may rewrite it
-    return MPE_OK;
-}
-
-// the context's own cameras: cfg.P, (fx, fy, cx, cy) of cfg.K, cfg.dist.  A K of another form than
-// [[fx,0,cx],[0,fy,cy],[0,0,1]] is refused.
-int camfit_start_own(mpe_ctx *ctx, const char *who, hipStream_t s, mpe_camfit_state *st) {
-    float k[MPE_MAX_CAMERAS * 4];
-    for (int c = 0; c < st->V; ++c) {
-        const float *K = ctx->hcfg.K[c];
-        if (K[1] != 0.0f || K[3] != 0.0f || K[6] != 0.0f || K[7] != 0.0f || K[8] != 1.0f)
-            return fail(ctx, MPE_ERR_INVALID, "%s: K of camera %d is not [[fx,0,cx],[0,fy,cy],[0,0,1]]", who, c);
-        k[4 * c] = K[0], k[4 * c + 1] = K[4], k[4 * c + 2] = K[2], k[4 * c + 3] = K[5];
-    }
-    return camfit_start(ctx, s, st, &ctx->hcfg.P[0][0], k, &ctx->hcfg.dist[0][0]);
-}
-
-int camfit_fetch(mpe_ctx *ctx, hipStream_t s, mpe_camfit_state *st) {
-    mpe_camfit_host *h = st->host;
-    HIPCHK(ctx, hipMemcpyAsync(h->sums, st->acc, (size_t)st->V * MPE_CAMFIT_SUMS * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(h->n_obs, st->n_obs, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(h->n_skipped, st->n_skipped, (size_t)st->V * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return MPE_OK;
-}
-
-void camfit_copy_out(const camfit_set &from, int c, double *E, float *k, double *dist) {
-    if (E) std::memcpy(E + 12 * c, from.E, sizeof from.E);
-    if (k) std::memcpy(k + 4 * c, from.k, sizeof from.k);
-    if (dist) std::memcpy(dist + 5 * c, from.dist, sizeof from.dist);
-}
-
-}  // namespace
-
-extern "C" {
-
-int mpe_camfit_destroy(mpe_ctx *ctx, mpe_camfit_state *st) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_destroy: NULL state");
-    DeviceGuard dg(ctx);
-    dev_free(ctx, st->cams);
-    dev_free(ctx, st->acc);
-    dev_free(ctx, st->n_obs);
-    dev_free(ctx, st->n_skipped);
-    dev_free(ctx, st->S);
-    delete st->host;
-    delete st;
-    return MPE_OK;
-}
+int mpe_camfit_destroy(mpe_ctx *ctx, mpe_camfit_state *st) { return normal_destroy(ctx, "mpe_camfit_destroy", st); }
 
 int mpe_camfit_create(mpe_ctx *ctx, mpe_camfit_state **out) {
     return create_state(ctx, "mpe_camfit_create", out, mpe_camfit_destroy, [&](mpe_camfit_state *st) {
-        st->host = new (std::nothrow) mpe_camfit_host();
-        if (!st->host) return fail(ctx, MPE_ERR_NOMEM, "mpe_camfit_create: out of memory");
-        st->V = ctx->cfg.n_cameras;
-        st->max_frames = ctx->cfg.max_frames;
-        for (int c = 0; c < st->V; ++c) {            // the form of K, before anything is allocated on the device
-            const float *K = ctx->hcfg.K[c];
-            if (K[1] != 0.0f || K[3] != 0.0f || K[6] != 0.0f || K[7] != 0.0f || K[8] != 1.0f)
-                return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_create: K of camera %d is not [[fx,0,cx],[0,fy,cy],[0,0,1]]", c);
-        }
-        int rc = dev_alloc(ctx, &st->cams, (size_t)st->V * CAMFIT_CAM);
-        if (!rc) rc = dev_alloc(ctx, &st->acc, (size_t)st->V * MPE_CAMFIT_SUMS);
-        if (!rc) rc = dev_alloc(ctx, &st->n_obs, st->V);
-        if (!rc) rc = dev_alloc(ctx, &st->n_skipped, st->V);
-        if (!rc) rc = dev_alloc(ctx, &st->S, camfit_workspace_doubles(st->max_frames, st->V), false);
-        if (!rc) rc = camfit_start_own(ctx, "mpe_camfit_create", nullptr, st);
+        float k[MPE_MAX_CAMERAS * 4];
+        int rc = camfit_own_k(ctx, "mpe_camfit_create", k);   // the form of K, before anything is allocated on the device
+        if (!rc) rc = normal_alloc(ctx, "mpe_camfit_create", st, new (std::nothrow) mpe_camfit_host(), MPE_CAMFIT_SUMS, CAMFIT_CAM);
+        if (!rc) rc = camfit_start(ctx, nullptr, st, &ctx->hcfg.P[0][0], k, &ctx->hcfg.dist[0][0]);
         return rc;
     });
 }
@@ -2544,7 +2531,9 @@ int mpe_camfit_reset(mpe_ctx *ctx, void *stream, mpe_camfit_state *st) {
     if (!ctx) return MPE_ERR_INVALID;
     if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_reset: NULL state");
     DeviceGuard dg(ctx);
-    return camfit_start_own(ctx, "mpe_camfit_reset", static_cast<hipStream_t>(stream), st);
+    float k[MPE_MAX_CAMERAS * 4];
+    const int rc = camfit_own_k(ctx, "mpe_camfit_reset", k);
+    return rc ? rc : camfit_start(ctx, static_cast<hipStream_t>(stream), st, &ctx->hcfg.P[0][0], k, &ctx->hcfg.dist[0][0]);
 }
 
 int mpe_camfit_set_cameras(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const double *E, const float *k, const double *dist) {
@@ -2578,32 +2567,11 @@ int mpe_camfit_get_cameras(mpe_ctx *ctx, const mpe_camfit_state *st, double *E_a
 int mpe_camfit_launches(mpe_ctx *ctx, const mpe_camfit_state *st, int64_t *n) { return state_launches(ctx, "mpe_camfit_launches", st, n); }
 
 int mpe_camfit_batch(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const mpe_batch *b, const mpe_calib_args *a) {
-    int rc = check_batch(ctx, b);
-    if (rc) return rc;
-    if (!st || !a) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: NULL argument");
-    DeviceGuard dg(ctx);
-    bool run;
-    rc = check_batch_rows(ctx, "mpe_camfit_batch", b, a, &run);
-    if (rc) return rc;
-    if (!(a->huber_px >= 0.0)) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: huber_px %g must not be negative", a->huber_px);
-    if (st->V != ctx->cfg.n_cameras || b->n_frames > st->max_frames)
-        return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: the state belongs to another context");
-    if (!run) return MPE_OK;
-    if (row_inputs_missing(a)) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_batch: NULL argument");
-    HIPCHK(ctx, launch_camfit(static_cast<hipStream_t>(stream), st->V, st, *b, *a));
-    return MPE_OK;
+    return normal_batch(ctx, "mpe_camfit_batch", stream, st, b, a, launch_camfit);
 }
 
 int mpe_camfit_read(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, double *sums, int64_t *n_obs, int64_t *n_skipped) {
-    if (!ctx) return MPE_ERR_INVALID;
-    if (!st) return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_read: NULL state");
-    DeviceGuard dg(ctx);
-    int rc = camfit_fetch(ctx, static_cast<hipStream_t>(stream), st);
-    if (rc) return rc;
-    if (sums) std::memcpy(sums, st->host->sums, (size_t)st->V * MPE_CAMFIT_SUMS * sizeof(double));
-    if (n_obs) std::memcpy(n_obs, st->host->n_obs, (size_t)st->V * sizeof(int64_t));
-    if (n_skipped) std::memcpy(n_skipped, st->host->n_skipped, (size_t)st->V * sizeof(int64_t));
-    return MPE_OK;
+    return normal_read(ctx, "mpe_camfit_read", stream, st, sums, n_obs, n_skipped);
 }
 
 int mpe_camfit_step(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const mpe_camfit_step_args *a, mpe_camfit_report *report) {
@@ -2619,47 +2587,13 @@ int mpe_camfit_step(mpe_ctx *ctx, void *stream, mpe_camfit_state *st, const mpe_
     if (!(a->rot_tol >= 0.0) || !(a->trans_tol >= 0.0) || !(a->pix_tol >= 0.0) || !(a->lens_tol >= 0.0))
         return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_step: rot_tol %g, trans_tol %g, pix_tol %g and lens_tol %g must not be negative", a->rot_tol,
                     a->trans_tol, a->pix_tol, a->lens_tol);
-    DeviceGuard dg(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    mpe_camfit_host *h = st->host;
-    int rc = camfit_fetch(ctx, s, st);
-    if (rc) return rc;
-    HIPCHK(ctx, launch_camfit_clear(s, st, st->V));
-    for (int c = 0; c < st->V; ++c)
-        if (h->cam[c].passes > 0 && h->n_obs[c] != h->cam[c].n_obs) {
-            HIPCHK(ctx, hipStreamSynchronize(s));
-            return fail(ctx, MPE_ERR_INVALID, "mpe_camfit_step: the passes did not see the same data (camera %d: %lld observations, %lld in the first pass)",
-                        c, (long long)h->n_obs[c], (long long)h->cam[c].n_obs);
-        }
     const camfit_rule rule{a->rot_tol, a->trans_tol, a->pix_tol, a->lens_tol, (long long)a->min_obs, a->free_mask};
-    int all_done = 1;
+    const int rc = normal_step(ctx, "mpe_camfit_step", stream, st, a->hold_mask, report,
+                               [&](camfit_cam *cam, const double *sums, long long n_obs, int held) { camfit_cam_step(cam, sums, n_obs, held, &rule); });
+    if (rc || !report) return rc;
     for (int c = 0; c < st->V; ++c) {
-        camfit_cam_step(&h->cam[c], h->sums + (size_t)c * MPE_CAMFIT_SUMS, h->n_obs[c], (a->hold_mask >> c) & 1u, &rule);
-        all_done &= camfit_cam_done(&h->cam[c]);
-    }
-    rc = camfit_upload(ctx, s, st);
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    if (report) {
-        std::memset(report, 0, sizeof *report);
-        report->n_cameras = st->V;
-        report->all_done = all_done;
-        for (int c = 0; c < st->V; ++c) {
-            const camfit_cam &cam = h->cam[c];
-            mpe_camfit_cam_report &r = report->cam[c];
-            r.status = cam.status;
-            r.passes = cam.passes;
-            r.n_obs = h->n_obs[c];
-            r.n_skipped = h->n_skipped[c];
-            r.cost_start = cam.cost_start;
-            r.cost = cam.Aa[CAMFIT_C];
-            r.lambda = cam.lambda;
-            r.last_rot = cam.last_rot;
-            r.last_trans = cam.last_trans;
-            r.last_pix = cam.last_pix;
-            r.last_lens = cam.last_lens;
-            std::memcpy(r.delta, cam.delta, sizeof r.delta);
-        }
+        report->cam[c].last_pix = st->host->cam[c].last_pix;
+        report->cam[c].last_lens = st->host->cam[c].last_lens;
     }
     return MPE_OK;
 }

@@ -9,9 +9,9 @@
 // g, q = 104 the cost C.
 //
 // camfit_solve: idx_0 < idx_1 < .. < idx_{n-1} the free unknowns (free_mask), M_ab = A[idx_a][idx_b], M_aa = A_aa +
-// lambda*A_aa, M y = -g[idx] by the unpivoted LDL^T of calib_solve6 with n in the place of 6, every inner sum a left fold
-// in increasing index; delta[idx_a] = y_a, delta of a held unknown = 0.0.  With only the pose group free n = 6 and idx =
-// 0..5: calib_solve6's operations in its order.
+// lambda*A_aa, M y = -g[idx] by calib_ldlt, the unpivoted LDL^T of calib_solve6 with n in the place of 6, every inner sum a
+// left fold in increasing index; delta[idx_a] = y_a, delta of a held unknown = 0.0.  With only the pose group free n = 6
+// and idx = 0..5: calib_solve6's call.  The step is calib_lm_step's bookkeeping around this file's sets.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -26,6 +26,7 @@
 #define CAMFIT_SUMS 105
 #define CAMFIT_G 91                  // q of g_0
 #define CAMFIT_C 104                 // q of the cost
+static_assert(CAMFIT_N <= CALIB_SOLVE_MAX, "calib_ldlt holds thirteen unknowns");
 
 enum {                               // the groups of include/mpe.h (MPE_CAMFIT_*), restated so that the header stands alone
     CAMFIT_POSE = 1,
@@ -49,39 +50,13 @@ static inline int camfit_free(unsigned free_mask, int *idx) {
     return n;
 }
 
-// -> 1 and delta [13], or 0 when a pivot is not > 0 or a delta is not finite
+// -> 1 and delta [13], or 0 when a pivot is not > 0 or a delta is not finite (delta is all zero then)
 static inline int camfit_solve(const double *A, const double *g, double lambda, unsigned free_mask, double *delta) {
-    double M[CAMFIT_N][CAMFIT_N], L[CAMFIT_N][CAMFIT_N], D[CAMFIT_N], v[CAMFIT_N], z[CAMFIT_N], y[CAMFIT_N];
+    double y[CAMFIT_N];
     int idx[CAMFIT_N];
     const int n = camfit_free(free_mask, idx);
     for (int k = 0; k < CAMFIT_N; ++k) delta[k] = 0.0;
-    for (int k = 0; k < n; ++k)
-        for (int l = k; l < n; ++l) M[k][l] = M[l][k] = A[camfit_tri(idx[k], idx[l])];
-    for (int k = 0; k < n; ++k) M[k][k] = M[k][k] + lambda * M[k][k];
-    for (int j = 0; j < n; ++j) {
-        for (int k = 0; k < j; ++k) v[k] = L[j][k] * D[k];
-        double d = M[j][j];
-        for (int k = 0; k < j; ++k) d = d - L[j][k] * v[k];
-        if (!(d > 0.0)) return 0;
-        D[j] = d;
-        for (int i = j + 1; i < n; ++i) {
-            double t = M[i][j];
-            for (int k = 0; k < j; ++k) t = t - L[i][k] * v[k];
-            L[i][j] = t / d;
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        double t = -g[idx[i]];
-        for (int k = 0; k < i; ++k) t = t - L[i][k] * z[k];
-        z[i] = t;
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        double t = z[i] / D[i];
-        for (int k = i + 1; k < n; ++k) t = t - L[k][i] * y[k];
-        y[i] = t;
-    }
-    for (int i = 0; i < n; ++i)
-        if (!calib_finite(y[i])) return 0;          // delta stays all zero, as after a pivot that is not > 0
+    if (!calib_ldlt(A, g, CAMFIT_N, idx, n, lambda, y)) return 0;
     for (int i = 0; i < n; ++i) delta[idx[i]] = y[i];
     return 1;
 }
@@ -94,15 +69,12 @@ typedef struct {
 } camfit_set;
 
 // What a camera carries from step to step.
-typedef struct {
+struct camfit_cam : calib_lm {
     camfit_set a, t;                 // accepted and trial
     double Aa[CAMFIT_SUMS];          // the sums at the accepted set (A, g, C)
     double delta[CAMFIT_N];          // the step that led from a to t
-    double lambda, cost_start;
-    double last_rot, last_trans, last_pix, last_lens;   // of the last trial built
-    long long n_obs;                 // of the first pass
-    int status, passes;              // CALIB_* bits; passes taken so far
-} camfit_cam;
+    double last_pix, last_lens;      // of the last trial built: max |delta_6..9| and max |delta_10..12|
+};
 
 static inline void camfit_cam_start(camfit_cam *c, const double *E, const float *k, const double *dist) {
     for (int i = 0; i < 12; ++i) c->a.E[i] = E[i];
@@ -111,10 +83,8 @@ static inline void camfit_cam_start(camfit_cam *c, const double *E, const float 
     c->t = c->a;
     for (int i = 0; i < CAMFIT_SUMS; ++i) c->Aa[i] = 0.0;
     for (int i = 0; i < CAMFIT_N; ++i) c->delta[i] = 0.0;
-    c->lambda = 1e-3;
-    c->cost_start = c->last_rot = c->last_trans = c->last_pix = c->last_lens = 0.0;
-    c->n_obs = 0;
-    c->status = c->passes = 0;
+    calib_lm_start(c);
+    c->last_pix = c->last_lens = 0.0;
 }
 
 static inline double camfit_max_abs(const double *x, int n) {
@@ -180,40 +150,19 @@ typedef struct {
 // One step of one camera: `sums` and n_obs are what the pass at c->t left.  held: the caller's hold_mask bit.
 // -> 0, or -1 when n_obs is not the first pass's (nothing is changed then).
 static inline int camfit_cam_step(camfit_cam *c, const double *sums, long long n_obs, int held, const camfit_rule *r) {
-    if (c->passes > 0 && n_obs != c->n_obs) return -1;
-    const double C = sums[CAMFIT_C];
-    const int first = c->passes == 0;
-    ++c->passes;
-    c->status &= ~(CALIB_ACCEPTED | CALIB_REJECTED | CALIB_HELD | CALIB_FEW_OBS);
-    if (first) {
-        c->n_obs = n_obs;
-        c->cost_start = C;
-    }
-    if (held || c->n_obs < r->min_obs) {
-        c->status |= CALIB_HELD | (c->n_obs < r->min_obs ? CALIB_FEW_OBS : 0);
-        for (int i = 0; i < CAMFIT_SUMS; ++i) c->Aa[i] = sums[i];     // reported, never solved
+    const int what = calib_lm_step(c, c->Aa, CAMFIT_SUMS, sums, n_obs, held, r->min_obs);
+    if (what == CALIB_LM_REFUSED) return -1;
+    if (what == CALIB_LM_STOPPED) return 0;
+    if (what == CALIB_LM_HELD) {
         c->t = c->a;
         return 0;
     }
-    if (c->status & (CALIB_CONVERGED | CALIB_STALLED)) return 0;
-    if (first || C < c->Aa[CAMFIT_C]) {
-        c->a = c->t;
-        for (int i = 0; i < CAMFIT_SUMS; ++i) c->Aa[i] = sums[i];
-        c->status |= CALIB_ACCEPTED;
-        if (!first) {
-            c->lambda = fmax(c->lambda / 10.0, 1e-12);
-            if (calib_norm3(c->delta) < r->rot_tol && camfit_max_abs(c->delta + 3, 3) < r->trans_tol &&
-                camfit_max_abs(c->delta + 6, 4) < r->pix_tol && camfit_max_abs(c->delta + 10, 3) < r->lens_tol) {
-                c->status |= CALIB_CONVERGED;
-                return 0;
-            }
-        }
-    } else {
-        c->status |= CALIB_REJECTED;
-        c->lambda = c->lambda * 10.0;
+    if (what != CALIB_LM_REJECTED) c->a = c->t;
+    if (what == CALIB_LM_ACCEPTED && calib_norm3(c->delta) < r->rot_tol && camfit_max_abs(c->delta + 3, 3) < r->trans_tol &&
+        camfit_max_abs(c->delta + 6, 4) < r->pix_tol && camfit_max_abs(c->delta + 10, 3) < r->lens_tol) {
+        c->status |= CALIB_CONVERGED;
+        return 0;
     }
     camfit_cam_trial(c, r->free_mask);
     return 0;
 }
-
-static inline int camfit_cam_done(const camfit_cam *c) { return (c->status & (CALIB_HELD | CALIB_CONVERGED | CALIB_STALLED)) != 0; }

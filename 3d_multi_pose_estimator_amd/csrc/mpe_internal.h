@@ -265,30 +265,26 @@ struct mpe_relink_state {
     double *table = nullptr;        // scratch [pcap][tid_cap]
 };
 
-// calib.hip: what mpe_calib_batch accumulates and mpe_calib_step reads.  The Levenberg-Marquardt state of the cameras lives
-// on the host (api.hip, csrc/calib_solve.h).
-struct mpe_calib_host;
-struct mpe_calib_state {
+// normal_sums.h: what mpe_calib_batch / mpe_camfit_batch accumulate and mpe_calib_step / mpe_camfit_step read, the same
+// at two sizes.  The Levenberg-Marquardt state of the cameras lives on the host (api.hip, csrc/calib_solve.h,
+// csrc/camfit_solve.h), behind each family's own opaque type.
+struct normal_state {
     int V = 0, max_frames = 0;
-    int64_t launches = 0;           // kernels enqueued since mpe_calib_create
-    double *E = nullptr;            // [V][12] trial extrinsics
-    double *acc = nullptr;          // [V][MPE_CALIB_SUMS] sums of the pass so far
+    int n_sums = 0, cam_width = 0;  // sums per camera; doubles of a trial camera on the device
+    int64_t launches = 0;           // kernels enqueued since create
+    double *cams = nullptr;         // [V][cam_width] the trial set
+    double *acc = nullptr;          // [V][n_sums] sums of the pass so far
     unsigned long long *n_obs = nullptr, *n_skipped = nullptr;   // [V]
-    double *S = nullptr;            // scratch [max_frames][V][MPE_CALIB_SUMS]: the per-frame partials of a call
+    double *S = nullptr;            // scratch [max_frames][V][n_sums]: the per-frame partials of a call
+};
+constexpr int CALIB_CAM = 12;       // doubles of a trial camera on the device: E [12]
+constexpr int CAMFIT_CAM = 21;      // E [12], dist [5], (fx, fy, cx, cy) widened (exact)
+struct mpe_calib_host;
+struct mpe_calib_state : normal_state {
     mpe_calib_host *host = nullptr;
 };
-
-// camfit.hip: what mpe_camfit_batch accumulates and mpe_camfit_step reads.  The Levenberg-Marquardt state of the cameras lives
-// on the host (api.hip, csrc/camfit_solve.h).
-constexpr int CAMFIT_CAM = 21;      // doubles of a trial camera on the device: E [12], dist [5], (fx, fy, cx, cy) widened (exact)
 struct mpe_camfit_host;
-struct mpe_camfit_state {
-    int V = 0, max_frames = 0;
-    int64_t launches = 0;           // kernels enqueued since mpe_camfit_create
-    double *cams = nullptr;         // [V][CAMFIT_CAM] the trial set
-    double *acc = nullptr;          // [V][MPE_CAMFIT_SUMS] sums of the pass so far
-    unsigned long long *n_obs = nullptr, *n_skipped = nullptr;   // [V]
-    double *S = nullptr;            // scratch [max_frames][V][MPE_CAMFIT_SUMS]: the per-frame partials of a call
+struct mpe_camfit_state : normal_state {
     mpe_camfit_host *host = nullptr;
 };
 
@@ -493,14 +489,9 @@ hipError_t launch_regroup(hipStream_t s, const DevCfg *cfg, int V, int min_views
 // consolidate.hip
 hipError_t launch_consolidate(hipStream_t s, const DevCfg *cfg, int V, int hmax, int32_t *sticky, const mpe_batch &b,
                               const mpe_consolidate_args &a);
-// calib.hip
-size_t calib_workspace_doubles(int max_frames, int V);
-hipError_t launch_calib(hipStream_t s, const DevCfg *cfg, int V, mpe_calib_state *st, const mpe_batch &b, const mpe_calib_args &a);
-hipError_t launch_calib_clear(hipStream_t s, mpe_calib_state *st, int V);
-// camfit.hip
-size_t camfit_workspace_doubles(int max_frames, int V);
-hipError_t launch_camfit(hipStream_t s, int V, mpe_camfit_state *st, const mpe_batch &b, const mpe_calib_args &a);
-hipError_t launch_camfit_clear(hipStream_t s, mpe_camfit_state *st, int V);
+// calib.hip, camfit.hip (normal_sums.h): one pass onto the state, two launches
+hipError_t launch_calib(hipStream_t s, const DevCfg *cfg, normal_state *st, const mpe_batch &b, const mpe_calib_args &a);
+hipError_t launch_camfit(hipStream_t s, const DevCfg *cfg, normal_state *st, const mpe_batch &b, const mpe_calib_args &a);
 // lag.hip
 size_t lag_counter_words(int V, int K);
 hipError_t launch_lag(hipStream_t s, const DevCfg *cfg, mpe_lag_state *st, const mpe_batch &b, const mpe_lag_args &a);

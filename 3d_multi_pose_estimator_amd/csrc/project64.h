@@ -2,7 +2,7 @@
 // regroup.hip, consolidate.hip, calib.hip), stated once so that every file rounds the same operations in the same order:
 // DESIGN.md 2.2.  include/mpe.h words the lines under mpe_refine_batch; harness/refine.py is their numpy statement, and
 // tests/native/camera64_test.cpp holds this file to it bit for bit on the host.  A camera is (T [12] the 3 x 4 extrinsics,
-// dist [5], K [9] float): calib.hip passes its trial extrinsics, everyone else cfg->P[c].  Plain inline functions that need
+// dist [5], K [9] float): calib.hip and camfit.hip pass their trial cameras, everyone else cfg->P[c].  Plain inline functions that need
 // <math.h> and <stdint.h> only.  Contraction is off from here to the end of the including file (a host build passes
 // -ffp-contract=off); f64 quotients and roots are the language's correctly rounded ones.
 #pragma once
@@ -100,6 +100,22 @@ MPE_CAM_HD inline void point_jacobian(const double *T, const double *dist, const
         const double ak = (T[k] - p.h0 * T[8 + k]) / p.pc2, bk = (T[4 + k] - p.h1 * T[8 + k]) / p.pc2;
         jacobian_tail(p, K, fd, ak, bk, jx + k, jy + k);
     }
+}
+
+// the derivatives of (px, py) by the six-vector (w, tau) of a rigid perturbation of the camera, d pc = w x pc + tau: those
+// by the camera-frame point through the shared tail, then the cross products; fd = radial_slope
+MPE_CAM_HD inline void rigid_jacobian(const Proj &pr, const float *K, double fd, const double *pc, double *jx, double *jy) {
+    const double da[3] = {1.0 / pc[2], 0.0, (-pr.h0) / pc[2]}, db[3] = {0.0, 1.0 / pc[2], (-pr.h1) / pc[2]};
+    double cx[3], cy[3];
+    for (int k = 0; k < 3; ++k) jacobian_tail(pr, K, fd, da[k], db[k], cx + k, cy + k);
+    jx[0] = cx[2] * pc[1] - cx[1] * pc[2];
+    jx[1] = cx[0] * pc[2] - cx[2] * pc[0];
+    jx[2] = cx[1] * pc[0] - cx[0] * pc[1];
+    jx[3] = cx[0], jx[4] = cx[1], jx[5] = cx[2];
+    jy[0] = cy[2] * pc[1] - cy[1] * pc[2];
+    jy[1] = cy[0] * pc[2] - cy[2] * pc[0];
+    jy[2] = cy[1] * pc[0] - cy[0] * pc[1];
+    jy[3] = cy[0], jy[4] = cy[1], jy[5] = cy[2];
 }
 
 // Huber's cost of a residual of length e, and the weight of its normal equations; huber <= 0: the plain square

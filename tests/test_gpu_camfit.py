@@ -13,7 +13,7 @@ from conftest import env, pkg
 
 pytestmark = pytest.mark.gpu
 _made = {}
-TILE_RECORDS = 180                                # csrc/camfit.hip CF_RECORDS: records per LDS tile; a tile holds 180 // V (p, j) pairs
+TILE_RECORDS = 180                                # csrc/camfit.hip CamfitSums::RECORDS: records per LDS tile; a tile holds 180 // V (p, j) pairs
 
 
 def CF():

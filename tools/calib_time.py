@@ -10,8 +10,8 @@ tools/refine_rate.py: one warm-up call, then `--reps` regions of `--inner` calls
 synchronisations; the figure is the median region divided by `--inner`, the spread (min .. max) is printed beside it.  A
 pass is one accumulate() of the whole batch (two launches); the step is timed on its own (it synchronises and solves
 on the host).  The refinement runs `--iters` iterations with step_tol = 0.  The host statement is timed once.  For the
-kernels' own time run it under `rocprofv3 --kernel-trace --stats -- python tools/calib_time.py ...` (k_calib_frame,
-k_calib_add)."""
+kernels' own time run it under `rocprofv3 --kernel-trace --stats -- python tools/calib_time.py ...` (the instantiations of
+csrc/normal_sums.h: k_normal_frame<CalibSums, 1>, k_normal_add<28>)."""
 import argparse
 import importlib
 import json

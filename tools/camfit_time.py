@@ -9,8 +9,9 @@ call each, then `--reps` rounds; a round is one region of `--inner` camera-fit p
 synchronisations followed by one such region of calibration passes, so that the two see the same clocks and the same
 neighbours.  The figure is the median region divided by `--inner`, the spread (min .. max) beside it, and the ratio of the
 medians.  A pass is one accumulate() of the whole batch (two launches).  The step is timed once on its own.  For the
-kernels' own time run it under `rocprofv3 --kernel-trace --stats -- python tools/camfit_time.py ...` (k_camfit_frame,
-k_camfit_add, k_calib_frame, k_calib_add), in a run of its own."""
+kernels' own time run it under `rocprofv3 --kernel-trace --stats -- python tools/camfit_time.py ...` (the instantiations of
+csrc/normal_sums.h: k_normal_frame<CamfitSums, 2>, k_normal_add<105>, k_normal_frame<CalibSums, 1>, k_normal_add<28>), in a run
+of its own."""
 import argparse
 import importlib
 import json

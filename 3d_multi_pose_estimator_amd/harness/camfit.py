@@ -31,19 +31,14 @@ import numpy as np
 
 from . import calibrate as CB
 from . import reprojection as R
-from .refine import huber_weight, _rho
 
 N = 13
-SUMS = 105
-G0, COST = 91, 104
 POSE, FOCAL, CENTRE, K1, K2, K3 = 1, 2, 4, 8, 16, 32
 ALL = 63
 GROUPS = {'pose': POSE, 'focal': FOCAL, 'centre': CENTRE, 'k1': K1, 'k2': K2, 'k3': K3}
 GROUP_OF = [POSE] * 6 + [FOCAL, FOCAL, CENTRE, CENTRE, K1, K2, K3]          # unknown -> its group
 HELD, FEW_OBS, CONVERGED, STALLED, ACCEPTED, REJECTED = CB.HELD, CB.FEW_OBS, CB.CONVERGED, CB.STALLED, CB.ACCEPTED, CB.REJECTED
 MAX_RETRIES = CB.MAX_RETRIES
-TRI = [(k, l) for k in range(N) for l in range(k, N)]           # q = 0..90 -> (k, l)
-POSE_BLOCK = [TRI.index(kl) for kl in CB.TRI] + [G0 + k for k in range(6)] + [COST]    # calibrate's 28 sums among the 105
 
 
 def free_mask(free):
@@ -100,114 +95,31 @@ def project_camera(E, k, dist, X0, X1, X2, jacobian=False):
     return out
 
 
-def new_sums(V):
-    return {'acc': np.zeros((V, SUMS)), 'n_obs': np.zeros(V, np.int64), 'n_skipped': np.zeros(V, np.int64)}
-
-
-def observation_terms(cams, pb, persons, n_persons, poses, flags, joint_mask, threshold=0.5, huber_px=0.0):
-    """cams = (E, k, dist): the trial set.  -> (summed [F,Pcap,V,J] bool, skipped [F,Pcap,V,J] bool, terms
-    [F,Pcap,V,J,105] float64: what every observation adds to its camera's sums; unspecified where summed is False)."""
-    if not huber_px >= 0.0:
-        raise ValueError('huber_px >= 0')
-    huber = float(huber_px)
-    poses = np.asarray(poses)
-    if poses.dtype not in (np.float32, np.float64):
-        raise ValueError('poses must be float32 or float64')
-    E, k, dist = cams
-    sel, xy = R.selection(pb, persons, n_persons, flags, joint_mask, threshold)
-    F, Pcap, V, J = sel.shape
-    X = poses.astype(np.float64)
-    terms = np.zeros((F, Pcap, V, J, SUMS))
-    summed = np.zeros(sel.shape, bool)
-    finite = np.isfinite(X).all(axis=-1)                                          # [F,Pcap,J]
-    with np.errstate(all='ignore'):
-        for c in range(V):
-            p = project_camera(E[c], k[c], dist[c], X[..., 0], X[..., 1], X[..., 2], jacobian=True)
-            ok = sel[:, :, c] & finite & (p['pc'][2] > 0.0) & np.isfinite(p['px']) & np.isfinite(p['py'])
-            summed[:, :, c] = ok
-            rx = p['px'] - xy[:, :, c, :, 0]
-            ry = p['py'] - xy[:, :, c, :, 1]
-            e = np.sqrt(rx * rx + ry * ry)
-            w, rho = huber_weight(e, huber), _rho(e, huber)
-            Jx, Jy = p['Jx'], p['Jy']
-            for q, (a, b) in enumerate(TRI):
-                terms[:, :, c, :, q] = w * (Jx[a] * Jx[b] + Jy[a] * Jy[b])
-            for a in range(N):
-                terms[:, :, c, :, G0 + a] = w * (Jx[a] * rx + Jy[a] * ry)
-            terms[:, :, c, :, COST] = rho
-    return summed, sel & ~summed, terms
+FAMILY = CB.Family(N, project_camera)          # a trial set is (E [V,3,4], k [V,4] float32, dist [V,5]) by camera slot
+SUMS, TRI, G0, COST = FAMILY.SUMS, FAMILY.TRI, FAMILY.G0, FAMILY.COST           # 105; q = 0..90 -> (k, l); 91; 104
+POSE_BLOCK = [TRI.index(kl) for kl in CB.TRI] + [G0 + k for k in range(6)] + [COST]    # calibrate's 28 sums among the 105
 
 
 def camfit_pass_host(cams, pb, persons, n_persons, poses, flags, joint_mask, threshold=0.5, huber_px=0.0, sums=None):
     """One mpe_camfit_batch call on the host.  cams = (E [V,3,4], k [V,4] float32, dist [V,5]): the trial set; the other
     arguments as calibrate.calib_pass_host takes them.  sums: what earlier calls of the pass left; it is updated and
     returned: {'acc' [V,105], 'n_obs' [V], 'n_skipped' [V]}."""
-    persons = np.asarray(persons)
-    F, Pcap, V = persons.shape
-    sums = new_sums(V) if sums is None else sums
-    if F == 0:
-        return sums
-    summed, skipped, terms = observation_terms(cams, pb, persons, n_persons, poses, flags, joint_mask, threshold, huber_px)
-    J = summed.shape[-1]
-    S = np.zeros((F, V, SUMS))                                                    # the frame partials: left folds over p, then j
-    for p in range(Pcap):
-        for j in range(J):
-            S = np.where(summed[:, p, :, j, None], S + terms[:, p, :, j, :], S)
-    acc = sums['acc']
-    for f in range(F):                                                            # every frame, in order
-        acc = acc + S[f]
-    sums['acc'] = acc
-    sums['n_obs'] = sums['n_obs'] + summed.sum(axis=(0, 1, 3))
-    sums['n_skipped'] = sums['n_skipped'] + skipped.sum(axis=(0, 1, 3))
-    return sums
+    return CB.pass_host(FAMILY, cams, pb, persons, n_persons, poses, flags, joint_mask, threshold, huber_px, sums)
 
 
 # ---- the step: csrc/camfit_solve.h, statement for statement, on Python floats ------------------------------------------
 
 def solve(A, g, lam, mask):
     """A: the 91 entries of the upper triangle row by row, g: 13, lam, mask: the free groups -> delta (list of 13 floats,
-    0.0 for a held unknown) or None when a pivot is not > 0 or a delta is not finite.  camfit_solve: the elimination of
-    calibrate.solve6 over the free unknowns in ascending index."""
+    0.0 for a held unknown) or None when a pivot is not > 0 or a delta is not finite.  camfit_solve: calibrate.ldlt, the
+    elimination of calibrate.solve6, over the free unknowns in ascending index."""
     idx = free_unknowns(mask)
-    n = len(idx)
-    M = [[0.0] * n for _ in range(n)]
-    for a in range(n):
-        for b in range(a, n):
-            M[a][b] = M[b][a] = float(A[TRI.index((idx[a], idx[b]))])
-    for a in range(n):
-        M[a][a] = M[a][a] + lam * M[a][a]
-    L = [[0.0] * n for _ in range(n)]
-    D = [0.0] * n
-    for j in range(n):
-        v = [L[j][k] * D[k] for k in range(j)]
-        d = M[j][j]
-        for k in range(j):
-            d = d - L[j][k] * v[k]
-        if not d > 0.0:
-            return None
-        D[j] = d
-        for i in range(j + 1, n):
-            t = M[i][j]
-            for k in range(j):
-                t = t - L[i][k] * v[k]
-            L[i][j] = t / d
-    z = [0.0] * n
-    for i in range(n):
-        t = -float(g[idx[i]])
-        for k in range(i):
-            t = t - L[i][k] * z[k]
-        z[i] = t
-    y = [0.0] * n
-    for i in range(n - 1, -1, -1):
-        t = z[i] / D[i]
-        for k in range(i + 1, n):
-            t = t - L[k][i] * y[k]
-        y[i] = t
-    if not all(math.isfinite(x) for x in y):
+    y = CB.ldlt(A, g, N, idx, lam)
+    if y is None:
         return None
     delta = [0.0] * N
-    for a in range(n):
-        delta[idx[a]] = y[a]
+    for a, u in enumerate(idx):
+        delta[u] = y[a]
     return delta
 
 
@@ -244,25 +156,14 @@ def same_free(a, t, mask):
     return all(np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes() for g, x, y in pairs if mask & g)
 
 
-def max_abs(x):
-    m = 0.0
-    for v in x:
-        m = max(m, abs(float(v)))
-    return m
-
-
-class CameraState:
-    """camfit_cam: what a camera carries from step to step."""
+class CameraState(CB.LMState):
+    """camfit_cam: a camera's accepted and trial sets."""
 
     def __init__(self, E, k, dist):
+        super().__init__(FAMILY)
         self.a = CameraSet(E, k, dist)
         self.t = self.a.copy()
-        self.Aa = np.zeros(SUMS)
-        self.delta = [0.0] * N
-        self.lam = 1e-3
-        self.cost_start = self.last_rot = self.last_trans = self.last_pix = self.last_lens = 0.0
-        self.n_obs = 0
-        self.status = self.passes = 0
+        self.last_pix = self.last_lens = 0.0
 
     def trial(self, mask):
         for attempt in range(MAX_RETRIES + 1):
@@ -273,7 +174,7 @@ class CameraState:
                 if ok:
                     self.t = t
                     self.last_rot, self.last_trans = CB.norm3(d[:3]), CB.norm3(d[3:6])
-                    self.last_pix, self.last_lens = max_abs(d[6:10]), max_abs(d[10:13])
+                    self.last_pix, self.last_lens = CB.max_abs(d[6:10]), CB.max_abs(d[10:13])
                     if same_free(self.a, self.t, mask):
                         self.status |= CONVERGED
                     return
@@ -285,38 +186,22 @@ class CameraState:
         self.t = self.a.copy()
 
     def step(self, sums, n_obs, held, min_obs, tols, mask):
+        """camfit_cam_step."""
         rot_tol, trans_tol, pix_tol, lens_tol = tols
-        C = float(sums[COST])
-        first = self.passes == 0
-        self.passes += 1
-        self.status &= ~(ACCEPTED | REJECTED | HELD | FEW_OBS)
-        if first:
-            self.n_obs, self.cost_start = int(n_obs), C
-        if held or self.n_obs < min_obs:
-            self.status |= HELD | (FEW_OBS if self.n_obs < min_obs else 0)
-            self.Aa = np.array(sums, np.float64)
+        what = self.lm_step(sums, n_obs, held, min_obs)
+        if what in (CB.LM_REFUSED, CB.LM_STOPPED):
+            return
+        if what == CB.LM_HELD:
             self.t = self.a.copy()
             return
-        if self.status & (CONVERGED | STALLED):
-            return
-        if first or C < float(self.Aa[COST]):
+        if what != CB.LM_REJECTED:
             self.a = self.t.copy()
-            self.Aa = np.array(sums, np.float64)
-            self.status |= ACCEPTED
-            if not first:
-                self.lam = max(self.lam / 10.0, 1e-12)
-                d = self.delta
-                if CB.norm3(d[:3]) < rot_tol and max_abs(d[3:6]) < trans_tol and max_abs(d[6:10]) < pix_tol and max_abs(d[10:13]) < lens_tol:
-                    self.status |= CONVERGED
-                    return
-        else:
-            self.status |= REJECTED
-            self.lam = self.lam * 10.0
+        d = self.delta
+        if what == CB.LM_ACCEPTED and CB.norm3(d[:3]) < rot_tol and CB.max_abs(d[3:6]) < trans_tol and CB.max_abs(d[6:10]) < pix_tol and \
+                CB.max_abs(d[10:13]) < lens_tol:
+            self.status |= CONVERGED
+            return
         self.trial(mask)
-
-    @property
-    def done(self):
-        return bool(self.status & (HELD | CONVERGED | STALLED))
 
 
 class HostCameraFitter:
@@ -344,22 +229,7 @@ class HostCameraFitter:
 def camfit_step_host(state, sums, rot_tol, trans_tol, pix_tol=1e-3, lens_tol=1e-7):
     """mpe_camfit_step on the host: `state` a HostCameraFitter, `sums` what the pass at state.trial() left
     (camfit_pass_host).  -> the report: calibrate.calib_step_host's keys with 'last_pix', 'last_lens' and 'delta' [V,13]."""
-    n_obs = np.asarray(sums['n_obs'])
-    for c, cam in enumerate(state.cams):
-        if cam.passes > 0 and int(n_obs[c]) != cam.n_obs:
-            raise ValueError('the passes did not see the same data (camera %d: %d observations, %d in the first pass)'
-                             % (c, int(n_obs[c]), cam.n_obs))
-    for c, cam in enumerate(state.cams):
-        cam.step(sums['acc'][c], n_obs[c], c in state.hold, state.min_obs, (rot_tol, trans_tol, pix_tol, lens_tol), state.mask)
-    cams = state.cams
-    rep = {'status': np.array([c.status for c in cams], np.int32), 'passes': np.array([c.passes for c in cams], np.int32),
-           'n_obs': n_obs.astype(np.int64), 'n_skipped': np.asarray(sums['n_skipped']).astype(np.int64),
-           'cost_start': np.array([c.cost_start for c in cams]), 'cost': np.array([float(c.Aa[COST]) for c in cams]),
-           'lambda': np.array([c.lam for c in cams]), 'delta': np.array([c.delta for c in cams], np.float64),
-           'all_done': all(c.done for c in cams)}
-    for key in ('last_rot', 'last_trans', 'last_pix', 'last_lens'):
-        rep[key] = np.array([getattr(c, key) for c in cams])
-    return rep
+    return CB.step_host(state, sums, (rot_tol, trans_tol, pix_tol, lens_tol), state.mask, more=('last_pix', 'last_lens'))
 
 
 # ---- bookkeeping of the script ----------------------------------------------------------------------------------------
@@ -405,11 +275,8 @@ def model_distance(calib, truth, idx):
 
 
 def run(args):
-    from ..lib import MpeError
     from ..parameters import parameters
-    from ..pipeline import Engine
-    from .common import collect_work, match_stage, max_skeletons_per_camera, repair_stage, report_consolidate, report_regroup, teacher_scores
-    free = [g for g in args.free.split(',') if g]
+    free =[g for g in args.free.split(',') if g]
     free_mask(free)
     true_calib = rig_calibration(args)
     names = list(parameters.used_cameras_skeleton_matching)
@@ -425,80 +292,13 @@ def run(args):
         k[at, 2:] = k[at, 2:] + np.array([args.perturb_centre, -args.perturb_centre])
         dist[at, 0] = dist[at, 0] + args.perturb_k1
         calib = true_calib.with_extrinsics(E).with_intrinsics(k, dist)
-    if args.synthetic:
-        work = collect_work(args, true_calib)           # synthetic frames are projected with the true calibration
-    else:
-        work, n_input = [], 0
-        for file in args.testfiles:
-            with open(file, 'rb') as fh:
-                for frame in json.load(fh):
-                    n_input += 1
-                    if (n_input - 1) % args.datastep == 0:
-                        work.append((frame, None, None))
-        if not work:
-            raise SystemExit('no frames: give --testfiles or --synthetic N')
-    hold = [names[0]] if args.hold is None else list(args.hold)
-    for h in hold:
-        if h not in names:
-            raise SystemExit('--hold %s: not a camera of the rig (%s)' % (h, ', '.join(names)))
-    ppc = max(4, args.persons + 1, max_skeletons_per_camera(work))
+    work, hold = CB.script_work(args, true_calib, names)
     n_free = len(free_unknowns(free_mask(free)))
-
-    def stages(eng):
-        """calibrate.run's stages: match, triangulate, (--regroup) regroup, (--merge, --found) consolidate and (--refine) refine."""
-        kept, regrouped, consolidated = [], [], []
-        for at in range(0, len(work), args.batch):
-            chunk = work[at:at + args.batch]
-            frames = [{c: [f[c][0], f[c][1]] for c in f if json.loads(f[c][0])} for f, _, _ in chunk]
-            db = eng.to_device(eng.pack(frames))
-            if args.teacher_scores and chunk[0][2] is not None:
-                persons, n_persons = eng.cluster(db, teacher_scores(db, [w[2] for w in chunk]))
-            else:
-                persons, n_persons = match_stage(eng, args, db)
-            poses, flags = eng.triangulate(db, persons, n_persons, all_joints=True)
-            persons, n_persons, poses, flags = repair_stage(eng, args, db, persons, n_persons, poses, flags, 'triang', regrouped, consolidated,
-                                                            lambda rows, n: eng.triangulate(db, rows, n, all_joints=True))
-            if args.refine:
-                eng.refine(db, persons, n_persons, poses, flags, 'triang', max_iters=args.refine, huber_px=args.refine_huber, out=poses)
-            kept.append((db, persons, n_persons, poses, flags))
-        eng.sync_status()
-        if args.regroup:
-            report_regroup(args, regrouped)
-        if args.merge or args.found:
-            report_consolidate(args, consolidated)
-        return kept
-
     start = calib
     report = {'cameras': names, 'hold': hold, 'free': free, 'moved': moved, 'rounds': []}
-    first_rms = None
-    for rnd in range(max(1, args.rounds)):
-        eng = Engine(parameters, calib, max_frames=args.batch, max_persons_per_camera=ppc)
-        batches = stages(eng)
-        before, _ = CB.rms_per_camera(eng, batches)
-        first_rms = before if first_rms is None else first_rms
-        fit = eng.camera_fitter('triang', free=free, huber_px=args.calib_huber, min_obs=max(args.min_obs, n_free), hold=hold)
-        rep, passes = None, 0
-        for _ in range(max(1, args.passes)):
-            for b in batches:
-                fit.accumulate(*b)
-            try:
-                rep = fit.step(args.rot_tol, args.trans_tol, args.pix_tol, args.lens_tol)
-            except MpeError as err:                      # a trial that loses an observation (a joint behind the camera): keep what is accepted
-                print('round %d stops after %d passes: %s' % (rnd + 1, passes, err))
-                break
-            passes += 1
-            if rep['all_done']:
-                break
-        calib = fit.calibration()
-        fit.close()
-        eng.close()
-        if rep is not None:
-            report['rounds'].append({'passes': passes, 'rms_before': before.tolist(), 'cost_start': rep['cost_start'].tolist(),
-                                     'cost': rep['cost'].tolist(), 'status': rep['status'].tolist(), 'n_obs': rep['n_obs'].tolist()})
-            print('round %d: %d passes, cost %.6g -> %.6g px^2' % (rnd + 1, passes, float(np.sum(rep['cost_start'])), float(np.sum(rep['cost']))))
-    eng = Engine(parameters, calib, max_frames=args.batch, max_persons_per_camera=ppc)
-    last_rms, counts = CB.rms_per_camera(eng, stages(eng))
-    eng.close()
+    calib, first_rms, last_rms, counts = CB.alternate(
+        args, work, calib, lambda eng: eng.camera_fitter('triang', free=free, huber_px=args.calib_huber, min_obs=max(args.min_obs, n_free), hold=hold),
+        (args.rot_tol, args.trans_tol, args.pix_tol, args.lens_tol), report)
     k0, k1 = start.intrinsics().astype(np.float64), calib.intrinsics().astype(np.float64)
     report.update(rms_before=first_rms.tolist(), rms_after=last_rms.tolist(), n_obs=counts.tolist(),
                   k_start=k0[idx].tolist(), k=k1[idx].tolist(), dist=np.asarray(calib.dist)[idx].tolist())

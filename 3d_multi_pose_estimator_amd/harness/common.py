@@ -566,6 +566,30 @@ def collect_work(args, calib, src=None):
     return work
 
 
+def load_frames(args):
+    """The frames of --testfiles at --datastep, the counter running over all files, as they are: no ground truth is read
+    (harness.calibrate, harness.camfit, harness.lag)."""
+    frames, n_input = [], 0
+    for file in args.testfiles:
+        with open(file, 'rb') as fh:
+            for frame in json.load(fh):
+                n_input += 1
+                if (n_input - 1) % args.datastep == 0:
+                    frames.append(frame)
+    if not frames:
+        raise SystemExit('no frames: give --testfiles or --synthetic N')
+    return frames
+
+
+def held_cameras(hold, names):
+    """--hold (a list of names, or None: the rig's first camera) checked against the rig's `names` -> the list."""
+    hold = [names[0]] if hold is None else list(hold)
+    for h in hold:
+        if h not in names:
+            raise SystemExit('--hold %s: not a camera of the rig (%s)' % (h, ', '.join(names)))
+    return hold
+
+
 def evaluate(work, infer, mode, T_i1, batch=256):
     """The callers' loop around the inference path.  `infer(frames, owners)` receives the
     pre-processed frames of one batch (cameras with an empty skeleton list dropped, :182-191) and

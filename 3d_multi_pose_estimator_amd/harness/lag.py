@@ -332,7 +332,7 @@ def run(args):
     from ..pipeline import Engine
     from .. import synthetic
     from .calibrate import rig_calibration
-    from .common import match_stage, max_skeletons_per_camera
+    from .common import held_cameras, load_frames, match_stage, max_skeletons_per_camera
     calib = rig_calibration(args)
     names = list(parameters.used_cameras_skeleton_matching)
     true_lags = None
@@ -342,18 +342,8 @@ def run(args):
             raise SystemExit('--lags: %d values for %d cameras' % (len(true_lags), len(names)))
         frames = synthetic.lagged_recording(calib, args.synthetic, true_lags, n_bodies=args.persons, seed=args.lag_seed, weave=args.weave)[0]
     else:
-        frames, n_input = [], 0
-        for file in args.testfiles:
-            with open(file, 'rb') as fh:
-                for frame in json.load(fh):
-                    n_input += 1
-                    if (n_input - 1) % args.datastep == 0:
-                        frames.append(frame)
-        if not frames:
-            raise SystemExit('no frames: give --testfiles or --synthetic N')
-    hold = names[0] if args.hold is None else args.hold
-    if hold not in names:
-        raise SystemExit('--hold %s: not a camera of the rig (%s)' % (hold, ', '.join(names)))
+        frames = load_frames(args)
+    hold = held_cameras(None if args.hold is None else [args.hold], names)[0]
     h = names.index(hold)
     ppc = max(4, args.persons + 1, max_skeletons_per_camera([(f, None, None) for f in frames]))
     eng = Engine(parameters, calib, max_frames=args.batch, max_persons_per_camera=ppc)

@@ -1762,12 +1762,12 @@ class Tracker(_DeviceState):
         self._issued = None
 
 
-class Calibrator(_DeviceState):
-    """Engine.calibrator's object: trial extrinsics and the 28 sums per camera on the device, the Levenberg-Marquardt
-    state of the cameras in the library.  A pass is accumulate() over every batch of the recording, in any chunking (the
-    sums are the same bits), then step(); passes repeat on the same batches and poses until the report says all_done.
-    accumulate() stays on the current stream and neither synchronises nor reads back; step() synchronises."""
-    _prefix, _noun = 'mpe_calib', 'calibrator'
+class _CameraLM(_DeviceState):
+    """What Calibrator and CameraFitter share (normal_state of csrc/api.hip, one algorithm at two sizes): trial cameras and
+    `_sums` sums per camera on the device, the Levenberg-Marquardt state of the cameras in the library, `_unknowns` of them
+    per camera; `_last` names the step sizes a report carries."""
+    _sums = _unknowns = None
+    _last = ('last_rot', 'last_trans')
 
     def __init__(self, eng, kind, huber_px, min_obs, hold):
         if kind not in ('est', 'triang'):
@@ -1780,6 +1780,7 @@ class Calibrator(_DeviceState):
             raise ValueError('hold names cameras of the engine')
         self.kind, self.huber_px, self.min_obs = kind, float(huber_px), int(min_obs)
         self.hold_mask = sum(1 << i for i in set(idx))
+        self._batch = getattr(eng.lib, self._prefix + '_batch')
         self._create(eng)
 
     def accumulate(self, db, persons, n_persons, poses, flags, joint_mask=None, threshold=0.5):
@@ -1792,36 +1793,60 @@ class Calibrator(_DeviceState):
         a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
         a.huber_px = self.huber_px
         a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
-        eng._chk(eng.lib.mpe_calib_batch(eng.ctx, eng._stream(), self.state, C.byref(db.struct), C.byref(a)))
+        eng._chk(self._batch(eng.ctx, eng._stream(), self.state, C.byref(db.struct), C.byref(a)))
 
     def read(self):
-        """The sums of the pass so far (synchronises) -> {'acc' [V,28] f64, 'n_obs' [V] i64, 'n_skipped' [V] i64}."""
+        """The sums of the pass so far (synchronises) -> {'acc' [V,28] f64 (the CameraFitter: [V,105]), 'n_obs' [V] i64,
+        'n_skipped' [V] i64}."""
         self._open()
         eng = self.eng
-        acc, n, k = np.zeros((eng.V, L.MPE_CALIB_SUMS)), np.zeros(eng.V, np.int64), np.zeros(eng.V, np.int64)
+        acc, n, k = np.zeros((eng.V, self._sums)), np.zeros(eng.V, np.int64), np.zeros(eng.V, np.int64)
         i64p = C.POINTER(C.c_int64)
-        eng._chk(eng.lib.mpe_calib_read(eng.ctx, eng._stream(), self.state, acc.ctypes.data_as(L.c_f64p), n.ctypes.data_as(i64p),
-                                        k.ctypes.data_as(i64p)))
+        eng._chk(getattr(eng.lib, self._prefix + '_read')(eng.ctx, eng._stream(), self.state, acc.ctypes.data_as(L.c_f64p),
+                                                          n.ctypes.data_as(i64p), k.ctypes.data_as(i64p)))
         return {'acc': acc, 'n_obs': n, 'n_skipped': k}
+
+    def _step(self, a, rep):
+        """`_prefix`_step with the filled step arguments -> the report struct as step()'s dictionary."""
+        self._open()
+        eng = self.eng
+        a.min_obs, a.hold_mask = self.min_obs, self.hold_mask
+        eng._chk(getattr(eng.lib, self._prefix + '_step')(eng.ctx, eng._stream(), self.state, C.byref(a), C.byref(rep)))
+        cams = [rep.cam[c] for c in range(rep.n_cameras)]
+        out = {k: np.array([getattr(c, k) for c in cams], np.int32) for k in ('status', 'passes')}
+        out.update({k: np.array([getattr(c, k) for c in cams], np.int64) for k in ('n_obs', 'n_skipped')})
+        out.update({k: np.array([getattr(c, k) for c in cams], np.float64) for k in ('cost_start', 'cost') + self._last})
+        out['lambda'] = np.array([c.lambda_ for c in cams], np.float64)
+        out['delta'] = np.array([list(c.delta) for c in cams], np.float64).reshape(-1, self._unknowns)
+        out['all_done'] = bool(rep.all_done)
+        return out
+
+    def launches(self):
+        self._open()
+        return super().launches()
+
+    def reset(self):
+        """Start afresh from the engine's own cameras (the Calibrator: from their extrinsics)."""
+        self._open()
+        super().reset()
+
+
+class Calibrator(_CameraLM):
+    """Engine.calibrator's object: trial extrinsics and the 28 sums per camera on the device, the Levenberg-Marquardt
+    state of the cameras in the library.  A pass is accumulate() over every batch of the recording, in any chunking (the
+    sums are the same bits), then step(); passes repeat on the same batches and poses until the report says all_done.
+    accumulate() stays on the current stream and neither synchronises nor reads back; step() synchronises."""
+    _prefix, _noun = 'mpe_calib', 'calibrator'
+    _sums, _unknowns = L.MPE_CALIB_SUMS, 6
 
     def step(self, rot_tol=1e-7, trans_tol=1e-6):
         """The end of a pass: per camera the pass is accepted or rejected and the next trial extrinsics are set
         (mpe_calib_step).  -> {'status' (MPE_CALIB_* bits), 'passes', 'n_obs', 'n_skipped', 'cost_start', 'cost',
         'lambda', 'last_rot', 'last_trans'} as arrays over the cameras, 'delta' [V,6] (the perturbation of the last trial
         built) and 'all_done'."""
-        self._open()
-        eng = self.eng
-        a, rep = L.mpe_calib_step_args(), L.mpe_calib_report()
-        a.rot_tol, a.trans_tol, a.min_obs, a.hold_mask = float(rot_tol), float(trans_tol), self.min_obs, self.hold_mask
-        eng._chk(eng.lib.mpe_calib_step(eng.ctx, eng._stream(), self.state, C.byref(a), C.byref(rep)))
-        cams = [rep.cam[c] for c in range(rep.n_cameras)]
-        out = {k: np.array([getattr(c, k) for c in cams], np.int32) for k in ('status', 'passes')}
-        out.update({k: np.array([getattr(c, k) for c in cams], np.int64) for k in ('n_obs', 'n_skipped')})
-        out.update({k: np.array([getattr(c, k) for c in cams], np.float64) for k in ('cost_start', 'cost', 'last_rot', 'last_trans')})
-        out['lambda'] = np.array([c.lambda_ for c in cams], np.float64)
-        out['delta'] = np.array([list(c.delta) for c in cams], np.float64).reshape(-1, 6)
-        out['all_done'] = bool(rep.all_done)
-        return out
+        a = L.mpe_calib_step_args()
+        a.rot_tol, a.trans_tol = float(rot_tol), float(trans_tol)
+        return self._step(a, L.mpe_calib_report())
 
     def extrinsics(self):
         """-> (accepted [V,3,4], trial [V,3,4]) f64, in the engine's camera order."""
@@ -1848,82 +1873,32 @@ class Calibrator(_DeviceState):
             raise ValueError('E must be [%d,3,4]' % eng.V)
         eng._chk(eng.lib.mpe_calib_set_extrinsics(eng.ctx, eng._stream(), self.state, E.ctypes.data_as(L.c_f64p)))
 
-    def launches(self):
-        self._open()
-        return super().launches()
 
-    def reset(self):
-        """Start afresh from the engine's own extrinsics."""
-        self._open()
-        super().reset()
-
-
-class CameraFitter(_DeviceState):
+class CameraFitter(_CameraLM):
     """Engine.camera_fitter's object: the trial set (extrinsics, fx fy cx cy as float32, lens terms) and the 105 sums per
     camera on the device, the Levenberg-Marquardt state of the cameras in the library.  Used as the Calibrator is: a pass
     is accumulate() over every batch of the recording, in any chunking (the sums are the same bits), then step().
     accumulate() stays on the current stream and neither synchronises nor reads back; step() synchronises."""
     _prefix, _noun = 'mpe_camfit', 'camera fitter'
+    _sums, _unknowns = L.MPE_CAMFIT_SUMS, L.MPE_CAMFIT_UNKNOWNS
+    _last = _CameraLM._last + ('last_pix', 'last_lens')
 
     def __init__(self, eng, kind, free, huber_px, min_obs, hold):
-        if kind not in ('est', 'triang'):
-            raise ValueError('kind must be est or triang')
-        if not huber_px >= 0.0:
-            raise ValueError('huber_px must be >= 0')
         if isinstance(free, str):
             free = [g for g in free.split(',') if g]
         unknown = [g for g in free if g not in L.MPE_CAMFIT_GROUPS]
         if unknown or not free:
             raise ValueError('free names groups out of %s' % ', '.join(L.MPE_CAMFIT_GROUPS))
-        names = list(eng.params.used_cameras_skeleton_matching)
-        idx = [names.index(h) if isinstance(h, str) else int(h) for h in hold]
-        if any(not 0 <= i < eng.V for i in idx):
-            raise ValueError('hold names cameras of the engine')
-        self.kind, self.huber_px, self.min_obs = kind, float(huber_px), int(min_obs)
         self.free_mask = sum(L.MPE_CAMFIT_GROUPS[g] for g in set(free))
-        self.hold_mask = sum(1 << i for i in set(idx))
-        self._create(eng)
-
-    def accumulate(self, db, persons, n_persons, poses, flags, joint_mask=None, threshold=0.5):
-        """The observations of one batch added to the pass (arguments as Engine.refine takes them)."""
-        self._open()
-        eng = self.eng
-        B, tri, joint_mask = eng._pose_args(db, persons, n_persons, poses, flags, self.kind, joint_mask, ('est', 'triang'))
-        a = L.mpe_calib_args()
-        a.n_frames, a.pcap, a.n_joints = B, eng.pcap, eng.J
-        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
-        a.huber_px = self.huber_px
-        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
-        eng._chk(eng.lib.mpe_camfit_batch(eng.ctx, eng._stream(), self.state, C.byref(db.struct), C.byref(a)))
-
-    def read(self):
-        """The sums of the pass so far (synchronises) -> {'acc' [V,105] f64, 'n_obs' [V] i64, 'n_skipped' [V] i64}."""
-        self._open()
-        eng = self.eng
-        acc, n, k = np.zeros((eng.V, L.MPE_CAMFIT_SUMS)), np.zeros(eng.V, np.int64), np.zeros(eng.V, np.int64)
-        i64p = C.POINTER(C.c_int64)
-        eng._chk(eng.lib.mpe_camfit_read(eng.ctx, eng._stream(), self.state, acc.ctypes.data_as(L.c_f64p), n.ctypes.data_as(i64p),
-                                         k.ctypes.data_as(i64p)))
-        return {'acc': acc, 'n_obs': n, 'n_skipped': k}
+        super().__init__(eng, kind, huber_px, min_obs, hold)
 
     def step(self, rot_tol=1e-7, trans_tol=1e-6, pix_tol=1e-3, lens_tol=1e-7):
         """The end of a pass: per camera the pass is accepted or rejected and the next trial set is built
         (mpe_camfit_step).  -> Calibrator.step's keys with 'last_pix', 'last_lens' and 'delta' [V,13]."""
-        self._open()
-        eng = self.eng
-        a, rep = L.mpe_camfit_step_args(), L.mpe_camfit_report()
+        a = L.mpe_camfit_step_args()
         a.rot_tol, a.trans_tol, a.pix_tol, a.lens_tol = float(rot_tol), float(trans_tol), float(pix_tol), float(lens_tol)
-        a.min_obs, a.hold_mask, a.free_mask = self.min_obs, self.hold_mask, self.free_mask
-        eng._chk(eng.lib.mpe_camfit_step(eng.ctx, eng._stream(), self.state, C.byref(a), C.byref(rep)))
-        cams = [rep.cam[c] for c in range(rep.n_cameras)]
-        out = {k: np.array([getattr(c, k) for c in cams], np.int32) for k in ('status', 'passes')}
-        out.update({k: np.array([getattr(c, k) for c in cams], np.int64) for k in ('n_obs', 'n_skipped')})
-        out.update({k: np.array([getattr(c, k) for c in cams], np.float64)
-                    for k in ('cost_start', 'cost', 'last_rot', 'last_trans', 'last_pix', 'last_lens')})
-        out['lambda'] = np.array([c.lambda_ for c in cams], np.float64)
-        out['delta'] = np.array([list(c.delta) for c in cams], np.float64).reshape(-1, L.MPE_CAMFIT_UNKNOWNS)
-        out['all_done'] = bool(rep.all_done)
-        return out
+        a.free_mask = self.free_mask
+        return self._step(a, L.mpe_camfit_report())
 
     def cameras(self):
         """-> (accepted, trial), each (E [V,3,4] f64, k [V,4] f32: fx fy cx cy, dist [V,5] f64), in the engine's camera order."""
@@ -1955,15 +1930,6 @@ class CameraFitter(_DeviceState):
             at = calib.index(cam)
             E[at], k[at], dist[at] = Ea[i], ka[i], da[i]
         return calib.with_extrinsics(E).with_intrinsics(k, dist)
-
-    def launches(self):
-        self._open()
-        return super().launches()
-
-    def reset(self):
-        """Start afresh from the engine's own cameras."""
-        self._open()
-        super().reset()
 
 
 class LagEstimator(_DeviceState):

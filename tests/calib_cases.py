@@ -78,17 +78,19 @@ class Scene:
                 pb.xy[h0 + i, :, 0], pb.xy[h0 + i, :, 1] = p['px'] + noise[:, 0], p['py'] + noise[:, 1]
         return pb
 
-    def one_pass(self, E, sums=None, frames=None, poses=None, flags=None, mask=ALL_JOINTS, huber_px=0.0, pb=None):
-        """calib_pass_host over the scene, or over the frames [a, b) of it packed on their own."""
+    def one_pass(self, E, sums=None, frames=None, poses=None, flags=None, mask=ALL_JOINTS, huber_px=0.0, pb=None, pass_host=None):
+        """calib_pass_host at the extrinsics E (or pass_host -- camfit_pass_host -- at the trial set E) over the scene, or
+        over the frames [a, b) of it packed on their own."""
         poses = self.truth if poses is None else poses
         flags = self.flags if flags is None else flags
         pb = self.pb if pb is None else pb
+        sl = slice(None)
         if frames is not None:
             a, b = frames
             pb, sl = self.sub_batch(a, b), slice(a, b)
-            return CB().calib_pass_host(self.calib, E, pb, self.persons[sl], self.n_persons[sl], poses[sl], flags[sl], mask,
-                                        huber_px=huber_px, sums=sums)
-        return CB().calib_pass_host(self.calib, E, pb, self.persons, self.n_persons, poses, flags, mask, huber_px=huber_px, sums=sums)
+        if pass_host is None:
+            return CB().calib_pass_host(self.calib, E, pb, self.persons[sl], self.n_persons[sl], poses[sl], flags[sl], mask, huber_px=huber_px, sums=sums)
+        return pass_host(E, pb, self.persons[sl], self.n_persons[sl], poses[sl], flags[sl], mask, huber_px=huber_px, sums=sums)
 
     def sub_batch(self, a, b):
         """Frames [a, b) packed on their own, with this scene's detections."""

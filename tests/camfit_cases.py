@@ -36,16 +36,9 @@ def moved_set(scene, seed, deg=0.4, mm=8.0, focal=1.01, centre=(5.0, -5.0), kd=(
     return E, k, dist
 
 
-def one_pass(scene, cams, sums=None, frames=None, poses=None, flags=None, mask=ALL_JOINTS, huber_px=0.0, pb=None):
-    """camfit_pass_host over the scene, or over the frames [a, b) of it packed on their own."""
-    poses = scene.truth if poses is None else poses
-    flags = scene.flags if flags is None else flags
-    pb = scene.pb if pb is None else pb
-    sl = slice(None)
-    if frames is not None:
-        a, b = frames
-        pb, sl = scene.sub_batch(a, b), slice(a, b)
-    return CF().camfit_pass_host(cams, pb, scene.persons[sl], scene.n_persons[sl], poses[sl], flags[sl], mask, huber_px=huber_px, sums=sums)
+def one_pass(scene, cams, **kw):
+    """camfit_pass_host over the scene, or over the frames [a, b) of it packed on their own (Scene.one_pass's arguments)."""
+    return scene.one_pass(cams, pass_host=CF().camfit_pass_host, **kw)
 
 
 def run_host(scene, start, passes, tols, free=63, hold=(), min_obs=13, huber_px=0.0, until_done=True, log=None, **pass_kw):

@@ -2004,6 +2004,27 @@ int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_r
     return MPE_OK;
 }
 
+int mpe_posecov_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_posecov_args *a) {
+    int rc = check_batch(ctx, b);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPE_ERR_INVALID, "mpe_posecov_batch: NULL argument");
+    DeviceGuard dg(ctx);
+    bool run;
+    rc = check_batch_rows(ctx, "mpe_posecov_batch", b, a, &run);
+    if (rc) return rc;
+    if (!(a->sigma_px > 0.0) || !(a->sigma_px < HUGE_VAL))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_posecov_batch: sigma_px %g must be positive and finite", a->sigma_px);
+    if (!(a->gate_m >= 0.0) || !(a->huber_px >= 0.0))
+        return fail(ctx, MPE_ERR_INVALID, "mpe_posecov_batch: gate_m %g and huber_px %g must not be negative", a->gate_m, a->huber_px);
+    if (a->d_flags_out && !a->joint_flags)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_posecov_batch: d_flags_out needs joint_flags 1 (the gate clears joints, not persons)");
+    if (!run) return MPE_OK;
+    if (row_inputs_missing(a) || !a->d_cov || !a->d_sigma || !a->d_status || !a->d_n_views)
+        return fail(ctx, MPE_ERR_INVALID, "mpe_posecov_batch: NULL argument");
+    HIPCHK(ctx, launch_posecov(static_cast<hipStream_t>(stream), ctx->d_cfg, ctx->cfg.n_cameras, *b, *a));
+    return MPE_OK;
+}
+
 int mpe_regroup_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_regroup_args *a) {
     int rc = check_batch(ctx, b);
     if (rc) return rc;

@@ -483,6 +483,8 @@ hipError_t launch_track_score(hipStream_t s, mpe_track_score_state *st, const mp
 hipError_t launch_reproject(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_reproject_args &a);
 // refine.hip
 hipError_t launch_refine(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_refine_args &a);
+// posecov.hip
+hipError_t launch_posecov(hipStream_t s, const DevCfg *cfg, int V, const mpe_batch &b, const mpe_posecov_args &a);
 // regroup.hip
 hipError_t launch_regroup(hipStream_t s, const DevCfg *cfg, int V, int min_views, int hmax, int32_t *sticky, const mpe_batch &b,
                           const mpe_regroup_args &a);

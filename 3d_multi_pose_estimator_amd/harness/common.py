@@ -125,6 +125,18 @@ def build_parser(description):
                         '(mpe_refine_batch: at most ITERS Levenberg-Marquardt iterations per joint, 1..64) and the refined poses are scored; '
                         'one further line reports the solved joints, the share that moved and the mean cost before and after')
     p.add_argument('--refine-huber', type=float, default=0.0, metavar='PX', help='--refine: Huber threshold in pixels (0: plain least squares)')
+    p.add_argument('--uncertainty', type=float, default=0.0, metavar='PX',
+                   help='implies --device-metrics; every joint gets its 3 x 3 covariance from the cameras that saw it, for detections with '
+                        'PX pixels of noise in x and in y (mpe_posecov_batch: PX^2 times the inverse of the normal matrix of --refine, the '
+                        'Gauss-Newton approximation), right after --refine (or the time-aware refinement of --lags; on the unrefined poses '
+                        'without either) and before tracking; one further line reports the joints computed and the median, 95th percentile '
+                        'and maximum sigma in millimetres, and with --refine and --refine-huber 0 the pooled pixel sigma of the recording, '
+                        'which says whether PX was a fair choice.  It is the covariance of the per-frame estimate: untimed (lags are '
+                        'ignored, as in the DLT), and it says nothing about what --smooth and --bones do afterwards.  It acts in '
+                        'metrics_from_model and metrics_from_triangulation; the other harnesses accept and ignore it')
+    p.add_argument('--uncertainty-gate', type=float, default=0.0, metavar='MM',
+                   help='--uncertainty, metrics_from_triangulation only (the flags of metrics_from_model are per person): a joint whose sigma is '
+                        'above MM millimetres loses its flag and is then neither tracked, scored nor written; the line reports how many')
     p.add_argument('--regroup', type=float, default=0.0, metavar='PX',
                    help='after the 3D stage the person proposals are repaired by reprojection consistency (mpe_regroup_batch: a skeleton whose mean '
                         'distance from its row\'s projected pose is PX pixels or more is released, free skeletons within PX are attached to rows '
@@ -722,6 +734,13 @@ def run(args, mode):
                              and args.bones_huber >= 0):
         raise ValueError('--bones-refine takes 1 .. 64 sweeps, --bones-bin a width > 0, --bones-weight and --bones-huber no negative value '
                          '(got %d, %g, %g, %g)' % (bones_refine, args.bones_bin, args.bones_weight, args.bones_huber))
+    uncertainty = float(getattr(args, 'uncertainty', 0.0) or 0.0)
+    uncertainty_gate = float(getattr(args, 'uncertainty_gate', 0.0) or 0.0)
+    if uncertainty != 0.0 or uncertainty_gate != 0.0:        # a NaN as well
+        if not (uncertainty > 0.0 and np.isfinite(uncertainty) and uncertainty_gate >= 0.0):
+            raise ValueError('--uncertainty takes a pixel noise > 0 and --uncertainty-gate no negative value (got %g, %g)' % (uncertainty, uncertainty_gate))
+        if uncertainty_gate and mode == 'mlp':
+            raise ValueError('--uncertainty-gate clears joint flags: metrics_from_triangulation only (the flags of metrics_from_model are per person)')
     relink = float(getattr(args, 'relink', 0.0) or 0.0)
     if relink != 0.0:                                        # a NaN as well
         relink_options = {'gate_m': relink / 1000.0, 'min_gap': args.track_gap + 2, 'max_gap': args.relink_max_gap, 'reach_m': args.relink_reach,
@@ -739,7 +758,7 @@ def run(args, mode):
             raise ValueError('--lags needs --track: the offsets of a joint come from its track')
         lags = load_lags(args.lags_file, list(parameters.used_cameras_skeleton_matching))
     write_path = getattr(args, 'write_poses', None)
-    if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine or write_path:
+    if getattr(args, 'device_gt', False) or getattr(args, 'track', False) or refine or write_path or uncertainty:
         args.device_metrics = True
     src = [] if device_gt else None
     work = collect_work(args, calib, src)
@@ -756,6 +775,7 @@ def run(args, mode):
     last = {}                                                # what the track score of a batch needs from infer_device
     refined = []
     timed = []                                               # --lags: the time-aware refinement's outputs of every batch
+    measured = []                                            # --uncertainty: mpe_posecov_batch's sigma and status of every batch
     regrouped = []                                         # --regroup: per round, the counts of every batch
     consolidated = []                                        # --merge / --found: the same of the consolidation
     used_mask = sum(1 << int(j) for j in parameters.used_joints)     # the joints both 3D stages of this script fill in
@@ -864,7 +884,16 @@ def run(args, mode):
         elif refine:
             ref = eng.refine(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', max_iters=refine,
                              huber_px=args.refine_huber, out=poses)
-            refined.append({k: ref[k].cpu().numpy() for k in ('status', 'cost0', 'cost1')})
+            refined.append({k: ref[k].cpu().numpy() for k in ('status', 'cost0', 'cost1') + (('n_views',) if uncertainty else ())})
+        if uncertainty:
+            # the covariance of the poses as they are now; with a gate the joints above it lose their flag here, before tracking
+            # (with --lags the tracker has already run on the unrefined poses: the gate then acts on what is smoothed, scored and written)
+            pc = eng.pose_covariance(db, persons, n_persons, poses, flags, 'est' if mode == 'mlp' else 'triang', uncertainty,
+                                     huber_px=args.refine_huber if (refine or lags is not None) else 0.0, gate_m=uncertainty_gate / 1000.0,
+                                     flags_out=flags if uncertainty_gate else None)
+            in_use = torch.arange(poses.shape[1], device=poses.device)[None, :] < n_persons.clamp(0, poses.shape[1])[:, None]
+            left = (flags != 0) & (in_use[..., None] if flags.dim() == 3 else in_use)
+            measured.append(dict({k: pc[k].cpu().numpy() for k in ('sigma', 'status')}, flagged=int(left.sum()) * (1 if flags.dim() == 3 else J)))
         torch.cuda.synchronize()
         t2 = time.time()
         if smoother is not None or skeleton is not None:
@@ -993,6 +1022,14 @@ def run(args, mode):
         out['refine'] = r = refine_summary(refined)
         print('Refined (at most %d iterations, Huber %g px): %d joints solved, %.1f %% moved, mean cost %.6g -> %.6g px^2'
               % (refine, args.refine_huber, r['solved'], 100.0 * r['moved_share'], r['mean_cost0'], r['mean_cost1']))
+    if uncertainty:
+        from . import uncertainty as uncertainty_rule
+        out['uncertainty'] = r = uncertainty_rule.summary(measured)
+        r['sigma_px'], r['gate_mm'] = uncertainty, uncertainty_gate
+        r['joints_flagged'] = sum(m['flagged'] for m in measured)      # what goes on to tracking, scoring and writing, after the gate
+        if refine and lags is None and args.refine_huber == 0.0:
+            r['pooled_sigma_px'], r['pooled_dof'] = uncertainty_rule.pixel_sigma(refined)
+        print(uncertainty_rule.report_line(uncertainty, uncertainty_gate, r, r.get('pooled_sigma_px')))
     if tracker is not None:
         out['tracks'] = summary.result()
         print('Tracks (gate %g m, gap %d): %d, mean length %.3f frames, %d born after the first frame'

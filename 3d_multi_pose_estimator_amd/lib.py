@@ -154,6 +154,15 @@ class mpe_reproject_args(C.Structure):
                 ('d_res', C.c_void_p)]
 
 
+class mpe_posecov_args(C.Structure):
+    _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
+                ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float), ('huber_px', C.c_double),
+                ('sigma_px', C.c_double), ('gate_m', C.c_double),
+                ('d_persons', C.c_void_p), ('d_n_persons', C.c_void_p), ('d_poses', C.c_void_p), ('d_flags', C.c_void_p),
+                ('d_cov', C.c_void_p), ('d_sigma', C.c_void_p), ('d_status', C.c_void_p), ('d_n_views', C.c_void_p),
+                ('d_flags_out', C.c_void_p)]
+
+
 class mpe_refine_args(C.Structure):
     _fields_ = [('n_frames', C.c_int32), ('pcap', C.c_int32), ('n_joints', C.c_int32), ('pose_f64', C.c_int32),
                 ('joint_flags', C.c_int32), ('joint_mask', C.c_uint32), ('threshold', C.c_float), ('max_iters', C.c_int32),
@@ -333,6 +342,9 @@ MPE_TRACK_SCORE_OVER_IDS, MPE_TRACK_SCORE_MAX_TABLE = 1, 1 << 22
 MPE_REFINE_SOLVED, MPE_REFINE_MOVED, MPE_REFINE_CONVERGED, MPE_REFINE_FEW_VIEWS, MPE_REFINE_BAD_START = 1, 2, 4, 8, 16
 MPE_REFINE_MAX_ITERS = 64
 
+# per-joint status bits of mpe_posecov_batch
+MPE_POSECOV_COMPUTED, MPE_POSECOV_FEW_VIEWS, MPE_POSECOV_BAD_POSE, MPE_POSECOV_SINGULAR, MPE_POSECOV_GATED = 1, 8, 16, 32, 64
+
 # per-frame status bits, the pass flags and the row cap of mpe_regroup_batch
 MPE_REGROUP_BAD_ROWS, MPE_REGROUP_OVER_CAP = 1, 2
 MPE_REGROUP_RELEASE, MPE_REGROUP_ATTACH = 1, 2
@@ -445,6 +457,7 @@ SYMBOLS = {
     'mpe_track_score_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mpe_reproject_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_reproject_args)]),
     'mpe_refine_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_refine_args)]),
+    'mpe_posecov_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_posecov_args)]),
     'mpe_regroup_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_regroup_args)]),
     'mpe_consolidate_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mpe_batch), C.POINTER(mpe_consolidate_args)]),
     'mpe_calib_create': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

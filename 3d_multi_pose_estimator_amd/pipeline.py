@@ -1235,6 +1235,46 @@ class Engine:
         self._chk(self.lib.mpe_refine_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
         return res
 
+    def pose_covariance(self, db, persons, n_persons, poses, flags, kind, sigma_px, joint_mask=None, threshold=0.5, huber_px=0.0,
+                        gate_m=0.0, flags_out=None):
+        """How far every joint can be trusted (mpe_posecov_batch): its 3 x 3 covariance in metres^2 from the cameras that
+        saw it, sigma_px^2 * A^-1 with A the normal matrix refine builds at that point (the Gauss-Newton approximation;
+        with huber_px > 0 the usual weighted one, not the sandwich estimator; include/mpe.h has the rule,
+        harness/uncertainty.py states it in numpy and the two agree bit for bit).  Arguments as for refine; sigma_px is the
+        standard deviation of a detection in x and in y.  It is the covariance of the per-frame estimate: untimed, and
+        silent on what smoothing or a bone fit do afterwards.  gate_m > 0 marks the computed joints whose sigma is larger
+        (MPE_POSECOV_GATED); flags_out (kind 'triang' only: True for a new tensor, or a u8 tensor like flags, flags itself
+        included) takes the flags with the gated joints cleared.  -> dict of device tensors: cov f64 [B,Pcap,J,6] in the
+        order (00, 01, 02, 11, 12, 22), sigma f64 (metres; -1 where not computed), status u8 (MPE_POSECOV_* bits),
+        n_views u8, all [B,Pcap,J], and flags when flags_out was given; one launch on the current stream."""
+        B, tri, joint_mask = self._pose_args(db, persons, n_persons, poses, flags, kind, joint_mask, ('est', 'triang'))
+        if flags_out is not None and flags_out is not False:
+            if not tri:
+                raise ValueError("flags_out needs kind 'triang': the gate clears joint flags, and kind 'est' has person flags")
+            if flags_out is True:
+                flags_out = torch.empty_like(flags)
+            elif (flags_out.dtype != flags.dtype or tuple(flags_out.shape) != tuple(flags.shape) or not flags_out.is_contiguous()
+                  or flags_out.device != flags.device):
+                raise ValueError('flags_out must be a contiguous tensor of the type, shape and device of flags')
+        else:
+            flags_out = None
+        shape = (B, self.pcap, self.J)
+        res = {'cov': torch.empty(shape + (6,), dtype=torch.float64, device=self.device),
+               'sigma': torch.empty(shape, dtype=torch.float64, device=self.device),
+               'status': torch.empty(shape, dtype=torch.uint8, device=self.device),
+               'n_views': torch.empty(shape, dtype=torch.uint8, device=self.device)}
+        a = L.mpe_posecov_args()
+        a.n_frames, a.pcap, a.n_joints = B, self.pcap, self.J
+        a.pose_f64, a.joint_flags, a.joint_mask, a.threshold = int(tri), int(tri), joint_mask, float(threshold)
+        a.huber_px, a.sigma_px, a.gate_m = float(huber_px), float(sigma_px), float(gate_m)
+        a.d_persons, a.d_n_persons, a.d_poses, a.d_flags = persons.data_ptr(), n_persons.data_ptr(), poses.data_ptr(), flags.data_ptr()
+        a.d_cov, a.d_sigma, a.d_status, a.d_n_views = res['cov'].data_ptr(), res['sigma'].data_ptr(), res['status'].data_ptr(), res['n_views'].data_ptr()
+        if flags_out is not None:
+            a.d_flags_out = flags_out.data_ptr()
+            res['flags'] = flags_out
+        self._chk(self.lib.mpe_posecov_batch(self.ctx, self._stream(), C.byref(db.struct), C.byref(a)))
+        return res
+
     def refine_timed(self, db, frame_start, persons, table_poses, table_flags, table_n_persons, table_ids, kind, lags, joint_mask=None,
                      threshold=0.5, max_iters=10, step_tol=1e-6, huber_px=0.0, out=None):
         """refine with every camera looking at the joint where its track says it was at that camera's time

@@ -427,6 +427,68 @@ typedef struct {
 } mpe_refine_args;
 int mpe_refine_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_refine_args *a);
 
+/* Uncertainty: the 3 x 3 covariance of every joint of every pose, in metres^2, from the cameras that saw it -- how far a
+ * joint can be trusted: five well-spread cameras and two nearly parallel ones leave mpe_refine_batch with the same flag.
+ * With independent pixel noise of standard deviation sigma_px in x and in y, the covariance of the minimiser of the
+ * reprojection cost is Sigma = sigma_px^2 * A^-1, A = sum_c w_c J_c^T J_c at that point: the Gauss-Newton approximation.
+ * With a Huber weight it is the usual weighted approximation, not the sandwich estimator.  It is the covariance of the
+ * per-frame estimate: untimed (camera lags are ignored, as in the DLT), and it says nothing about what smoothing or a
+ * bone-length fit do afterwards.  It describes d_poses as the minimum of the cost; on poses that are not refined it is the
+ * covariance the refined joint would have, to first order.  All binary64, every operation named below rounded on its own
+ * (nothing fused), quotients and roots correctly rounded.  harness/uncertainty.py states the same in numpy, and the two
+ * agree bit for bit; csrc/cov3.h holds the inverse for host and device.
+ * Inputs per (frame, person, joint): the observing cameras, n_views, x, y, the projection of X = the joint widened to f64,
+ *   rx, ry, e, the Jacobian jx_k, jy_k and the weight w_c are exactly those of mpe_refine_batch at its start, given the
+ *   same batch, d_persons / d_n_persons / d_poses / d_flags / pose_f64 / joint_flags / joint_mask / threshold / huber_px.
+ * Normal matrix.  A_kl (k <= l) starts at 0.0 and takes, per observing camera in increasing c,
+ *   A_kl = A_kl + w_c * (jx_k*jx_l + jy_k*jy_l)                           (the line of mpe_refine_batch)
+ * Inverse.  A = L D L^T by the lines of mpe_refine_batch without damping, then S = A^-1 written out:
+ *   D0 = A_00 ; L10 = A_01 / D0 ; L20 = A_02 / D0 ; D1 = A_11 - L10*A_01 ; t = A_12 - L20*A_01 ; L21 = t / D1
+ *   D2 = (A_22 - L20*A_02) - L21*t
+ *   i0 = 1 / D0 ; i1 = 1 / D1 ; i2 = 1 / D2 ; m = L10*L21 - L20
+ *   S22 = i2 ; S12 = -L21*i2 ; S02 = m*i2
+ *   S11 = i1 - L21*S12 ; S01 = (-L10)*i1 + m*S12
+ *   S00 = (i0 + (L10*L10)*i1) + m*S02
+ * Outputs.  s2 = sigma_px*sigma_px ; cov_kl = s2 * S_kl ; sigma = sqrt((cov_00 + cov_11) + cov_22), metres.
+ * Status per joint: no observing camera: 0.  Exactly one: MPE_POSECOV_FEW_VIEWS (A has rank 2; nothing is invented).  Two
+ *   or more and a pose that is not finite, or pc_2 <= 0 (or NaN) in an observing camera: _BAD_POSE.  Otherwise a pivot D0,
+ *   D1 or D2 that is not > 0, or an entry of cov or sigma that is not finite: _SINGULAR.  Otherwise _COMPUTED.  A joint
+ *   that is not computed gets cov = 0, sigma = -1 and n_views as counted.
+ * Gate.  With gate_m > 0 a COMPUTED joint whose sigma > gate_m takes _GATED as well (cov and sigma stay).  d_flags_out,
+ *   when given, receives d_flags with the GATED joints cleared and every other entry copied; it needs joint_flags = 1, is
+ *   [n_frames][pcap][J], and may be d_flags itself.  A joint that is not COMPUTED keeps its flag: the stage does not judge
+ *   what it cannot measure.
+ * Outputs per [n_frames][pcap][J]: d_cov [..][6] in the order (00, 01, 02, 11, 12, 22), d_sigma, d_status, d_n_views.
+ * One launch, ordered on `stream`; neither synchronises nor allocates; n_frames == 0 does nothing.  MPE_ERR_INVALID for a
+ * sigma_px that is not > 0 or not finite, a negative (or NaN) gate_m or huber_px, d_flags_out with joint_flags = 0,
+ * n_frames other than the batch's or n_joints other than the context's. */
+enum {
+    MPE_POSECOV_COMPUTED = 1,
+    MPE_POSECOV_FEW_VIEWS = 8,
+    MPE_POSECOV_BAD_POSE = 16,
+    MPE_POSECOV_SINGULAR = 32,
+    MPE_POSECOV_GATED = 64
+};
+typedef struct {
+    int32_t n_frames, pcap, n_joints;
+    int32_t pose_f64;              /* 0: d_poses f32 [n_frames][pcap][J][3]; 1: f64                  */
+    int32_t joint_flags;           /* 0: d_flags [n_frames][pcap] u8; 1: d_flags [n_frames][pcap][J] */
+    uint32_t joint_mask;           /* bit j: joint j is measured                                     */
+    float threshold;               /* 0.5, as for mpe_reproject_batch                                */
+    double huber_px;               /* pixels, >= 0; 0: every weight is 1                             */
+    double sigma_px;               /* pixels, > 0: the noise of a detection in x and in y            */
+    double gate_m;                 /* metres, >= 0; 0: no gate                                       */
+    const int32_t *d_persons;      /* [n_frames][pcap][V]                                            */
+    const int32_t *d_n_persons;    /* [n_frames]                                                     */
+    const void *d_poses;
+    const uint8_t *d_flags;
+    double *d_cov;                 /* [n_frames][pcap][J][6]                                         */
+    double *d_sigma;               /* [n_frames][pcap][J]                                            */
+    uint8_t *d_status, *d_n_views; /* [n_frames][pcap][J]                                            */
+    uint8_t *d_flags_out;          /* [n_frames][pcap][J] or NULL                                    */
+} mpe_posecov_args;
+int mpe_posecov_batch(mpe_ctx *ctx, void *stream, const mpe_batch *b, const mpe_posecov_args *a);
+
 /* Calibration: the camera extrinsics refined from a recording's own poses -- the other half of bundle adjustment: the 3D
  * joints are held fixed and every camera is moved to the minimum of the reprojection cost of the joints it observed.  A
  * pass (mpe_calib_batch over every batch of the recording) reduces all observations into one 6 x 6 system per camera on the

@@ -1164,12 +1164,14 @@ int mpe_status_queue(mpe_ctx *ctx, void *stream) {
     DeviceGuard dg(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (ctx->status_queued) {                       // an earlier half nobody waited for: its word must not be lost
-        HIPCHK(ctx, hipStreamSynchronize(s));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->status_stream));      // (the stream IT was ordered on, which need not be `s`)
         ctx->status_carry |= *ctx->h_status;
+        ctx->status_queued = false;
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_status, 0, sizeof(int32_t), s));
     ctx->status_queued = true;
+    ctx->status_stream = s;
     return MPE_OK;
 }
 
@@ -1180,6 +1182,8 @@ int mpe_status_wait(mpe_ctx *ctx, void *stream) {
         if (rc) return rc;
     }
     DeviceGuard dg(ctx);
+    // the pending read-back may have been ordered on another stream than `stream`: h_status is valid once THAT stream has drained
+    if (ctx->status_stream != static_cast<hipStream_t>(stream)) HIPCHK(ctx, hipStreamSynchronize(ctx->status_stream));
     HIPCHK(ctx, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     ctx->status_queued = false;
     const int32_t st = *ctx->h_status | ctx->status_carry;

@@ -940,6 +940,7 @@ class Engine:
         self._chk(self.lib.mpe_status_wait(self.ctx, self._stream()))
 
     def set_threshold(self, thr):
+        """The clustering threshold (mpe_set_threshold takes no stream: call this with nothing pending on the engine)."""
         if self._state.get('threshold', self._made_with['threshold']) == float(thr):
             return                          # (the C call re-uploads the whole device-side configuration, synchronously)
         self._chk(self.lib.mpe_set_threshold(self.ctx, float(thr)))
@@ -1047,7 +1048,7 @@ class Engine:
         gj = up(gt['joint'], torch.uint8) if gt['xyz'].shape[1] else torch.zeros((B, 1, self.J), dtype=torch.uint8, device=dev)
         gv = up(gt['valid'], torch.uint8) if gt['xyz'].shape[1] else torch.zeros((B, 1), dtype=torch.uint8, device=dev)
         gn = up(gt['n'], torch.int32)
-        sk = up(np.asarray(skip, dtype=np.uint8), torch.uint8)
+        sk = up(skip if isinstance(skip, torch.Tensor) else np.asarray(skip, dtype=np.uint8), torch.uint8)      # (a device tensor: taken as it is)
         out = {'table': torch.empty((B, gcap, self.pcap), dtype=torch.float64, device=dev),
                'assign': torch.empty((B, self.pcap), dtype=torch.int32, device=dev),
                'err': torch.empty((B, self.pcap), dtype=torch.float64, device=dev),

@@ -6,6 +6,7 @@ through the same C-ABI entry points the batched engine uses.  Engines without we
 theirs because weights are frozen into a context's padded device copies.
 """
 import os
+import threading
 
 import numpy as np
 
@@ -219,12 +220,19 @@ class _AheadSlot:
 
 class FrameAhead:
     """Clustering + MLP input rows of one frame, queued by GAT2.forward behind the scores it returned."""
-    __slots__ = ('out', 'version', 'threshold', 'engine', 'slot', 'gen', 'db')
+    __slots__ = ('out', 'version', 'threshold', 'engine', 'slot', 'gen', 'db', 'stream')
 
     def matches(self, outputs, threshold):
         import torch
         out = self.out
         if not getattr(self.engine, 'ctx', None):          # the matcher has replaced its engine since (new weights): nothing to wait on
+            return False
+        if self.stream != self.engine._stream().value:
+            # queued on another stream than the caller is on now (GAT2.forward under `with torch.cuda.stream(s)`, the proposals asked
+            # for outside it): the step-by-step route answers, on the caller's stream.  That stream is ordered behind neither the
+            # slot's copy nor the scores themselves, so the chain is waited for first: the status read-back is its last link, and
+            # status_wait synchronises the stream it was queued on (it raises what that read-back saw, as take_proposals would).
+            self.engine.status_wait()
             return False
         return (isinstance(outputs, torch.Tensor) and outputs.data_ptr() == out.data_ptr() and outputs.numel() == out.numel()
                 and outputs.dtype == out.dtype and outputs._version == self.version and float(threshold) == self.threshold
@@ -257,6 +265,7 @@ def queue_proposals(eng, db, scores, out):
     ah = FrameAhead()
     ah.out, ah.version, ah.engine, ah.slot, ah.gen, ah.db = out, out._version, eng, slot, slot.gen, db
     ah.threshold = float(eng._state.get('threshold', eng._made_with['threshold']))
+    ah.stream = stream.value
     return ah
 
 
@@ -268,7 +277,9 @@ def queue_proposals(eng, db, scores, out):
 # being waited for inside get_person_proposal_from_network_output.  GAT2.forward hands the queued scores out only if it is that
 # very engine (same weights: a changed parameter makes GAT2 build a new engine), the same output activation, the same stream,
 # the graph's own features; everything else is computed as before.  A frame nobody scores costs idle GPU time, nothing else.
-_matcher_hint = None
+# The hint is kept PER THREAD: a context belongs to one host thread at a time, so a dataset built on one thread
+# never enters the engine another thread's matcher noted.
+_matcher_hint = threading.local()
 
 
 class FrameScores:
@@ -276,18 +287,20 @@ class FrameScores:
 
 
 def note_matcher(eng):
-    global _matcher_hint
     import weakref
-    if _matcher_hint is None or _matcher_hint() is not eng:
-        _matcher_hint = weakref.ref(eng)
+    ref = getattr(_matcher_hint, 'ref', None)
+    if ref is None or ref() is not eng:
+        _matcher_hint.ref = weakref.ref(eng)
 
 
 def start_frame(graph):
-    """Queue scoring + proposals of a one-frame graph on the last matcher's engine (never raises: whatever is wrong with the frame
-    is reported where the step-by-step route reports it)."""
-    if _matcher_hint is None or not prefetch_enabled():
+    """Queue scoring + proposals of a one-frame graph on the engine of the last matcher THIS thread ran.  A frame the engine has no
+    room for (ValueError from check_capacity) is declined here and reported where the step-by-step route reports it; any other
+    failure (an MpeError from a launch, a bug) propagates."""
+    ref = getattr(_matcher_hint, 'ref', None)
+    if ref is None or not prefetch_enabled():
         return
-    eng = _matcher_hint()
+    eng = ref()
     try:
         if eng is None or not getattr(eng, 'ctx', None) or graph.batch_size != 1 or graph.M < 1 or getattr(graph.packed, 'en_pair', None) is not None:
             return
@@ -298,7 +311,7 @@ def start_frame(graph):
         fs.engine, fs.version, fs.sigmoid, fs.stream = eng, fs.out._version, bool(eng._state.get('gat_output', True)), eng._stream().value
         fs.ahead = queue_proposals(eng, db, sc, fs.out)
         graph.__dict__['_scored'] = fs
-    except Exception:
+    except ValueError:
         graph.__dict__.pop('_scored', None)
 
 

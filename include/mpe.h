@@ -1241,11 +1241,18 @@ int mpe_edge_softmax_aggregate(mpe_ctx *ctx, void *stream, const mpe_batch *b, i
 int mpe_sync_status(mpe_ctx *ctx, void *stream);
 /* The same in two halves: mpe_status_queue orders the read-back (into page-locked memory) and the reset of the word behind everything
  * queued on `stream` so far and returns at once; mpe_status_wait synchronises `stream` and reports what the read-back saw (it queues
- * one itself if none is pending).  Bits raised by work queued after mpe_status_queue are reported by the next call. */
+ * one itself if none is pending).  Bits raised by work queued after mpe_status_queue are reported by the next call.
+ * The context remembers the stream a pending read-back was ordered on: mpe_status_wait on another stream synchronises that stream
+ * as well before it reads the word, and a second mpe_status_queue (on any stream) waits for the pending one and carries its bits
+ * into the next report -- no bit is lost and none is read early, whichever streams the two halves are given.  (A stream with a
+ * read-back pending on it must stay alive until that read-back has been waited for.) */
 int mpe_status_queue(mpe_ctx *ctx, void *stream);
 int mpe_status_wait(mpe_ctx *ctx, void *stream);
 
-/* CLASSIFICATION_THRESHOLD of get_person_proposal_from_network_output (default from mpe_config) */
+/* CLASSIFICATION_THRESHOLD of get_person_proposal_from_network_output (default from mpe_config).  It takes no stream: the
+ * device-side configuration is rewritten with a blocking copy that is ordered against nothing a non-blocking stream holds.  Call
+ * it only with nothing pending on the context (after mpe_sync_status / a synchronisation of every stream the context was given
+ * work on); clustering that is still queued may otherwise run with either threshold. */
 int mpe_set_threshold(mpe_ctx *ctx, float threshold);
 
 /* get_person_proposal_from_network_output on caller-provided scores. */
